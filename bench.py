@@ -8,6 +8,11 @@ over one batch of synthetic nginx log that is ALREADY RESIDENT IN HBM when the t
 Workload at N=1 = BASELINE.json configs[1]: 100K mixed IoCs (40K IPv4 + 10K CIDR + 35K domains + 15K hashes),
 10M nginx-style lines, 1x MI355X. For N>1 every rank scans its own 10M-line block (line-block sharding, no
 collective on the data path; `scaling` = weak). Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step` = one timed step).
+`--full` adds every other leg (records left in HBM, batches in flight, the host-buffer entry, scatter / gather, the
+measured copy peak, the CPU baselines and the same-run parity check). `--dump-outputs DIR` writes the last timed step's
+hit records as .npy files, so that two builds can be compared output for output on identical input.
 """
 import argparse
 import ctypes
@@ -24,6 +29,39 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s s
 
 
 fetch_hits = 9
+DUMP_LIMIT = 64 << 20   # --dump-outputs: bytes of .npy data at most
+
+
+def hit_arrays(res):
+    """The hit records of a host-resident ScanResult as float64 arrays in canonical order (the device order of fetch modes 1 / 9
+    varies from run to run): hits (n, 6) = [start, end, item type, kind (0 ip, 1 pattern), prefix_len, ip_data_offset] and
+    ids (m, 3) = [row of hits, pattern id, data offset]."""
+    import numpy as np
+    import matchy_amd as M
+    types = {name: i for i, name in enumerate(M.ITEM_TYPE_NAMES)}
+    recs = sorted(((h["start"], h["end"], types[h["type"]], 0 if h["kind"] == "ip" else 1, h["prefix_len"], h["ip_data_offset"],
+                    tuple(h["ids"]), tuple(h["offs"])) for h in res.hits()))
+    hits = np.array([r[:6] for r in recs], dtype=np.float64).reshape(-1, 6)
+    ids = np.array([(i, pid, off) for i, r in enumerate(recs) for pid, off in zip(r[6], r[7])], dtype=np.float64).reshape(-1, 3)
+    return hits, ids
+
+
+def dump_outputs(out_dir, counts, hits, ids):
+    """--dump-outputs: counts / hits / hit_ids as .npy files; hit rows beyond DUMP_LIMIT are thinned to a sample drawn with a fixed seed."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    row_bytes = hits.shape[1] * 8 + (ids.nbytes / max(1, len(hits)))
+    if hits.nbytes + ids.nbytes > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(len(hits), int(0.9 * DUMP_LIMIT / row_bytes), replace=False))
+        new_row = np.full(len(hits), -1, dtype=np.int64)
+        new_row[keep] = np.arange(len(keep))
+        ids = ids[np.isin(ids[:, 0].astype(np.int64), keep)]
+        ids[:, 0] = new_row[ids[:, 0].astype(np.int64)]
+        hits = hits[keep]
+    np.save(out / "counts.npy", np.array(counts, dtype=np.float64))
+    np.save(out / "hits.npy", hits)
+    np.save(out / "hit_ids.npy", ids)
 
 
 def run_strong(args, rank, local_rank, world, rehearse, torch, dist, dev, coll_dev):
@@ -69,7 +107,7 @@ def run_strong(args, rank, local_rank, world, rehearse, torch, dist, dev, coll_d
         [t.start() for t in ths]; [t.join() for t in ths]
         dlog[bi * cap: bi * cap + total].copy_(stage[:total])
         torch.cuda.synchronize()
-        if len(keep_host) < args.e2e_batches:
+        if args.full and len(keep_host) < args.e2e_batches:
             h = torch.empty(total, dtype=torch.uint8).pin_memory()
             h.copy_(stage[:total])
             keep_host.append(h)
@@ -103,6 +141,20 @@ def run_strong(args, rank, local_rank, world, rehearse, torch, dist, dev, coll_d
     elapsed = time.perf_counter() - t0
     agg = sharding.aggregate(dist, world, coll_dev, elapsed, nbytes, counts[0], counts[2], counts[1])
     kagg = sharding.aggregate(dist, world, coll_dev, kernel_ms * 1e-3, 0, 0, 0, 0)
+    # ---- --dump-outputs: rank 0's records of a pass are only readable batch by batch, so the pass runs once more, untimed, and
+    # every batch's records are kept (same input, same records in canonical order); hits.npy carries the batch as a first column
+    if args.dump_outputs is not None and rank == 0:
+        import numpy as np
+        all_hits, all_ids, n_rows = [], [], 0
+        for bi, sz in enumerate(sizes):
+            r = scanner.scan_device(dlog.data_ptr() + bi * cap, sz, stream=stream, fetch_mode=fetch_hits)
+            h, ids = hit_arrays(r)
+            r.close()
+            all_hits.append(np.hstack([np.full((len(h), 1), bi, dtype=np.float64), h]))
+            ids[:, 0] += n_rows
+            all_ids.append(ids)
+            n_rows += len(h)
+        dump_outputs(args.dump_outputs, counts[:3], np.vstack(all_hits), np.vstack(all_ids))
     # ---- end to end from pinned host memory: two scanners, two threads, alternating batches
     e2e = None
     if keep_host:
@@ -131,7 +183,7 @@ def run_strong(args, rank, local_rank, world, rehearse, torch, dist, dev, coll_d
     # same-run parity on the head of the job: the first lines of rank 0's first batch (the generator is a pure function of the line
     # index, so the sample is generated again on the host) through the same scanner and through the oracle
     parity = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         from oracle import oracle
         n_par = min(args.cpu_lines, batches[0][1], 1_000_000)
         sample = synth.make_log(cfg, batches[0][0], n_par)
@@ -200,7 +252,7 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive host-buffer measurement")
     ap.add_argument("--case-insensitive", action="store_true", help="build the database with match_mode 1 (matchy build -i)")
-    ap.add_argument("--pipelined", type=int, default=3, help="N > 1: after the timed steps, time the same K steps again with N batches in flight per GPU "
+    ap.add_argument("--pipelined", type=int, default=3, help="--full, N > 1: after the timed steps, time the same K steps again with N batches in flight per GPU "
                     "(scanners on their own streams) and report it as the extra object `pipelined` (never as `value`). 0 / 1 = skip "
                     "(tools/prof.sh does, so that a profile shows every kernel of a step running alone)")
     ap.add_argument("--records", choices=["compact", "full"], default="compact", help="host-resident hit records of the timed steps: compact = IPv4 results "
@@ -216,7 +268,17 @@ def main():
                     help="shape of the synthetic log (tools/synthgen.cpp): nginx = the BASELINE workload; the others answer 'what does the number do on other "
                          "input' (BASELINE.md §3). skewed-halves: the first half of every rank's block is prose with nothing to extract, the second half is ip-dense")
     ap.add_argument("--no-scatter-gather", action="store_true", help="skip the one-process scatter / gather leg (matchy_multi_scanner over all GPUs of the job)")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, run every other leg as well: records left in HBM, batches in flight "
+                    "(--pipelined), the measured copy peak, the host-buffer entry, scatter / gather, the CPU baselines and the same-run parity check "
+                    "(strong scaling: end to end and parity). Without it a run sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy "
+                    "(float64): counts.npy = [lines, candidates, hits]; hits.npy = one row per hit record [start, end, item type, kind (0 ip, 1 pattern), "
+                    "prefix_len, ip_data_offset] in canonical order; hit_ids.npy = [row of hits.npy, pattern id, data offset] per pattern id. Above "
+                    f"{DUMP_LIMIT >> 20} MB in all, a fixed seeded sample of the hit rows is written. --scaling strong: every batch of a pass, "
+                    "with the batch index as the first column of hits.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.scaling == "strong":
         if "--lines" not in " ".join(sys.argv):
             args.lines = 100_000_000
@@ -315,10 +377,15 @@ def main():
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream().cuda_stream
 
-    def step():
+    last_res = [None]
+
+    def step(keep=False):
         res = scanner.scan_device(dlog.data_ptr(), nbytes, stream=stream, fetch_mode=fetch_hits)
         out = (res.lines, res.candidates, res.n_hits)
-        res.close()
+        if keep:
+            last_res[0] = res   # --dump-outputs: the records stay readable until the scanner's next scan
+        else:
+            res.close()
         return out
 
     # --pipelined N > 1: N scanners, each on its own stream; a step submits a batch to the next scanner after collecting
@@ -372,11 +439,12 @@ def main():
     for _ in range(args.warmup):
         counts = step()
     tok_ms, look_ms, rare_ms, val_ms = [], [], [], []
+    dump_last = args.dump_outputs is not None and rank == 0
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         ts0 = time.perf_counter()
-        counts = step()
+        counts = step(keep=dump_last and i == args.steps - 1)
         if os.environ.get("BENCH_DEBUG"):
             print(f"step {1e3 * (time.perf_counter() - ts0):.3f} ms", file=sys.stderr)
         t = scanner.timing_ms()
@@ -391,6 +459,11 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_bytes / (elapsed / args.steps) / 1e9
 
+    # ---- --dump-outputs: what the last timed step handed its caller (rank 0's batch)
+    if last_res[0] is not None:
+        dump_outputs(args.dump_outputs, counts, *hit_arrays(last_res[0]))
+        last_res[0].close()
+
     # ---- the same K steps with the hit records left in device memory (MATCHY_SCAN_FETCH_DEVICE): what a consumer that stays on
     # the GPU gets, and the only way a workload where nearly every line hits is not bound by 16 bytes per hit over PCIe
     def step_dev():
@@ -398,24 +471,26 @@ def main():
         out = (res.lines, res.candidates, res.n_hits)
         res.close()
         return out
-    for _ in range(2):
-        dcounts = step_dev()
-    barrier()
-    td0 = time.perf_counter()
-    for _ in range(args.steps):
-        dcounts = step_dev()
-    barrier()
-    tdev = time.perf_counter() - td0
-    dagg = sharding.aggregate(dist, world, coll_dev, tdev, nbytes, dcounts[0], dcounts[2], dcounts[1])
-    device_results = {"value": round(float(dagg["bytes"]) / (dagg["elapsed_s"] / args.steps) / 1e9, 3), "unit": "GB/s",
-                      "ms_per_step": round(dagg["elapsed_s"] / args.steps * 1e3, 4), "same_counts": bool(tuple(dcounts) == tuple(counts)),
-                      "note": "hit records stay in HBM (fetch_mode 4); `value` above moves them to host memory"}
+    device_results = None
+    if args.full:
+        for _ in range(2):
+            dcounts = step_dev()
+        barrier()
+        td0 = time.perf_counter()
+        for _ in range(args.steps):
+            dcounts = step_dev()
+        barrier()
+        tdev = time.perf_counter() - td0
+        dagg = sharding.aggregate(dist, world, coll_dev, tdev, nbytes, dcounts[0], dcounts[2], dcounts[1])
+        device_results = {"value": round(float(dagg["bytes"]) / (dagg["elapsed_s"] / args.steps) / 1e9, 3), "unit": "GB/s",
+                          "ms_per_step": round(dagg["elapsed_s"] / args.steps * 1e3, 4), "same_counts": bool(tuple(dcounts) == tuple(counts)),
+                          "note": "hit records stay in HBM (fetch_mode 4); `value` above moves them to host memory"}
 
     # ---- the same K steps once more with several batches in flight (how a streaming host drives the scanners: submit /
     # wait, one stream per scanner). Reported beside the headline numbers, never instead of them: with overlapping
     # batches the kernels time-share the GPU and their individual durations say nothing about the kernels.
     pipelined = None
-    if args.pipelined > 1:
+    if args.full and args.pipelined > 1:
         make_pipeline_scanners()
         for _ in range(2 * len(scanners)):
             step_pipelined()
@@ -470,7 +545,7 @@ def main():
 
     # ---- the box's own copy bandwidth, measured in this run (report the spec peak and the measured one)
     peak_measured = None
-    if rank == 0:
+    if args.full and rank == 0:
         nb = 1 << 30
         a = torch.empty(nb, dtype=torch.uint8, device=dev); b = torch.empty(nb, dtype=torch.uint8, device=dev)
         a.fill_(1)
@@ -487,7 +562,7 @@ def main():
     # ---- PCIe-inclusive rate of the host-buffer entry (matchy_scanner_scan from pinned host memory: H2D in < 1 GiB pieces,
     # scan, canonical-order sort on the GPU, hit records back). Reported beside the headline, never as `value`.
     end_to_end = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
         pinned.copy_(host[:nbytes])
         sc2 = M.Scanner(db, extract_flags=args.extract_flags, device=local_rank)
@@ -512,7 +587,7 @@ def main():
     # is this rank's 10 M lines again: generating `world` different blocks would take longer than the driver's run, and the
     # mechanics — H2D per device, scan, ordered gather — do not depend on the bytes.
     scatter_gather = None
-    if not args.no_scatter_gather:
+    if args.full and not args.no_scatter_gather:
         barrier()
         if rank == 0:
             import numpy as np
@@ -591,7 +666,7 @@ def main():
     cpu_t1 = None
     cpu_all = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # ---- CPU baseline: the oracle ("port" of the reference CPU path) on a bounded sample of the SAME log,
         # all host cores, newline-aligned chunks + 10 000-entry per-thread LRU like `matchy match` defaults.
         from oracle import oracle
@@ -669,25 +744,29 @@ def main():
                               "behind it as one interval (k_validate_dom -> k_lookup on the scan's stream; tokens / IPv6 / e-mail, the undecided domains "
                               "and k_rare with their own lookups on three side streams); per-kernel durations: profiles/r04_bench_c2_summary.txt, r04_step_timeline.txt",
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "peak_measured": peak_measured, "peak_measured_note": "device-to-device copy of 1 GiB in this run, read + write bytes / time",
+                         "peak_measured": peak_measured, "peak_measured_note": "device-to-device copy of 1 GiB in this run (--full), read + write bytes / time",
                          "traffic": traffic, "kernel": dom_name, "algorithmic_bytes_per_launch": nbytes, "traffic_source": tr_note},
             "roofline_pipeline": {"bound": "hbm", "achieved": round(pipe_achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                   "frac": round(pipe_achieved / HBM_PEAK_GBS, 4), "kernels_ms": round(pipe_ms, 4)},
-            "cpu_baseline": cpu,
-            "cpu_baseline_t1": cpu_t1,
-            "cpu_baseline_all": cpu_all,
-            # what the reference documents for itself (unstated hardware) — the oracle port above is a restatement, not the
-            # Rust binary, and its single-thread rate is below these ranges: read the GPU/CPU ratio against BOTH
-            "reference_documented": {"extractor_single_thread_MBps": "~450 (DEVELOPMENT.md:266)", "match_sequential_MBps": "200-500 (book/src/commands/matchy-match.md:343)",
-                                     "match_parallel_MBps": "400-2000 depending on core count (matchy-match.md:344)",
-                                     "extract_plus_lookup_MBps": "100-300 (book/src/guide/querying.md:187)"} if cpu else None,
-            "end_to_end": end_to_end,
-            "scatter_gather": scatter_gather,
             "numa": numa,
-            "device_results": device_results,
-            "pipelined": pipelined,
-            "parity_vs_oracle": parity,
         }
+        if args.full:
+            # the legs only a --full run measures
+            out.update({
+                "cpu_baseline": cpu,
+                "cpu_baseline_t1": cpu_t1,
+                "cpu_baseline_all": cpu_all,
+                # what the reference documents for itself (unstated hardware) — the oracle port above is a restatement, not the
+                # Rust binary, and its single-thread rate is below these ranges: read the GPU/CPU ratio against BOTH
+                "reference_documented": {"extractor_single_thread_MBps": "~450 (DEVELOPMENT.md:266)", "match_sequential_MBps": "200-500 (book/src/commands/matchy-match.md:343)",
+                                         "match_parallel_MBps": "400-2000 depending on core count (matchy-match.md:344)",
+                                         "extract_plus_lookup_MBps": "100-300 (book/src/guide/querying.md:187)"} if cpu else None,
+                "end_to_end": end_to_end,
+                "scatter_gather": scatter_gather,
+                "device_results": device_results,
+                "pipelined": pipelined,
+                "parity_vs_oracle": parity,
+            })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

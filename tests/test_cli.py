@@ -186,11 +186,11 @@ def test_match_config1_end_to_end(cli, tmp_path, oracle):
 @pytest.mark.parametrize("prog", ["test_c_api", "test_c_api_extensions"])
 def test_reference_c_test_programs(prog, tmp_path):
     """The reference's own C test programs (crates/matchy/tests/test_c_api*.c), compiled unmodified against the
-    reference's header and linked with libmatchy_amd.so by `make -C oracle ref_c_tests` (needs /root/reference at build
-    time; the binaries travel to the GPU box). They must pass as they do against the reference library."""
-    exe = ROOT / "tests" / "ref_c_bin" / prog
+    reference's header and linked with libmatchy_amd.so by `make -C oracle ref_c_tests` into oracle/_ref/ (needs the reference's
+    sources at build time). They must pass as they do against the reference library."""
+    exe = ROOT / "oracle" / "_ref" / prog
     if not exe.exists():
-        pytest.skip("tests/ref_c_bin not built (no /root/reference at build time)")
+        pytest.skip("oracle/_ref not built (the reference's sources were absent at build time)")
     r = subprocess.run([str(exe)], capture_output=True, timeout=300, cwd=tmp_path)
     out = r.stdout.decode("utf-8", "replace")
     assert r.returncode == 0, out[-2000:] + r.stderr.decode("utf-8", "replace")[-500:]

@@ -10,13 +10,13 @@ O=gpurun_out/ev_$TAG
 mkdir -p $O
 if [ "$PART" = A ]; then
   bash tools/prof.sh $TAG > $O/prof.log 2>&1 || exit 1
-  timeout -k 10 500 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || exit 1
+  timeout -k 10 500 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || exit 1
   bash tools/tl.sh $TAG > $O/step_timeline.txt 2>&1 || exit 1
 elif [ "$PART" = B ]; then
   for c in c3 c3b c4 c5; do
-    timeout -k 10 400 python bench.py --config $c --lines 10000000 --steps 10 --cpu-lines 1000000 --no-e2e > $O/bench_${c}_10Mlines.json 2> $O/bench_$c.err || exit 1
+    timeout -k 10 400 python bench.py --full --config $c --lines 10000000 --steps 10 --cpu-lines 1000000 --no-e2e > $O/bench_${c}_10Mlines.json 2> $O/bench_$c.err || exit 1
   done
-  timeout -k 10 600 python bench.py --scaling strong --lines 20000000 --steps 2 --warmup 1 > $O/strong_scaling_1gpu_20Mlines.json 2> $O/strong.err || exit 1
+  timeout -k 10 600 python bench.py --full --scaling strong --lines 20000000 --steps 2 --warmup 1 > $O/strong_scaling_1gpu_20Mlines.json 2> $O/strong.err || exit 1
 else
   timeout -k 10 300 python tools/cli_fixed.py 30 > $O/cli_end_to_end.txt 2>&1 || exit 1
   timeout -k 10 300 python tools/cli_e2e.py 10000000 6 >> $O/cli_end_to_end.txt 2>&1 || exit 1

@@ -4,7 +4,7 @@ TAG=$1; shift
 O=gpurun_out/shapes_$TAG
 mkdir -p $O
 for sh in nginx jsonl-app ip-dense url-heavy hash-dense skewed-halves; do
-  timeout -k 10 300 python bench.py --log-shape $sh --cpu-lines 500000 --steps 20 --no-e2e --no-scatter-gather "$@" > $O/$sh.json 2> $O/$sh.err || echo FAILED $sh
+  timeout -k 10 300 python bench.py --full --log-shape $sh --cpu-lines 500000 --steps 20 --no-e2e --no-scatter-gather "$@" > $O/$sh.json 2> $O/$sh.err || echo FAILED $sh
   python3 - $sh $O/$sh.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])

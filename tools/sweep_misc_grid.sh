@@ -7,7 +7,7 @@ for spec in "$@"; do
   set -- $spec
   sh=$1; vm=$2; shift 2
   for g in "$@"; do
-    timeout -k 10 200 env MATCHY_AMD_MISC_GRID_V$vm=$g python bench.py --log-shape $sh --no-cpu --steps 20 --no-e2e --no-scatter-gather > $O/$sh.$vm.$g.json 2> $O/$sh.$vm.$g.err || { echo FAILED $sh $vm $g; exit 1; }
+    timeout -k 10 200 env MATCHY_AMD_MISC_GRID_V$vm=$g python bench.py --full --log-shape $sh --no-cpu --steps 20 --no-e2e --no-scatter-gather > $O/$sh.$vm.$g.json 2> $O/$sh.$vm.$g.err || { echo FAILED $sh $vm $g; exit 1; }
     python3 - $sh $vm $g $O/$sh.$vm.$g.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[4]) if l.startswith("{")][-1])

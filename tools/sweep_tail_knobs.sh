@@ -4,7 +4,7 @@ O=gpurun_out/gridsweep; mkdir -p $O
 for spec in "$@"; do
   set -- $spec
   name=$1; sh=$2; shift 2
-  timeout -k 10 200 env X=1 "$@" python bench.py --log-shape $sh --no-cpu --steps 20 --no-e2e --no-scatter-gather > $O/$name.json 2> $O/$name.err || { echo FAILED $name; exit 1; }
+  timeout -k 10 200 env X=1 "$@" python bench.py --full --log-shape $sh --no-cpu --steps 20 --no-e2e --no-scatter-gather > $O/$name.json 2> $O/$name.err || { echo FAILED $name; exit 1; }
   python3 - $name $O/$name.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
