@@ -829,8 +829,10 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
     try {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         const bool sorted = (fetch_mode & 2) != 0;
-        const bool compact = compact_mode(fetch_mode);
-        h->sc->scan_device(reinterpret_cast<const uint8_t*>(dptr), (uint32_t)len, true, st, (fetch_mode & 1) && !sorted, /*fork=*/true, h->sc->slices(), compact);
+        ScanRequest rq;
+        rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
+        h->sc->scan_device(rq, st);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
         if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); return MATCHY_SUCCESS; }
@@ -851,8 +853,10 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
     ScannerH* h = reinterpret_cast<ScannerH*>(s);
     try {
         const bool sorted = (fetch_mode & 2) != 0;
-        h->sc->scan_device(reinterpret_cast<const uint8_t*>(dptr), (uint32_t)len, true, reinterpret_cast<hipStream_t>(stream), (fetch_mode & 1) && !sorted, /*fork=*/false, 0,
-                           compact_mode(fetch_mode));
+        ScanRequest rq;   // not forked: several batches in flight (ScanRequest::fork)
+        rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
+        h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
         return MATCHY_SUCCESS;
     } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }

@@ -564,7 +564,7 @@ void Scanner::ensure_mirror_c4(uint32_t recs) {
 
 namespace {
 // grid multipliers (workgroups per CU) of k_anchor / k_validate_dom / k_lookup: what is resident at once (grid-stride kernels; a
-// larger grid only adds a partially filled second round). MATCHY_AMD_GRID=a,v,l overrides for experiments.
+// larger grid only adds a partially filled second round).
 // k_anchor: one full round of resident workgroups; k_validate_dom: one; k_lookup: 2 per CU measured best (the string
 // lookups are chains of dependent loads: more waves in flight only add contention on the random table accesses).
 void grid_multipliers(bool filter_ac, int (&gm)[3]) {
@@ -573,11 +573,6 @@ void grid_multipliers(bool filter_ac, int (&gm)[3]) {
     // that run beside it (k_validate over tokens / IPv6 / e-mail anchors: 26 KB per workgroup), which then start when
     // k_validate_dom's workgroups retire (measured: tail 0.250 -> 0.232 ms)
     gm[0] = occ_a; gm[1] = std::min(filter_ac ? occ_v_ac : occ_v, 4); gm[2] = 2;
-    if (const char* g = getenv("MATCHY_AMD_GRID")) {   // 0 keeps the default of that kernel
-        int o[3] = {0, 0, 0};
-        (void)sscanf(g, "%d,%d,%d", &o[0], &o[1], &o[2]);
-        for (int k = 0; k < 3; ++k) if (o[k] > 0) gm[k] = o[k];
-    }
     for (int& m : gm) m = std::max(1, std::min(m, 64));
 }
 }  // namespace
@@ -585,16 +580,23 @@ void grid_multipliers(bool filter_ac, int (&gm)[3]) {
 // workgroups for a list kernel: the default while the previous scan's list was short, else one workgroup per `per_wg` entries of it,
 // at most max_per_cu per CU (workgroups beyond the end of a list leave at once)
 int Scanner::grid_for(uint32_t n_hint, uint32_t per_wg, int dflt, int max_per_cu) const {
-    static const bool fixed = getenv("MATCHY_AMD_FIXED_GRIDS") != nullptr;
-    if (fixed) return dflt;
     const uint64_t want = ((uint64_t)n_hint + per_wg - 1) / per_wg;
     return (int)std::max<uint64_t>((uint64_t)dflt, std::min<uint64_t>(want, (uint64_t)n_cu_ * (uint64_t)max_per_cu));
 }
 
+namespace {
+// point the parameters of a kernel at the candidate list `l` of a slice and at the counter `n` of its entries
+void point_at(TokParams& t, const DevBuf<Candidate>& l, uint32_t* n) { t.cands = l.p; t.cand_cap = (uint32_t)l.n; t.n_cand = n; }
+void point_at(LookupParams& p, const DevBuf<Candidate>& l, const uint32_t* n) { p.cands = l.p; p.cand_cap = (uint32_t)l.n; p.n_in = n; }
+}  // namespace
+
 // Kernel parameters of slice `sl` for the byte range [lo, hi) of the batch (hi = len + 1 for the range that ends the batch).
 // The lists and counters are the slice's own; the final record arrays (and the counters that hand out their slots: slice 0's)
 // are shared by all slices.
-void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t lo, uint32_t hi, bool lookup, bool host_mirror, SliceLaunch& L) {
+void Scanner::slice_params(int sl, const ScanRequest& rq, uint32_t lo, uint32_t hi, SliceLaunch& L) {
+    const uint8_t* dptr = rq.ptr;
+    const uint32_t len = rq.len;
+    const bool lookup = rq.lookup;
     Work& w = work_[sl];
     ScanCounters* ctr = counters_.p + sl;
     TokParams& tp = L.tp;
@@ -608,7 +610,7 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
     tp.filter_ac = (lookup && ac_ok) ? 1u : 0u;
     tp.filter_lit = (lookup && (!ddb_->view.has_glob || ac_ok)) ? 1u : 0u;
     if (const char* dbg = getenv("MATCHY_AMD_DEBUG")) tp.debug = (uint32_t)atoi(dbg);
-    tp.cands = w.cands.p; tp.cand_cap = (uint32_t)w.cands.n; tp.n_cand = &ctr->n_cand;
+    point_at(tp, w.cands, &ctr->n_cand);
     tp.cands_a = w.cands_a.p; tp.cand_a_cap = (uint32_t)w.cands_a.n;
     // IPv4 candidates are listed sparsely when the /24 bitmap of the database filters most of the address space
     tp.cand_chunk = (lookup && ddb_->view.ip_bm24_permille <= 250) ? 64u : 1024u;
@@ -627,8 +629,7 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
         // Short ranges get SEG_MIN segments and fewer waves.
         const uint64_t waves = (uint64_t)n_cu_ * L.gm[0] * 4;
         const uint64_t span = (uint64_t)hi - lo;
-        uint64_t sb = ((span + waves - 1) / waves + SEG_ALIGN - 1) / SEG_ALIGN * SEG_ALIGN;
-        if (const char* e = getenv("MATCHY_AMD_SEG_KB")) sb = (uint64_t)atoi(e) * 1024 / SEG_ALIGN * SEG_ALIGN;
+        const uint64_t sb = ((span + waves - 1) / waves + SEG_ALIGN - 1) / SEG_ALIGN * SEG_ALIGN;
         tp.seg_bytes = (uint32_t)std::min<uint64_t>(SEG_MAX, std::max<uint64_t>(SEG_MIN, sb));
         tp.n_segs = (uint32_t)((span + tp.seg_bytes - 1) / tp.seg_bytes);
         tp.seg_base = lo; tp.scan_end = hi;
@@ -668,7 +669,7 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
         pp.glob_offsets = ddb_->glob_offsets.p; pp.n_glob = ddb_->n_glob_offsets;
         pp.out = final_.p; pp.out_cap = (uint32_t)final_.n;
         pp.out_ids = final_ids_.p; pp.out_offs = final_offs_.p; pp.out_ids_cap = (uint32_t)final_ids_.n;
-        if (host_mirror) {
+        if (rq.host_mirror) {
             uint8_t* mb = (uint8_t*)mirror_;
             pp.host_out = (FinalHit*)mb; pp.host_cap = mirror_cap_;
             pp.host_ids = (uint32_t*)(mb + (size_t)mirror_cap_ * sizeof(FinalHit));
@@ -677,7 +678,7 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
         }
         if (compact_) {
             pp.c4_out = c4_.p; pp.c4_cap = (uint32_t)c4_.n;
-            if (host_mirror) { pp.host_c4 = mirror_c4_; pp.host_c4_cap = mirror_c4_cap_; }
+            if (rq.host_mirror) { pp.host_c4 = mirror_c4_; pp.host_c4_cap = mirror_c4_cap_; }
         }
         pp.counters = counters_.p;   // n_final / n_final_ids of slice 0 hand out the slots of the shared record arrays
         // k_lookup writes the final records itself (the PCIe writes of the mirror overlap the lookups); only the
@@ -688,15 +689,14 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
         // (k_anchor.hip v4_lookup_flush) — their hit records, most of the result traffic of a log scan, then cross the bus under
         // the streaming pass instead of behind it. Dense lists (a database that answers most addresses) keep the lookup kernel:
         // there the walks are the work, and a kernel of lanes that do nothing else hides their latency better.
-        static const bool env_no_inline = getenv("MATCHY_AMD_INLINE_V4") && atoi(getenv("MATCHY_AMD_INLINE_V4")) == 0;
-        tp.inline_v4 = (!env_no_inline && tp.filter_v4 && tp.cand_chunk == 64u) ? 1u : 0u;
+        tp.inline_v4 = (tp.filter_v4 && tp.cand_chunk == 64u) ? 1u : 0u;
         tp.pk = pp;
     }
     // a database without any IPv4 answer lists no IPv4 candidate (the /24 bitmap is empty): nothing to look up
     L.ip_pass = lookup && !tp.inline_v4 && (ddb_->view.ip_bm24_any || !tp.filter_v4);
     L.la = lp;
     if (L.ip_pass) {
-        L.la.cands = w.cands_a.p; L.la.cand_cap = (uint32_t)w.cands_a.n; L.la.n_in = &ctr->n_cand_a;
+        point_at(L.la, w.cands_a, &ctr->n_cand_a);
         L.la.glob_work = nullptr; L.la.glob_work_cap = 0;
     }
     // Forked scans of a database without globs: the third stream (tokens, IPv6 / e-mail anchors, k_rare) gets a candidate list and a
@@ -712,63 +712,35 @@ void Scanner::slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t l
         // candidates) on a stream of their own; what spills there is listed with bit 31 set and read from cands_alt by the spill pass
         lp.cands_alt = w.cands_d.p; lp.cand_alt_cap = (uint32_t)w.cands_d.n;
         L.ld = lp;
-        L.ld.cands = w.cands_d.p; L.ld.cand_cap = (uint32_t)w.cands_d.n; L.ld.n_in = &ctr->n_cand_d;
+        point_at(L.ld, w.cands_d, &ctr->n_cand_d);
         L.ld.glob_work = nullptr; L.ld.glob_work_cap = 0; L.ld.early_glob = 0; L.ld.spill_tag = 1u;
     }
     if (L.split_misc) {
-        L.ld.cands = w.cands_d.p; L.ld.cand_cap = (uint32_t)w.cands_d.n; L.ld.n_in = &ctr->n_cand_d;
-        L.lm.cands = w.cands_m.p; L.lm.cand_cap = (uint32_t)w.cands_m.n; L.lm.n_in = &ctr->n_cand_m;
-        L.lr.cands = w.cands_r.p; L.lr.cand_cap = (uint32_t)w.cands_r.n; L.lr.n_in = &ctr->n_cand_r;
+        point_at(L.ld, w.cands_d, &ctr->n_cand_d);
+        point_at(L.lm, w.cands_m, &ctr->n_cand_m);
+        point_at(L.lr, w.cands_r, &ctr->n_cand_r);
     }
     // one workgroup on every other CU: enough lanes to keep the result traffic on the bus, and the validation kernels beside it
     // keep nearly all of their resident waves (128 / 256 / 512 workgroups measured 1.199 / 1.213 / 1.241 ms per headline batch)
     // (dense lists — a database that answers most addresses, C5 — are latency-bound trie walks for every line: full grid)
-    static const int ip_wgs = getenv("MATCHY_AMD_IPGRID") ? atoi(getenv("MATCHY_AMD_IPGRID")) : 0;
     L.ip_dense = tp.cand_chunk != 64u;
-    L.ip_grid = ip_wgs > 0 ? ip_wgs : L.ip_dense ? n_cu_ * L.gm[2] : std::max(1, n_cu_ / 2);
+    L.ip_grid = L.ip_dense ? n_cu_ * L.gm[2] : std::max(1, n_cu_ / 2);
 }
 
-// How a device-resident batch of `len` bytes is cut into slices: cuts[0] = 0 < cuts[1] < ... < cuts[n] = len + 1, inner cuts on
-// multiples of one full round of k_anchor segments (waves x SEG_ALIGN bytes), so that every wave of a slice gets a segment of
-// the same size. MATCHY_AMD_SLICES = "n" (equal slices) or "a,b,c,..." (relative sizes) overrides the default.
+// How a device-resident batch of `len` bytes is cut into `want` equal slices (matchy_scanner_set_slices: tests, experiments):
+// cuts[0] = 0 < cuts[1] < ... < cuts[n] = len + 1, inner cuts on SEG_ALIGN boundaries. The default (want = 0) is ONE slice: measured
+// on the headline batch (profiles/r03_slices_sweep.txt), with k_anchor's segments handed out statically — one per resident wave —
+// the tail kernels of slice i take wave slots that k_anchor of slice i + 1 needs at its start, the workgroups that start late finish
+// late, and the whole scan gets slower (2 slices 1.32 ms, 4 slices 1.53 ms against 1.16 ms for one).
 int Scanner::plan_slices(uint32_t len, int want, uint32_t (&cuts)[MAX_SLICES + 1]) {
-    int gm[3];
-    grid_multipliers(false, gm);
-    // an explicit slice count (matchy_scanner_set_slices: tests, experiments) is honoured down to SEG_ALIGN-sized slices
-    const uint64_t unit = want > 0 ? (uint64_t)SEG_ALIGN : (uint64_t)n_cu_ * gm[0] * 4 * SEG_ALIGN;
-    double share[MAX_SLICES];
-    int n = 0;
-    static const char* env = getenv("MATCHY_AMD_SLICES");
-    if (want > 0) {
-        n = std::min(want, (int)MAX_SLICES);
-        for (int k = 0; k < n; ++k) share[k] = 1.0;
-    } else if (env && *env) {
-        const char* q = env;
-        while (*q && n < MAX_SLICES) {
-            char* e = nullptr;
-            const double v = strtod(q, &e);
-            if (e == q) break;
-            share[n++] = v > 0 ? v : 1.0;
-            q = *e == ',' ? e + 1 : e;
-        }
-        if (n == 1) { n = std::max(1, std::min((int)share[0], (int)MAX_SLICES)); for (int k = 0; k < n; ++k) share[k] = 1.0; }
-    } else {
-        // default: ONE slice. Measured on the headline batch (profiles/r03_slices_sweep.txt): with k_anchor's segments handed out
-        // statically — one per resident wave — the tail kernels of slice i take wave slots that k_anchor of slice i + 1 needs at
-        // its start, the workgroups that start late finish late, and the whole scan gets slower (2 slices 1.32 ms, 4 slices 1.53 ms
-        // against 1.16 ms for one). The mechanism stays available (matchy_scanner_set_slices, MATCHY_AMD_SLICES).
-        n = 1;
-        share[0] = 1.0;
-    }
-    // a slice wants at least two rounds of segments (an explicitly requested one: one segment)
-    n = (int)std::min<uint64_t>((uint64_t)std::max(n, 1), std::max<uint64_t>(1, ((uint64_t)len + 1) / (want > 0 ? unit : 2 * unit)));
-    double total = 0;
-    for (int k = 0; k < n; ++k) total += share[k];
     cuts[0] = 0;
-    double acc = 0;
+    cuts[1] = len + 1;
+    if (want <= 0) return 1;
+    const uint64_t unit = SEG_ALIGN;
+    // a slice wants at least one segment
+    const int n = (int)std::min<uint64_t>((uint64_t)std::min(want, (int)MAX_SLICES), std::max<uint64_t>(1, ((uint64_t)len + 1) / unit));
     for (int k = 1; k < n; ++k) {
-        acc += share[k - 1];
-        uint64_t c = (uint64_t)((double)len * acc / total) / unit * unit;
+        uint64_t c = (uint64_t)((double)len * k / n) / unit * unit;
         c = std::max<uint64_t>(c, (uint64_t)cuts[k - 1] + unit);
         cuts[k] = (uint32_t)c;
     }
@@ -777,41 +749,39 @@ int Scanner::plan_slices(uint32_t len, int want, uint32_t (&cuts)[MAX_SLICES + 1
     return n;
 }
 
-void Scanner::scan_device(const uint8_t* dptr, uint32_t len, bool lookup, hipStream_t stream, bool host_mirror, bool fork, int slices, bool compact) {
-    if (len >= 0x7FFF0000u) throw HipError{"scan_device: chunk too large (must be < 2^31 bytes)"};
-    if (((uintptr_t)dptr & 15) != 0) throw HipError{"scan_device: device pointer must be 16-byte aligned"};
+void Scanner::scan_device(const ScanRequest& rq, hipStream_t stream) {
+    if (rq.len >= 0x7FFF0000u) throw HipError{"scan_device: chunk too large (must be < 2^31 bytes)"};
+    if (((uintptr_t)rq.ptr & 15) != 0) throw HipError{"scan_device: device pointer must be 16-byte aligned"};
     MXY_HIP(hipSetDevice(ddb_->device));
-    last_ptr_ = dptr; last_len_ = len; last_lookup_ = lookup; last_mirror_ = host_mirror; last_fork_ = fork; last_slices_ = slices;
-    last_compact_ = compact;
-    compact_ = compact && lookup && compact_possible();
+    last_ = rq;
+    compact_ = rq.compact && rq.lookup && compact_possible();
     last_forked_ = false;
     spill_done_ = false;
     expect_chains_ = 0;
     // MATCHY_AMD_NO_FORK=1 keeps everything on one stream.
     static const bool env_no_fork = getenv("MATCHY_AMD_NO_FORK") != nullptr;
-    const bool no_fork = env_no_fork || !fork;
-    uint32_t cuts[MAX_SLICES + 1] = {0, len + 1};
-    const int ns = (no_fork || !lookup) ? 1 : plan_slices(len, slices, cuts);
+    const bool no_fork = env_no_fork || !rq.fork;
+    uint32_t cuts[MAX_SLICES + 1] = {0, rq.len + 1};
+    const int ns = (no_fork || !rq.lookup) ? 1 : plan_slices(rq.len, rq.slices, cuts);
     n_slices_ = ns;
     // buffers first: what they may allocate (lists, mirror, glob work list) must not sit between the launches
-    if (ns == 1) ensure_capacity(len);
+    if (ns == 1) ensure_capacity(rq.len);
     else {
         size_t recs = 0, ids = 0;
         for (int k = 0; k < ns; ++k) { work_[k].ensure(cuts[k + 1] - cuts[k]); recs += work_[k].hits.n; ids += work_[k].ids.n; }
         ensure_final(recs, ids);
     }
     mirror_used_ = false;
-    if (lookup && host_mirror) {
+    if (rq.lookup && rq.host_mirror) {
         static const uint32_t mirror0 = getenv("MATCHY_AMD_MIRROR_RECS") ? (uint32_t)atoi(getenv("MATCHY_AMD_MIRROR_RECS")) : (1u << 20);
         ensure_mirror(std::max(mirror0, 16u), std::max(mirror0 / 16, 16u));
         if (compact_) ensure_mirror_c4(std::max(mirror0, 16u));
         mirror_used_ = true;
     }
     if (compact_ && c4_.n < final_.n) c4_.alloc(final_.n);
-    // databases with globs, one slice, forked: k_validate_dom queues the candidates it flags for the glob pass itself (MATCHY_AMD_NO_EARLY_GLOB=1: off)
-    static const bool env_no_early = getenv("MATCHY_AMD_NO_EARLY_GLOB") != nullptr;
-    early_glob_ = !no_fork && ns == 1 && lookup && ddb_->view.has_glob && !env_no_early;
-    for (int k = 0; k < ns; ++k) slice_params(k, dptr, len, cuts[k], cuts[k + 1], lookup, host_mirror, launch_[k]);
+    // databases with globs, one slice, forked: k_validate_dom queues the candidates it flags for the glob pass itself
+    early_glob_ = !no_fork && ns == 1 && rq.lookup && ddb_->view.has_glob;
+    for (int k = 0; k < ns; ++k) slice_params(k, rq, cuts[k], cuts[k + 1], launch_[k]);
     early_glob_ = early_glob_ && launch_[0].lp.early_glob != 0;
     // the counter blocks are zero already when the last scan ended with fetch() (k_finish copies them out and clears them)
     if (!counters_clean_) { MXY_HIP(hipMemsetAsync(counters_.p, 0, sizeof(ScanCounters) * MAX_SLICES, stream)); dom_preset_ = 0; }
@@ -820,270 +790,253 @@ void Scanner::scan_device(const uint8_t* dptr, uint32_t len, bool lookup, hipStr
         // First chunks of the domain list without a reservation (DomWriter::reserve): when the previous batch needed more than one chunk per
         // wave on average, wave w of k_anchor owns chunk w and the counter starts behind those chunks — k_finish of the previous scan has
         // written that value already when the batches are alike; otherwise it is set here.
-        static const bool env_no_static = getenv("MATCHY_AMD_NO_DOM_STATIC") != nullptr;
         const uint64_t total = (uint64_t)launch_[0].grid_anchor * 4u * ANCHOR_CHUNK;
         uint32_t want = 0;
-        if (ns == 1 && !env_no_static && total <= launch_[0].tp.dom_cap && (uint64_t)hint_.n_dom * 2 >= total * 3) want = (uint32_t)total;
+        if (ns == 1 && total <= launch_[0].tp.dom_cap && (uint64_t)hint_.n_dom * 2 >= total * 3) want = (uint32_t)total;
         if (want != dom_preset_) MXY_HIP(hipMemsetD32Async((hipDeviceptr_t)&counters_.p->n_dom, (int)want, 1, stream));
         dom_preset_ = want;
         dom_want_ = want;
         launch_[0].tp.dom_static = want ? ANCHOR_CHUNK : 0u;
         // behind the first chunk: an eighth of what a wave wrote last time, in whole tiles, 256..ANCHOR_CHUNK slots (less padding for k_validate_dom
         // to read; these reservations are spread over the kernel)
-        static const int env_chunk = getenv("MATCHY_AMD_DOM_CHUNK") ? atoi(getenv("MATCHY_AMD_DOM_CHUNK")) : 0;
         for (int k = 0; k < ns; ++k) launch_[k].tp.dom_chunk = ANCHOR_CHUNK;
         if (want) {
             const uint32_t share = hint_.n_dom / ((uint32_t)launch_[0].grid_anchor * 4u) / 8u;
-            launch_[0].tp.dom_chunk = env_chunk > 0 ? (uint32_t)env_chunk : std::min<uint32_t>(ANCHOR_CHUNK, std::max<uint32_t>(256u, share & ~63u));
+            launch_[0].tp.dom_chunk = std::min<uint32_t>(ANCHOR_CHUNK, std::max<uint32_t>(256u, share & ~63u));
         }
     }
-    const bool rare_possible = (flags_ & (EX_HASHES | EX_BITCOIN | EX_ETHEREUM | EX_MONERO)) != 0;
-    static const int misc_wgs = getenv("MATCHY_AMD_MISC_GRID") ? atoi(getenv("MATCHY_AMD_MISC_GRID")) : 0;
+    if (profile_) MXY_HIP(hipEventRecord(ev_[0], stream));
+    if (ns > 1) launch_sliced(ns, stream);
+    else if (no_fork) launch_one_stream(stream);
+    else launch_forked(stream);
+    if (profile_) MXY_HIP(hipEventRecord(ev_[4], stream));
+}
+
+void Scanner::ensure_dom_stream() {
+    if (dom_stream_) return;
+    MXY_HIP(hipStreamCreateWithFlags(&dom_stream_, hipStreamNonBlocking));
+    MXY_HIP(hipEventCreateWithFlags(&ev_join3_, hipEventDisableTiming));
+    MXY_HIP(hipEventCreateWithFlags(&ev_dom_, hipEventDisableTiming));
+}
+
+// Sliced scan. The scan's stream carries the k_anchor launches, slice after slice. Behind k_anchor of slice i three side streams
+// take over, as in the one-slice fork (launch_forked): dom_stream_ k_validate_dom -> k_validate (undecided domains) -> k_lookup;
+// aux_stream_ k_lookup_ip; aux2_stream_ k_validate (tokens, IPv6 / e-mail) -> k_rare. They run BESIDE k_anchor of slice i + 1
+// (whose workgroups leave the CUs one by one), the slices of one side stream in stream order. Only the tail of the last slice is
+// not covered by a k_anchor.
+void Scanner::launch_sliced(int ns, hipStream_t stream) {
     const DevDb& view = ddb_->view;
-    if (ns > 1) {
-        // Sliced scan. The scan's stream carries the k_anchor launches, slice after slice. Behind k_anchor of slice i three
-        // side streams take over, as in the one-slice fork below: dom_stream_ k_validate_dom -> k_validate (undecided
-        // domains) -> k_lookup; aux_stream_ k_lookup_ip; aux2_stream_ k_validate (tokens, IPv6 / e-mail) -> k_rare. They
-        // run BESIDE k_anchor of slice i + 1 (whose workgroups leave the CUs one by one), the slices of one side stream in
-        // stream order. Only the tail of the last slice is not covered by a k_anchor.
-        last_forked_ = true;
-        if (!dom_stream_) {
-            MXY_HIP(hipStreamCreateWithFlags(&dom_stream_, hipStreamNonBlocking));
-            MXY_HIP(hipEventCreateWithFlags(&ev_join3_, hipEventDisableTiming));
-            MXY_HIP(hipEventCreateWithFlags(&ev_dom_, hipEventDisableTiming));
-        }
-        if (!ev_anchor_[0]) {
-            for (auto& e : ev_anchor_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto& e : ev_misc_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        if (profile_) MXY_HIP(hipEventRecord(ev_[0], stream));
-        for (int k = 0; k < ns; ++k) {
-            SliceLaunch& L = launch_[k];
-            launch_anchor(L.tp, view, L.grid_anchor, stream);
-            hipEvent_t done = ev_anchor_[k];
-            if (profile_ && k == ns - 1) { MXY_HIP(hipEventRecord(ev_[1], stream)); done = ev_[1]; }
-            else MXY_HIP(hipEventRecord(done, stream));
-            if (L.ip_pass) {
-                MXY_HIP(hipStreamWaitEvent(aux_stream_, done, 0));
-                launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, aux_stream_);
-            }
-            MXY_HIP(hipStreamWaitEvent(aux2_stream_, done, 0));
-            TokParams t1 = L.tp;
-            t1.vmode = 5u;
-            if (L.split_misc) { t1.cands = work_[k].cands_m.p; t1.cand_cap = (uint32_t)work_[k].cands_m.n; t1.n_cand = &(counters_.p + k)->n_cand_m; }
-            launch_validate_misc(t1, view, misc_wgs > 0 ? misc_wgs : std::max(1, n_cu_ / 2), aux2_stream_);
-            if (L.split_misc) launch_lookup(L.lm, view, std::max(1, n_cu_ / 2), aux2_stream_);
-            if (rare_possible) {
-                TokParams tr = t1;
-                tr.vmode = L.tp.vmode;
-                if (L.split_misc) { tr.cands = work_[k].cands_r.p; tr.cand_cap = (uint32_t)work_[k].cands_r.n; tr.n_cand = &(counters_.p + k)->n_cand_r; }
-                launch_rare(tr, view, n_cu_ * 4, aux2_stream_);
-                if (L.split_misc) launch_lookup(L.lr, view, std::max(1, n_cu_ / 8), aux2_stream_);
-            }
-            MXY_HIP(hipEventRecord(ev_misc_[k], aux2_stream_));
-            MXY_HIP(hipStreamWaitEvent(dom_stream_, done, 0));
-            launch_validate_dom(L.tp, view, n_cu_ * L.gm[1], dom_stream_);
-            TokParams t2 = L.tp;
-            t2.vmode = 2u;
-            launch_validate_misc(t2, view, misc_wgs > 0 ? misc_wgs : n_cu_, dom_stream_);
-            if (!L.split_misc) MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_misc_[k], 0));
-            launch_lookup(L.lp, view, n_cu_ * L.gm[2], dom_stream_);
-        }
-        MXY_HIP(hipEventRecord(ev_join3_, dom_stream_));
-        MXY_HIP(hipStreamWaitEvent(stream, ev_join3_, 0));
-        if (launch_[0].split_misc) MXY_HIP(hipStreamWaitEvent(stream, ev_misc_[ns - 1], 0));
-        bool any_ip = false;
-        for (int k = 0; k < ns; ++k) any_ip |= launch_[k].ip_pass;
-        if (any_ip) {
-            MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
-            MXY_HIP(hipStreamWaitEvent(stream, ev_join_, 0));
-        }
-        if (profile_) MXY_HIP(hipEventRecord(ev_[4], stream));
-        return;
+    last_forked_ = true;
+    ensure_dom_stream();
+    if (!ev_anchor_[0]) {
+        for (auto& e : ev_anchor_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto& e : ev_misc_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
+    for (int k = 0; k < ns; ++k) {
+        SliceLaunch& L = launch_[k];
+        ScanCounters* ctr = counters_.p + k;
+        launch_anchor(L.tp, view, L.grid_anchor, stream);
+        hipEvent_t done = ev_anchor_[k];
+        if (profile_ && k == ns - 1) { MXY_HIP(hipEventRecord(ev_[1], stream)); done = ev_[1]; }
+        else MXY_HIP(hipEventRecord(done, stream));
+        if (L.ip_pass) {
+            MXY_HIP(hipStreamWaitEvent(aux_stream_, done, 0));
+            launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, aux_stream_);
+        }
+        MXY_HIP(hipStreamWaitEvent(aux2_stream_, done, 0));
+        TokParams t1 = L.tp;
+        t1.vmode = 5u;
+        if (L.split_misc) point_at(t1, work_[k].cands_m, &ctr->n_cand_m);
+        launch_validate_misc(t1, view, std::max(1, n_cu_ / 2), aux2_stream_);
+        if (L.split_misc) launch_lookup(L.lm, view, std::max(1, n_cu_ / 2), aux2_stream_);
+        if (rare_possible()) {
+            TokParams tr = t1;
+            tr.vmode = L.tp.vmode;
+            if (L.split_misc) point_at(tr, work_[k].cands_r, &ctr->n_cand_r);
+            launch_rare(tr, view, n_cu_ * 4, aux2_stream_);
+            if (L.split_misc) launch_lookup(L.lr, view, std::max(1, n_cu_ / 8), aux2_stream_);
+        }
+        MXY_HIP(hipEventRecord(ev_misc_[k], aux2_stream_));
+        MXY_HIP(hipStreamWaitEvent(dom_stream_, done, 0));
+        launch_validate_dom(L.tp, view, n_cu_ * L.gm[1], dom_stream_);
+        TokParams t2 = L.tp;
+        t2.vmode = 2u;
+        launch_validate_misc(t2, view, n_cu_, dom_stream_);
+        if (!L.split_misc) MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_misc_[k], 0));
+        launch_lookup(L.lp, view, n_cu_ * L.gm[2], dom_stream_);
+    }
+    MXY_HIP(hipEventRecord(ev_join3_, dom_stream_));
+    MXY_HIP(hipStreamWaitEvent(stream, ev_join3_, 0));
+    if (launch_[0].split_misc) MXY_HIP(hipStreamWaitEvent(stream, ev_misc_[ns - 1], 0));
+    bool any_ip = false;
+    for (int k = 0; k < ns; ++k) any_ip |= launch_[k].ip_pass;
+    if (any_ip) {
+        MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
+        MXY_HIP(hipStreamWaitEvent(stream, ev_join_, 0));
+    }
+}
+
+// One slice forked after k_anchor. Everything k_anchor lists is complete then, and two parts of the rest do not depend on
+// k_validate_dom:
+//  * the trie lookups of the IPv4 candidates (and the PCIe writes of their hit records, which is most of the result traffic
+//    of a log scan) -> k_lookup_ip on a stream of its own; both lookup passes append to the same final arrays (atomic slot
+//    reservation);
+//  * k_validate over the long tokens and k_anchor's IPv6 / e-mail anchors, and k_rare behind it -> a third stream.
+// The scan's stream keeps k_validate_dom, k_validate over the domain anchors k_validate_dom left undecided, and the lookups
+// of the validation kernels' candidates; it joins the third stream before those lookups and the second after them.
+void Scanner::launch_forked(hipStream_t stream) {
     SliceLaunch& L = launch_[0];
     const TokParams& tp = L.tp;
-    if (profile_) MXY_HIP(hipEventRecord(ev_[0], stream));
+    const DevDb& view = ddb_->view;
+    Work& w = work_[0];
+    ScanCounters* ctr = counters_.p;
     launch_anchor(tp, view, L.grid_anchor, stream);
     if (profile_) MXY_HIP(hipEventRecord(ev_[1], stream));
-    // Fork. Everything k_anchor lists is complete now, and two parts of the rest do not depend on k_validate_dom:
-    //  * the trie lookups of the IPv4 candidates (and the PCIe writes of their hit records, which is most of the result traffic
-    //    of a log scan) -> k_lookup_ip on a stream of its own; both lookup passes append to the same final arrays (atomic slot
-    //    reservation);
-    //  * k_validate over the long tokens and k_anchor's IPv6 / e-mail anchors, and k_rare behind it -> a third stream.
-    // The scan's stream keeps k_validate_dom, k_validate over the domain anchors k_validate_dom left undecided, and the lookups
-    // of the validation kernels' candidates; it joins the third stream before those lookups and the second after them.
-    last_forked_ = !no_fork;
-    if (!no_fork) {
-        hipEvent_t fork = profile_ ? ev_[1] : ev_fork_;
-        if (!profile_) MXY_HIP(hipEventRecord(ev_fork_, stream));
-        if (L.ip_pass) {
-            MXY_HIP(hipStreamWaitEvent(aux_stream_, fork, 0));
-            launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, aux_stream_);
-            MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
-        }
-        MXY_HIP(hipStreamWaitEvent(aux2_stream_, fork, 0));
-        TokParams t1 = tp;
-        t1.vmode = 5u;
-        if (L.split_misc) { t1.cands = work_[0].cands_m.p; t1.cand_cap = (uint32_t)work_[0].cands_m.n; t1.n_cand = &counters_.p->n_cand_m; }
-        // split lists: the lookups of k_validate's candidates do not wait for k_rare (checksum validators: a chain of their own,
-        // almost always over next to nothing), whose few candidates get a list and a lookup launch of their own — on the second
-        // stream when the IPv4 lookups do not need it (they run inside k_anchor), beside the third stream's lookups. The long tokens
-        // — k_rare takes what they leave — then get a launch of their own in front of the rare anchors (IPv6 / e-mail: ten times as
-        // many, 0.12 ms), so that k_rare runs beside those instead of behind them.
-        const bool rare_own = L.split_misc && rare_possible && !L.ip_pass;
-        // Long lists (dense logs): these passes wait for memory most of their time, and beyond a few workgroups per CU more of them only
-        // queue up in front of it. Measured per pass on 1.85 GB batches (tools/sweep_misc_grid.sh, profiles/r05_log_shapes.txt): long tokens
-        // 8 -> 6 per CU: step 2.61 -> 2.41 ms (endpoint log with hashes); '@' / "::" anchors 8 -> 4: 2.37 -> 2.31 (JSON lines); domains
-        // k_validate_dom left undecided 8 -> 2: 2.36 -> 2.22 (proxy log with URLs). Short lists keep their default grids.
-        constexpr int TOK_WGS_PER_CU = 6, RARE_WGS_PER_CU = 4, RARE_DOM_WGS_PER_CU = 2;
-        // Both lists long (the previous batch had hundreds of thousands of long tokens AND of IPv6 / e-mail anchors: application logs in
-        // JSON lines): the long tokens do not run in front of the rare anchors on the third stream but beside them on the second, in front
-        // of k_rare (which takes what they leave: stream order instead of an event), and list their hashes in k_rare's candidate list — the
-        // lookup behind k_rare takes both. Two latency-bound passes over millions of entries each then overlap instead of queueing (the
-        // JSON-lines shape: tail 1.18 -> see profiles/r04_log_shapes.txt). With short lists (a web-server log) the two kernels would only
-        // take vector-ALU time from k_validate_dom beside them (+6 us measured): the order stays as it is there.
-        static const int env_tok_aside = getenv("MATCHY_AMD_TOK_ASIDE") ? atoi(getenv("MATCHY_AMD_TOK_ASIDE")) : -1;
-        const bool tok_aside = rare_own && (env_tok_aside >= 0 ? env_tok_aside != 0 : (hint_.n_tok >= 262144u && hint_.n_rare >= 262144u));
-        if (tok_aside) {
-            MXY_HIP(hipStreamWaitEvent(aux_stream_, fork, 0));
-            TokParams tt = t1;
-            tt.vmode = 4u;
-            tt.cands = work_[0].cands_r.p; tt.cand_cap = (uint32_t)work_[0].cands_r.n; tt.n_cand = &counters_.p->n_cand_r;
-            launch_validate_misc(tt, view, misc_wgs > 0 ? misc_wgs : grid_for(hint_.n_tok, 1024, std::max(1, n_cu_ / 2), TOK_WGS_PER_CU), aux_stream_);
-            t1.vmode = 1u;
-        } else if (rare_own) {
-            TokParams tt = t1;
-            tt.vmode = 4u;
-            launch_validate_misc(tt, view, misc_wgs > 0 ? misc_wgs : grid_for(hint_.n_tok, 1024, std::max(1, n_cu_ / 2), TOK_WGS_PER_CU), aux2_stream_);   // 6 KB of LDS, workgroups beyond the list leave at once
-            if (!ev_v1_) MXY_HIP(hipEventCreateWithFlags(&ev_v1_, hipEventDisableTiming));
-            MXY_HIP(hipEventRecord(ev_v1_, aux2_stream_));
-            t1.vmode = 1u;
-        }
-        // beside k_validate_dom: half the CUs, so that kernel keeps most of its resident waves (more when the previous batch's lists were long)
-        launch_validate_misc(t1, view, misc_wgs > 0 ? misc_wgs : grid_for(rare_own ? hint_.n_rare : std::max(hint_.n_rare, hint_.n_tok), 1024, std::max(1, n_cu_ / 2), rare_own ? RARE_WGS_PER_CU : 8), aux2_stream_);
-        // Split lists: the side chains do not join the scan's stream through events — the last kernel of each (a k_lookup launch) reports
-        // its end in ScanCounters::chains_done, which k_finish polls (arrive_chain 1: third stream, 2: k_rare's, 3: the fourth stream)
-        static const bool env_join = getenv("MATCHY_AMD_EVENT_JOIN") != nullptr;
-        const bool arrive = L.split_misc && !env_join;
-        uint32_t chains = 0;
+    last_forked_ = true;
+    hipEvent_t fork = profile_ ? ev_[1] : ev_fork_;
+    if (!profile_) MXY_HIP(hipEventRecord(ev_fork_, stream));
+    if (L.ip_pass) {
+        MXY_HIP(hipStreamWaitEvent(aux_stream_, fork, 0));
+        launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, aux_stream_);
+        MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
+    }
+    MXY_HIP(hipStreamWaitEvent(aux2_stream_, fork, 0));
+    TokParams t1 = tp;
+    t1.vmode = 5u;
+    if (L.split_misc) point_at(t1, w.cands_m, &ctr->n_cand_m);
+    // split lists: the lookups of k_validate's candidates do not wait for k_rare (checksum validators: a chain of their own,
+    // almost always over next to nothing), whose few candidates get a list and a lookup launch of their own — on the second
+    // stream when the IPv4 lookups do not need it (they run inside k_anchor), beside the third stream's lookups. The long tokens
+    // — k_rare takes what they leave — then get a launch of their own in front of the rare anchors (IPv6 / e-mail: ten times as
+    // many, 0.12 ms), so that k_rare runs beside those instead of behind them.
+    const bool rare_own = L.split_misc && rare_possible() && !L.ip_pass;
+    // Long lists (dense logs): these passes wait for memory most of their time, and beyond a few workgroups per CU more of them only
+    // queue up in front of it. Measured per pass on 1.85 GB batches (profiles/r05_log_shapes.txt): long tokens 8 -> 6 per CU: step
+    // 2.61 -> 2.41 ms (endpoint log with hashes); '@' / "::" anchors 8 -> 4: 2.37 -> 2.31 (JSON lines); domains k_validate_dom left
+    // undecided 8 -> 2: 2.36 -> 2.22 (proxy log with URLs). Short lists keep their default grids.
+    constexpr int TOK_WGS_PER_CU = 6, RARE_WGS_PER_CU = 4, RARE_DOM_WGS_PER_CU = 2;
+    // Both lists long (the previous batch had hundreds of thousands of long tokens AND of IPv6 / e-mail anchors: application logs in
+    // JSON lines): the long tokens do not run in front of the rare anchors on the third stream but beside them on the second, in front
+    // of k_rare (which takes what they leave: stream order instead of an event), and list their hashes in k_rare's candidate list — the
+    // lookup behind k_rare takes both. Two latency-bound passes over millions of entries each then overlap instead of queueing (the
+    // JSON-lines shape: tail 1.18 -> see profiles/r04_log_shapes.txt). With short lists (a web-server log) the two kernels would only
+    // take vector-ALU time from k_validate_dom beside them (+6 us measured): the order stays as it is there.
+    static const int env_tok_aside = getenv("MATCHY_AMD_TOK_ASIDE") ? atoi(getenv("MATCHY_AMD_TOK_ASIDE")) : -1;
+    const bool tok_aside = rare_own && (env_tok_aside >= 0 ? env_tok_aside != 0 : (hint_.n_tok >= 262144u && hint_.n_rare >= 262144u));
+    const int tok_grid = grid_for(hint_.n_tok, 1024, std::max(1, n_cu_ / 2), TOK_WGS_PER_CU);   // 6 KB of LDS, workgroups beyond the list leave at once
+    if (tok_aside) {
+        MXY_HIP(hipStreamWaitEvent(aux_stream_, fork, 0));
+        TokParams tt = t1;
+        tt.vmode = 4u;
+        point_at(tt, w.cands_r, &ctr->n_cand_r);
+        launch_validate_misc(tt, view, tok_grid, aux_stream_);
+        t1.vmode = 1u;
+    } else if (rare_own) {
+        TokParams tt = t1;
+        tt.vmode = 4u;
+        launch_validate_misc(tt, view, tok_grid, aux2_stream_);
+        if (!ev_v1_) MXY_HIP(hipEventCreateWithFlags(&ev_v1_, hipEventDisableTiming));
+        MXY_HIP(hipEventRecord(ev_v1_, aux2_stream_));
+        t1.vmode = 1u;
+    }
+    // beside k_validate_dom: half the CUs, so that kernel keeps most of its resident waves (more when the previous batch's lists were long)
+    launch_validate_misc(t1, view, grid_for(rare_own ? hint_.n_rare : std::max(hint_.n_rare, hint_.n_tok), 1024, std::max(1, n_cu_ / 2), rare_own ? RARE_WGS_PER_CU : 8), aux2_stream_);
+    // Split lists: the side chains do not join the scan's stream through events — the last kernel of each (a k_lookup launch) reports
+    // its end in ScanCounters::chains_done, which k_finish polls (arrive_chain 1: third stream, 2: k_rare's, 3: the fourth stream)
+    uint32_t chains = 0;
+    if (L.split_misc) {
+        LookupParams lm = L.lm;
+        if (rare_own || !rare_possible()) { lm.arrive_chain = 1; lm.arrive = ctr; ++chains; }
+        launch_lookup(lm, view, grid_for(hint_.n_cand_m, 512, std::max(1, n_cu_ / 2), 4), aux2_stream_);
+    }
+    if (rare_possible()) {   // one wave per SIMD (297 VGPRs)
+        TokParams tr = t1;
+        tr.vmode = tp.vmode;
+        if (L.split_misc) point_at(tr, w.cands_r, &ctr->n_cand_r);
+        hipStream_t rs = rare_own ? aux_stream_ : aux2_stream_;
+        if (rare_own && !tok_aside) MXY_HIP(hipStreamWaitEvent(aux_stream_, ev_v1_, 0));
+        launch_rare(tr, view, grid_for(hint_.n_heavy, 128, n_cu_ * 4, 16), rs);
         if (L.split_misc) {
-            LookupParams lm = L.lm;
-            if (arrive && (rare_own || !rare_possible)) { lm.arrive_chain = 1; lm.arrive = counters_.p; ++chains; }
-            static const int lm_wgs = getenv("MATCHY_AMD_LMGRID") ? atoi(getenv("MATCHY_AMD_LMGRID")) : 0;   // experiments (tools/sweep_tail_knobs.sh)
-            launch_lookup(lm, view, lm_wgs > 0 ? lm_wgs : grid_for(hint_.n_cand_m, 512, std::max(1, n_cu_ / 2), 4), aux2_stream_);
+            LookupParams lr = L.lr;
+            lr.arrive_chain = rare_own ? 2u : 1u; lr.arrive = ctr; ++chains;
+            launch_lookup(lr, view, grid_for(hint_.n_cand_r, 512, std::max(1, n_cu_ / 8), 4), rs);   // (tok_aside: the hint follows the list that now holds the hashes too)
         }
-        if (rare_possible) {   // one wave per SIMD (297 VGPRs)
-            TokParams tr = t1;
-            tr.vmode = tp.vmode;
-            if (L.split_misc) { tr.cands = work_[0].cands_r.p; tr.cand_cap = (uint32_t)work_[0].cands_r.n; tr.n_cand = &counters_.p->n_cand_r; }
-            hipStream_t rs = rare_own ? aux_stream_ : aux2_stream_;
-            if (rare_own && !tok_aside) MXY_HIP(hipStreamWaitEvent(aux_stream_, ev_v1_, 0));
-            launch_rare(tr, view, grid_for(hint_.n_heavy, 128, n_cu_ * 4, 16), rs);
-            if (L.split_misc) {
-                LookupParams lr = L.lr;
-                if (arrive) { lr.arrive_chain = rare_own ? 2u : 1u; lr.arrive = counters_.p; ++chains; }
-                launch_lookup(lr, view, grid_for(hint_.n_cand_r, 512, std::max(1, n_cu_ / 8), 4), rs);   // (tok_aside: the hint follows the list that now holds the hashes too)
-            }
-            if (rare_own && !arrive) MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
-        }
-        if (!arrive) MXY_HIP(hipEventRecord(ev_join2_, aux2_stream_));
-        launch_validate_dom(tp, view, n_cu_ * L.gm[1], stream);
-        TokParams t2 = tp;
-        t2.vmode = 2u;
-        if (L.split_misc) {
-            // Behind k_validate_dom two chains: the few domain anchors it left undecided (general walk + lookups of THEIR candidates,
-            // a list of their own) stay on the scan's stream — no event between producer and consumer —, the lookups of
-            // k_validate_dom's candidates go to a fourth stream beside them. That stream then takes the other side streams' end
-            // events in, so the scan's stream joins ONE event (every event wait on it is ~10 us in front of k_finish).
-            if (!dom_stream_) {
-                MXY_HIP(hipStreamCreateWithFlags(&dom_stream_, hipStreamNonBlocking));
-                MXY_HIP(hipEventCreateWithFlags(&ev_join3_, hipEventDisableTiming));
-                MXY_HIP(hipEventCreateWithFlags(&ev_dom_, hipEventDisableTiming));
-            }
+    }
+    if (!L.split_misc) MXY_HIP(hipEventRecord(ev_join2_, aux2_stream_));
+    launch_validate_dom(tp, view, n_cu_ * L.gm[1], stream);
+    TokParams t2 = tp;
+    t2.vmode = 2u;
+    if (L.split_misc) {
+        // Behind k_validate_dom two chains: the few domain anchors it left undecided (general walk + lookups of THEIR candidates,
+        // a list of their own) stay on the scan's stream — no event between producer and consumer —, the lookups of
+        // k_validate_dom's candidates go to a fourth stream beside them and report their end to k_finish like the other side chains.
+        ensure_dom_stream();
+        MXY_HIP(hipEventRecord(ev_dom_, stream));
+        MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_dom_, 0));
+        LookupParams lpm = L.lp;
+        lpm.arrive_chain = 3; lpm.arrive = ctr; ++chains;
+        // one workgroup per CU: every workgroup ends with a pair of returning atomics on the two record counters, and with 512
+        // of them those queue up behind each other (64 / 128 / 192 / 256 / 512 workgroups: tail 0.236 / 0.218 / 0.217 / 0.218 / 0.227 ms;
+        // not fewer than one per CU: a database that most names hit makes this the kernel with the work)
+        launch_lookup(lpm, view, grid_for(hint_.n_cand, 512, n_cu_, 4), dom_stream_);
+        expect_chains_ = chains;
+        point_at(t2, w.cands_d, &ctr->n_cand_d);
+        launch_validate_misc(t2, view, grid_for(hint_.n_rare_dom, 512, n_cu_, RARE_DOM_WGS_PER_CU), stream);
+        launch_lookup(L.ld, view, grid_for(hint_.n_cand_d, 512, std::max(1, n_cu_ / 8), 4), stream);
+    } else {
+        // k_validate<2> and the glob pass over ITS candidates go to the second stream when the early glob pass runs and the IPv4
+        // lookups do not need that stream: the lean pass does not have to wait for them
+        const bool v2_aside = early_glob_ && !L.ip_pass;
+        if (early_glob_) {
+            // Databases with globs keep one candidate list, but the candidates k_validate_dom flags for the glob pass — most of that
+            // pass's work — are on a work list of their own already (TokParams::glob_work_d): the glob pass over them starts here, on the
+            // fourth stream, beside k_validate<2> and the lean pass over everything else (which skips them and defers what IT finds to
+            // the usual work list for a second, small glob pass behind it).
+            ensure_dom_stream();
             MXY_HIP(hipEventRecord(ev_dom_, stream));
             MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_dom_, 0));
-            {
-                LookupParams lpm = L.lp;
-                if (arrive) { lpm.arrive_chain = 3; lpm.arrive = counters_.p; ++chains; }
-                static const int lp_wgs = getenv("MATCHY_AMD_LPGRID") ? atoi(getenv("MATCHY_AMD_LPGRID")) : 0;
-                // one workgroup per CU: every workgroup ends with a pair of returning atomics on the two record counters, and with 512
-                // of them those queue up behind each other (64 / 128 / 192 / 256 / 512 workgroups: tail 0.236 / 0.218 / 0.217 / 0.218 / 0.227 ms;
-                // not fewer than one per CU: a database that most names hit makes this the kernel with the work)
-                launch_lookup(lpm, view, lp_wgs > 0 ? lp_wgs : grid_for(hint_.n_cand, 512, n_cu_, 4), dom_stream_);
+            // Both side chains report their ends to k_finish (arrival counters, as in the scans without globs: an event join in front of
+            // k_finish costs ~10-20 us each).
+            LookupParams lg = L.lp;
+            lg.glob_work = w.glob_work_d.p; lg.glob_work_cap = (uint32_t)w.glob_work_d.n;
+            lg.n_work = &ctr->n_glob_work_d;
+            lg.arrive_chain = 3; lg.arrive = ctr; ++chains;
+            launch_lookup_early_glob(lg, view, n_cu_ * L.gm[2], dom_stream_);
+            if (v2_aside) {
+                MXY_HIP(hipStreamWaitEvent(aux_stream_, ev_dom_, 0));
+                point_at(t2, w.cands_d, &ctr->n_cand_d);
+                launch_validate_misc(t2, view, grid_for(hint_.n_rare_dom, 512, n_cu_, 8), aux_stream_);
+                LookupParams ld = L.ld;
+                ld.arrive_chain = 2; ld.arrive = ctr; ++chains;
+                launch_lookup(ld, view, grid_for(hint_.n_cand_d, 512, std::max(2, n_cu_ / 8), 4), aux_stream_);
             }
-            if (arrive) expect_chains_ = chains;
-            else {
-                MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_join2_, 0));
-                if (rare_own) MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_join_, 0));
-                MXY_HIP(hipEventRecord(ev_join3_, dom_stream_));
-            }
-            t2.cands = work_[0].cands_d.p; t2.cand_cap = (uint32_t)work_[0].cands_d.n; t2.n_cand = &counters_.p->n_cand_d;
-            launch_validate_misc(t2, view, misc_wgs > 0 ? misc_wgs : grid_for(hint_.n_rare_dom, 512, n_cu_, RARE_DOM_WGS_PER_CU), stream);
-            static const int ld_wgs = getenv("MATCHY_AMD_LDGRID") ? atoi(getenv("MATCHY_AMD_LDGRID")) : 0;
-            launch_lookup(L.ld, view, ld_wgs > 0 ? ld_wgs : grid_for(hint_.n_cand_d, 512, std::max(1, n_cu_ / 8), 4), stream);
-        } else {
-            if (early_glob_) {
-                // Databases with globs keep one candidate list, but the candidates k_validate_dom flags for the glob pass — most of that
-                // pass's work — are on a work list of their own already (TokParams::glob_work_d): the glob pass over them starts here, on the
-                // fourth stream, beside k_validate<2> and the lean pass over everything else (which skips them and defers what IT finds to
-                // the usual work list for a second, small glob pass behind it).
-                if (!dom_stream_) {
-                    MXY_HIP(hipStreamCreateWithFlags(&dom_stream_, hipStreamNonBlocking));
-                    MXY_HIP(hipEventCreateWithFlags(&ev_join3_, hipEventDisableTiming));
-                    MXY_HIP(hipEventCreateWithFlags(&ev_dom_, hipEventDisableTiming));
-                }
-                MXY_HIP(hipEventRecord(ev_dom_, stream));
-                MXY_HIP(hipStreamWaitEvent(dom_stream_, ev_dom_, 0));
-                // Both side chains report their ends to k_finish (arrival counters, as in the scans without globs: an event join in front of
-                // k_finish costs ~10-20 us each).
-                static const bool env_join_g = getenv("MATCHY_AMD_EVENT_JOIN") != nullptr;
-                uint32_t chains = 0;
-                LookupParams lg = L.lp;
-                lg.glob_work = work_[0].glob_work_d.p; lg.glob_work_cap = (uint32_t)work_[0].glob_work_d.n;
-                lg.n_work = &counters_.p->n_glob_work_d;
-                if (!env_join_g) { lg.arrive_chain = 3; lg.arrive = counters_.p; ++chains; }
-                launch_lookup_early_glob(lg, view, n_cu_ * L.gm[2], dom_stream_);
-                if (env_join_g) MXY_HIP(hipEventRecord(ev_join3_, dom_stream_));
-                glob_join3_ = env_join_g;
-                // ... and the undecided domains (k_validate<2>: general walk) with the glob pass over THEIR candidates leave the scan's
-                // stream for the second one, when the IPv4 lookups do not need it: the lean pass does not have to wait for them
-                static const bool env_no_aside = getenv("MATCHY_AMD_NO_V2_ASIDE") != nullptr;
-                glob_v2_aside_ = !L.ip_pass && !env_no_aside;
-                if (glob_v2_aside_) {
-                    MXY_HIP(hipStreamWaitEvent(aux_stream_, ev_dom_, 0));
-                    t2.cands = work_[0].cands_d.p; t2.cand_cap = (uint32_t)work_[0].cands_d.n; t2.n_cand = &counters_.p->n_cand_d;
-                    launch_validate_misc(t2, view, misc_wgs > 0 ? misc_wgs : grid_for(hint_.n_rare_dom, 512, n_cu_, 8), aux_stream_);
-                    LookupParams ld = L.ld;
-                    if (!env_join_g) { ld.arrive_chain = 2; ld.arrive = counters_.p; ++chains; }
-                    launch_lookup(ld, view, grid_for(hint_.n_cand_d, 512, std::max(2, n_cu_ / 8), 4), aux_stream_);
-                    if (env_join_g) MXY_HIP(hipEventRecord(ev_join_, aux_stream_));
-                }
-                expect_chains_ = chains;
-            }
-            if (!(early_glob_ && glob_v2_aside_)) launch_validate_misc(t2, view, misc_wgs > 0 ? misc_wgs : grid_for(hint_.n_rare_dom, 512, n_cu_, RARE_DOM_WGS_PER_CU), stream);
-            // no timing events inside the forked tail: every packet between two kernels of the chain is ~6-8 us of it, and with
-            // kernels running side by side the intervals would not be kernel times anyway (ScanTiming: validate_ms = the whole tail)
-            MXY_HIP(hipStreamWaitEvent(stream, ev_join2_, 0));
+            expect_chains_ = chains;
         }
-    } else {
-        launch_validate_dom(tp, view, n_cu_ * L.gm[1], stream);
-        launch_validate_misc(tp, view, misc_wgs > 0 ? misc_wgs : grid_for(std::max(std::max(hint_.n_tok, hint_.n_rare), hint_.n_rare_dom), 1024, n_cu_, 8), stream);   // vmode 3: every list
-        if (profile_) MXY_HIP(hipEventRecord(ev_[2], stream));
-        if (rare_possible) launch_rare(tp, view, grid_for(hint_.n_heavy, 128, n_cu_ * 4, 16), stream);
-        if (profile_) MXY_HIP(hipEventRecord(ev_[3], stream));
+        if (!v2_aside) launch_validate_misc(t2, view, grid_for(hint_.n_rare_dom, 512, n_cu_, RARE_DOM_WGS_PER_CU), stream);
+        // no timing events inside the forked tail: every packet between two kernels of the chain is ~6-8 us of it, and with
+        // kernels running side by side the intervals would not be kernel times anyway (ScanTiming: validate_ms = the whole tail)
+        MXY_HIP(hipStreamWaitEvent(stream, ev_join2_, 0));
+        if (last_.lookup) launch_lookup(L.lp, view, n_cu_ * L.gm[2], stream);
     }
-    if (lookup) {
-        if (L.ip_pass && no_fork) launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, stream);
-        if (no_fork || !L.split_misc) launch_lookup(L.lp, view, n_cu_ * L.gm[2], stream);   // split lists: launched on the fourth stream above
-        if (L.ip_pass && !no_fork) MXY_HIP(hipStreamWaitEvent(stream, ev_join_, 0));
-        if (L.split_misc && !no_fork && !expect_chains_) MXY_HIP(hipStreamWaitEvent(stream, ev_join3_, 0));
-        if (early_glob_ && !no_fork && glob_join3_) {
-            MXY_HIP(hipStreamWaitEvent(stream, ev_join3_, 0));
-            if (glob_v2_aside_) MXY_HIP(hipStreamWaitEvent(stream, ev_join_, 0));
-        }
+    if (L.ip_pass) MXY_HIP(hipStreamWaitEvent(stream, ev_join_, 0));
+}
+
+// Everything on the scan's stream (MATCHY_AMD_NO_FORK, submit / wait, scan_host).
+void Scanner::launch_one_stream(hipStream_t stream) {
+    const SliceLaunch& L = launch_[0];
+    const TokParams& tp = L.tp;
+    const DevDb& view = ddb_->view;
+    launch_anchor(tp, view, L.grid_anchor, stream);
+    if (profile_) MXY_HIP(hipEventRecord(ev_[1], stream));
+    launch_validate_dom(tp, view, n_cu_ * L.gm[1], stream);
+    launch_validate_misc(tp, view, grid_for(std::max(std::max(hint_.n_tok, hint_.n_rare), hint_.n_rare_dom), 1024, n_cu_, 8), stream);   // vmode 7: every list
+    if (profile_) MXY_HIP(hipEventRecord(ev_[2], stream));
+    if (rare_possible()) launch_rare(tp, view, grid_for(hint_.n_heavy, 128, n_cu_ * 4, 16), stream);
+    if (profile_) MXY_HIP(hipEventRecord(ev_[3], stream));
+    if (last_.lookup) {
+        if (L.ip_pass) launch_lookup_ip(L.la, view, L.ip_grid, L.ip_dense, stream);
+        launch_lookup(L.lp, view, n_cu_ * L.gm[2], stream);
     }
-    if (profile_) MXY_HIP(hipEventRecord(ev_[4], stream));
 }
 
 void Scanner::ensure_pinned(size_t bytes) {
@@ -1097,12 +1050,34 @@ size_t sort_hits_temp_bytes(uint32_t n);
 hipError_t sort_hits(const FinalHit* fin, uint32_t n, unsigned long long* keys, uint32_t* vals, void* temp, size_t temp_bytes, FinalHit* out,
                      hipStream_t stream);
 
+namespace {
+size_t grown(uint32_t n) { return (size_t)n + n / 4 + 1024; }
+}  // namespace
+
+// Every work list of slice `w` with the counter of its entries in `s`: f(capacity, count, grow), grow() reallocates the list for the
+// count. glob_work and spill count only while allocated, glob_work_d only with the early glob pass; the domain list is counted in
+// slots and allocated in planes; hits holds at least a quarter of the candidate list (visited behind it: its regrow counts).
+template <class F>
+void Scanner::each_list(Work& w, const ScanCounters& s, F&& f) {
+    auto list = [&](auto& b, uint32_t n) { f(b.n, n, [&b, n] { b.alloc(grown(n)); }); };
+    list(w.cands, s.n_cand); list(w.cands_a, s.n_cand_a); list(w.cands_m, s.n_cand_m); list(w.cands_r, s.n_cand_r); list(w.cands_d, s.n_cand_d);
+    list(w.rare, s.n_rare); list(w.rare_dom, s.n_rare_dom); list(w.tok, s.n_tok); list(w.heavy, s.n_heavy);
+    if (w.glob_work.n) list(w.glob_work, s.n_glob_work);
+    if (early_glob_) list(w.glob_work_d, s.n_glob_work_d);
+    if (w.spill.n) list(w.spill, s.n_spill);
+    f(w.dom_slots, s.n_dom, [&] {
+        w.dom_slots = (((size_t)s.n_dom + s.n_dom / 4 + ANCHOR_CHUNK) / ANCHOR_CHUNK) * ANCHOR_CHUNK;
+        w.dom_list.alloc(w.dom_slots * DOM_PLANES);
+    });
+    f(w.hits.n, std::max<size_t>(s.n_hits, w.cands.n / 4), [&] { w.hits.alloc(std::max<size_t>(grown(s.n_hits), w.cands.n / 4)); });
+    list(w.ids, s.n_ids);
+}
+
 // Wait for the stream. poll: the scan behind it is about a millisecond (device-resident input), and the runtime's blocking wait
 // takes ~10 us longer to notice the end — poll the stream for the first milliseconds, then block. Host-buffer scans wait for tens
 // of milliseconds of copies with other threads busy in the runtime (the command line's reader and second scanner): they block.
 static void wait_stream(hipStream_t stream, bool poll) {
-    static const bool env_block = getenv("MATCHY_AMD_BLOCKING_WAIT") != nullptr;
-    if (poll && !env_block) {
+    if (poll) {
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
             const hipError_t e = hipStreamQuery(stream);
@@ -1126,7 +1101,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         // side chains that report to k_finish end behind the last event scan_device recorded: the interval ends behind k_finish then
         if (profile_ && expect_chains_) MXY_HIP(hipEventRecord(ev_[4], stream));
         expect_chains_ = 0;   // a rescan sets it again; the spill pass below runs on this stream
-        wait_stream(stream, last_fork_);
+        wait_stream(stream, last_.fork);
         if (host_slices_[0].error & 8u) {
             // k_finish gave up polling for the side chains (they are slow, not lost): the counters it copied are a snapshot and the
             // device copies were left alone. Join the side streams here, then take the counters again without a poll.
@@ -1147,20 +1122,14 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             c.lines += s.lines; c.cand_true += s.cand_true; c.hits_true += s.hits_true; c.error |= s.error;
         }
         bool over = c.n_final > final_.n || c.n_final_ids > final_ids_.n || (compact_ && c.n_c4 > c4_.n);
-        for (int k = 0; k < ns; ++k) {
-            const ScanCounters& s = host_slices_[k];
-            const Work& w = work_[k];
-            over = over || s.n_cand > w.cands.n || s.n_cand_a > w.cands_a.n || s.n_cand_m > w.cands_m.n || s.n_cand_r > w.cands_r.n || s.n_cand_d > w.cands_d.n || s.n_rare > w.rare.n || s.n_rare_dom > w.rare_dom.n || s.n_tok > w.tok.n ||
-                   s.n_heavy > w.heavy.n || (w.glob_work.n && s.n_glob_work > w.glob_work.n) || (early_glob_ && s.n_glob_work_d > w.glob_work_d.n) || s.n_hits > w.hits.n || s.n_ids > w.ids.n ||
-                   s.n_dom > w.dom_slots || (w.spill.n && s.n_spill > w.spill.n);
-        }
+        for (int k = 0; k < ns; ++k) each_list(work_[k], host_slices_[k], [&](size_t cap, size_t need, auto&&) { over = over || need > cap; });
         if (!over) {
             // candidates the glob pass could not hold (more results / deeper star nesting than a lane stores): normally none.
             // If there are, the spill pass runs now — its scratch (one bit per pattern id per thread) is allocated only here — and
             // appends their records to the same arrays; the counters are read again afterwards.
             uint32_t n_spill = 0;
             for (int k = 0; k < ns; ++k) n_spill += work_[k].spill.n ? host_slices_[k].n_spill : 0u;
-            if (n_spill == 0 || spill_done_ || !last_lookup_) break;
+            if (n_spill == 0 || spill_done_ || !last_.lookup) break;
             const uint32_t threads = spill_threads();
             const size_t words = launch_[0].lp.spill_words;
             if (spill_scratch_.n < words * SPILL_BLOCKS * threads) spill_scratch_.alloc(words * SPILL_BLOCKS * threads);
@@ -1181,30 +1150,10 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         if (single_) throw HipError{"lookup_one: work buffers overflow"};
         if (attempt >= 5) throw HipError{"scan: work buffers still overflow after regrowing"};
         // grow and run again: the kernels count past the capacity without writing, so the counts are exact demands
-        auto grown = [](uint32_t n) { return (size_t)n + n / 4 + 1024; };
         size_t recs = 0, ids = 0;
         for (int k = 0; k < ns; ++k) {
-            const ScanCounters& s = host_slices_[k];
-            Work& w = work_[k];
-            if (s.n_cand > w.cands.n) w.cands.alloc(grown(s.n_cand));
-            if (s.n_cand_a > w.cands_a.n) w.cands_a.alloc(grown(s.n_cand_a));
-            if (s.n_cand_m > w.cands_m.n) w.cands_m.alloc(grown(s.n_cand_m));
-            if (s.n_cand_r > w.cands_r.n) w.cands_r.alloc(grown(s.n_cand_r));
-            if (s.n_cand_d > w.cands_d.n) w.cands_d.alloc(grown(s.n_cand_d));
-            if (s.n_rare > w.rare.n) w.rare.alloc(grown(s.n_rare));
-            if (s.n_rare_dom > w.rare_dom.n) w.rare_dom.alloc(grown(s.n_rare_dom));
-            if (s.n_tok > w.tok.n) w.tok.alloc(grown(s.n_tok));
-            if (s.n_heavy > w.heavy.n) w.heavy.alloc(grown(s.n_heavy));
-            if (w.glob_work.n && s.n_glob_work > w.glob_work.n) w.glob_work.alloc(grown(s.n_glob_work));
-            if (early_glob_ && s.n_glob_work_d > w.glob_work_d.n) w.glob_work_d.alloc(grown(s.n_glob_work_d));
-            if (w.spill.n && s.n_spill > w.spill.n) w.spill.alloc(grown(s.n_spill));
-            if (s.n_dom > w.dom_slots) {
-                w.dom_slots = (((size_t)s.n_dom + s.n_dom / 4 + ANCHOR_CHUNK) / ANCHOR_CHUNK) * ANCHOR_CHUNK;
-                w.dom_list.alloc(w.dom_slots * DOM_PLANES);
-            }
-            if (s.n_hits > w.hits.n || w.hits.n < w.cands.n / 4) w.hits.alloc(std::max<size_t>(grown(s.n_hits), w.cands.n / 4));
-            if (s.n_ids > w.ids.n) w.ids.alloc(grown(s.n_ids));
-            recs += w.hits.n; ids += w.ids.n;
+            each_list(work_[k], host_slices_[k], [](size_t cap, size_t need, auto&& grow) { if (need > cap) grow(); });
+            recs += work_[k].hits.n; ids += work_[k].ids.n;
         }
         if (final_.n < recs || c.n_final > final_.n) final_.alloc(std::max<size_t>(recs, grown(c.n_final)));
         if (final_ids_.n < recs + ids || c.n_final_ids > final_ids_.n) {
@@ -1212,7 +1161,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             final_ids_.alloc(want); final_offs_.alloc(want);
         }
         if (compact_ && c.n_c4 > c4_.n) c4_.alloc(grown(c.n_c4));
-        scan_device(last_ptr_, last_len_, last_lookup_, stream, last_mirror_, last_fork_, last_slices_, last_compact_);
+        scan_device(last_, stream);
     }
     {
         ListHint hh;
@@ -1240,7 +1189,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
                 ns, c.lines, t.n_dom, t.n_rare, t.n_rare_dom, t.n_tok, t.n_heavy, t.n_cand_a, t.n_cand, c.cand_true, t.n_hits, c.hits_true, t.n_ids, t.n_glob_work, c.n_final);
     }
     out.lines = c.lines; out.n_cand = single_ ? c.n_cand : c.cand_true;
-    out.n_hits = !last_lookup_ ? 0 : (single_ ? c.hits_true : c.n_final + (compact_ ? c.n_c4 : 0u));
+    out.n_hits = !last_.lookup ? 0 : (single_ ? c.hits_true : c.n_final + (compact_ ? c.n_c4 : 0u));
     if (profile_) {
         MXY_HIP(hipEventElapsedTime(&timing_.anchor_ms, ev_[0], ev_[1]));
         if (last_forked_) {   // one interval for everything behind k_anchor (kernels on three streams)
@@ -1259,8 +1208,8 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     out.c4 = nullptr; out.n_c4 = 0;
     const bool had_mirror = mirror_used_;
     Work& w0 = work_[0];   // raw hits and candidate lists are read by one-slice scans only (single queries, extraction)
-    const bool get_raw = last_lookup_ && hit_mode == HITS_RAW && c.n_hits;
-    const bool get_fin = last_lookup_ && hit_mode == HITS_FINAL && c.n_final;
+    const bool get_raw = last_.lookup && hit_mode == HITS_RAW && c.n_hits;
+    const bool get_fin = last_.lookup && hit_mode == HITS_FINAL && c.n_final;
     if ((get_raw || want_cands) && ns != 1) throw HipError{"fetch: raw hits / candidates of a sliced scan"};
     // D2H into pinned memory (pageable destinations run at a fraction of the PCIe rate)
     if (get_raw) {
@@ -1304,7 +1253,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         out.fin = (const FinalHit*)base; out.n_fin = c.n_final;
         out.fin_ids = (const uint32_t*)(base + hb); out.fin_offs = (const long long*)(base + hb + ib); out.n_fin_ids = c.n_final_ids;
     }
-    if (last_lookup_ && hit_mode == HITS_FINAL && compact_ && c.n_c4) {
+    if (last_.lookup && hit_mode == HITS_FINAL && compact_ && c.n_c4) {
         if (had_mirror && !sorted && c.n_c4 <= mirror_c4_cap_) out.c4 = mirror_c4_;   // written by the kernels
         else {
             if (had_mirror) { mirror_used_ = false; ensure_mirror_c4(c.n_c4 + c.n_c4 / 2); }   // a larger mirror next time
@@ -1324,7 +1273,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         if (c.n_cand_a) MXY_HIP(hipMemcpyAsync(out.cands.data(), w0.cands_a.p, (size_t)c.n_cand_a * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
         if (c.n_cand) MXY_HIP(hipMemcpyAsync(out.cands.data() + c.n_cand_a, w0.cands.p, (size_t)c.n_cand * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     }
-    wait_stream(stream, last_fork_);
+    wait_stream(stream, last_.fork);
     if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
     // drop the padding slots of partially filled chunks
     if (get_raw) {
@@ -1374,7 +1323,7 @@ void Scanner::lookup_one(const std::string& text, Candidate c, ScanOutput& out) 
     launch_lookup(lp, ddb_->view, 1, nullptr);
     launch_[0].lp = lp;   // fetch() launches the spill pass from here if the candidate spilled
     n_slices_ = 1; spill_done_ = false;
-    last_lookup_ = true; last_ptr_ = staging_.p; last_len_ = (uint32_t)text.size();
+    last_.lookup = true; last_.ptr = staging_.p; last_.len = (uint32_t)text.size();
     bool prof = profile_;
     profile_ = false;
     single_ = true;
@@ -1435,7 +1384,9 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             MXY_HIP(hipMemcpyAsync(staging_.p + head, reg_lo, reg_len, hipMemcpyHostToDevice, host_stream_));
             if (tail) MXY_HIP(hipMemcpyAsync(staging_.p + head + reg_len, reg_lo + reg_len, tail, hipMemcpyHostToDevice, host_stream_));
         } else if (n) MXY_HIP(hipMemcpyAsync(staging_.p, src, n, hipMemcpyHostToDevice, host_stream_));
-        scan_device(staging_.p, (uint32_t)n, lookup, host_stream_);
+        ScanRequest rq;
+        rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup;
+        scan_device(rq, host_stream_);
         ScanOutput part;
         const double t_launch = ms_since(th0);
         fetch(part, want_cands, host_stream_, lookup && fin ? HITS_FINAL : HITS_NONE, true);   // synchronises the stream: the copy is done

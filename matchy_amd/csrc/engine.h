@@ -127,22 +127,29 @@ int add_caller(const void* ptr, size_t bytes);
 void remove_caller(const void* ptr);
 }
 
+// What Scanner::scan_device scans and how. `ptr` is `len` bytes resident in device memory (16-byte aligned), len < 2^31.
+struct ScanRequest {
+    const uint8_t* ptr = nullptr;
+    uint32_t len = 0;
+    bool lookup = false;       // false stops after extraction
+    // pack_record also writes the final records into pinned host memory (unsorted fetches then need no copy)
+    bool host_mirror = false;
+    // run the parts of the scan that do not depend on each other on the scanner's extra streams (engine.cpp). For ONE batch at a
+    // time on device-resident input; callers that keep several batches in flight (submit / wait) or whose time is the host-to-device
+    // copy (scan_host) stay on one stream per scanner: the runtime multiplexes streams onto a few hardware queues, and three
+    // scanners with three streams each ran 25 % slower than with one each.
+    bool fork = false;
+    int slices = 0;            // with fork: cut the batch into that many slices (see Scanner::MAX_SLICES); 0 = the default (one slice)
+    bool compact = false;      // IPv4 results leave as 8-byte records (ScanOutput::c4, scan_types.h c4_pack) when compact_possible()
+};
+
 // A scan session: owns the per-launch work buffers on one device. Not thread-safe; create one per thread/stream.
 class Scanner {
 public:
     Scanner(std::shared_ptr<const DbImage> img, std::shared_ptr<DeviceDb> ddb, uint32_t extract_flags, uint32_t min_labels);
     ~Scanner();
-    // Scan `len` bytes already resident in device memory (16-byte aligned). len < 2^31.
-    // lookup=false stops after extraction. Results stay on the device until fetch().
-    // host_mirror: pack_record also writes the final records into pinned host memory (unsorted fetches then need no copy)
-    // fork: run the parts of the scan that do not depend on each other on the scanner's two extra streams (engine.cpp). For ONE
-    // batch at a time on device-resident input; callers that keep several batches in flight (submit / wait) or whose time is the
-    // host-to-device copy (scan_host) stay on one stream per scanner: the runtime multiplexes streams onto a few hardware queues,
-    // and three scanners with three streams each ran 25 % slower than with one each.
-    // slices > 1 (with fork): cut the batch into that many slices (see MAX_SLICES); 0 = the scanner's default for the batch size
-    // compact: IPv4 results leave as 8-byte records (ScanOutput::c4, scan_types.h c4_pack) when compact_possible()
-    void scan_device(const uint8_t* dptr, uint32_t len, bool lookup, hipStream_t stream, bool host_mirror = false, bool fork = false, int slices = 0,
-                     bool compact = false);
+    // Launches the scan of `rq` on `stream`. Results stay on the device until fetch().
+    void scan_device(const ScanRequest& rq, hipStream_t stream);
     // the compact record holds data-section offsets of C4_DATA_BITS bits: every offset an IP result of this database can carry must fit
     bool compact_possible() const { return img_->max_ip_data_offset() < (1u << C4_DATA_BITS); }
     // Copies counters (and hits / candidates) back. Call after scan_device; synchronises the stream.
@@ -160,7 +167,7 @@ public:
     void scan_host(const uint8_t* data, size_t len, bool lookup, bool want_cands, ScanOutput& out, std::vector<uint64_t>* cand_bases,
                    std::vector<FinalHit>* fin, std::vector<uint32_t>* fin_ids, std::vector<long long>* fin_offs);
     void set_profile(bool on) { profile_ = on; }
-    // slices of the forked scan_device: 0 = default for the batch size (MATCHY_AMD_SLICES overrides), 1 = never cut, n = n equal slices
+    // slices of the forked scan_device: 0 = default for the batch size (one slice), 1 = never cut, n = n equal slices
     void set_slices(int n) { slices_ = n < 0 ? 0 : n; }
     int slices() const { return slices_; }
     int last_slice_count() const { return n_slices_; }
@@ -206,11 +213,18 @@ private:
         bool ip_pass = false, ip_dense = false;
     };
     SliceLaunch launch_[MAX_SLICES];
-    void slice_params(int sl, const uint8_t* dptr, uint32_t len, uint32_t lo, uint32_t hi, bool lookup, bool host_mirror, SliceLaunch& L);
+    void slice_params(int sl, const ScanRequest& rq, uint32_t lo, uint32_t hi, SliceLaunch& L);
     int plan_slices(uint32_t len, int want, uint32_t (&cuts)[MAX_SLICES + 1]);
     void setup_spill(int sl, LookupParams& lp);
+    // the launch schedules of scan_device: slices on the side streams / one slice forked onto them / everything on `stream`
+    void launch_sliced(int ns, hipStream_t stream);
+    void launch_forked(hipStream_t stream);
+    void launch_one_stream(hipStream_t stream);
+    void ensure_dom_stream();       // the fourth stream and its events, created at first use
+    bool rare_possible() const { return (flags_ & (EX_HASHES | EX_BITCOIN | EX_ETHEREUM | EX_MONERO)) != 0; }
+    // visits every (work list, counter) pair of a slice for fetch's overflow test and regrow
+    template <class F> void each_list(Work& w, const ScanCounters& s, F&& f);
     bool spill_done_ = false;
-    bool glob_join3_ = false, glob_v2_aside_ = false;   // early glob pass joined by event (MATCHY_AMD_EVENT_JOIN); k_validate<2> and its lookups on the second stream
     bool early_glob_ = false;       // last scan_device: the glob pass over k_validate_dom's flagged candidates runs beside the lean pass
     uint32_t expect_chains_ = 0;    // side-stream chains of the last scan_device that report their end to k_finish (0: event joins)
     // List sizes of the PREVIOUS scan of this scanner (fetch): the grids of the kernels behind the streaming pass are sized for the
@@ -222,7 +236,7 @@ private:
     uint32_t dom_want_ = 0;     // ... and what the scan in flight asked for
     int grid_for(uint32_t n_hint, uint32_t per_wg, int dflt, int max_per_cu) const;
     bool counters_clean_ = false;   // the device counter blocks are zero (k_finish of the last fetch left them so)
-    int last_slices_ = 0;
+    ScanRequest last_;              // of the last scan_device (fetch runs it again after regrowing the work lists)
     std::shared_ptr<const DbImage> img_;
     std::shared_ptr<DeviceDb> ddb_;
     hipStream_t host_stream_ = nullptr;   // scan_host: this scanner's own non-blocking stream
@@ -253,7 +267,7 @@ private:
     // pinned mirror of the final records written by the lookup kernels themselves: FinalHit[mirror_cap_] | u32 ids[mirror_ids_cap_] | i64 offs[..]
     void* mirror_ = nullptr;
     uint32_t mirror_cap_ = 0, mirror_ids_cap_ = 0;
-    bool mirror_used_ = false, last_mirror_ = false;
+    bool mirror_used_ = false;
     void ensure_mirror(uint32_t recs, uint32_t ids);
     // compact IPv4 records (scan_device `compact`): device array, pinned mirror written by the kernels, pinned block of the copy path
     DevBuf<uint2> c4_;
@@ -262,15 +276,13 @@ private:
     void ensure_mirror_c4(uint32_t recs);
     uint2* pinned_c4_ = nullptr;
     size_t pinned_c4_n_ = 0;
-    bool compact_ = false, last_compact_ = false;   // of the last scan_device: in effect / as asked for
+    bool compact_ = false;   // of the last scan_device: in effect
     void* pinned_ = nullptr;   // one pinned block: FinalHit[n] | u32 ids[m] | i64 offs[m]  (or Hit[n] for HITS_RAW)
     size_t pinned_bytes_ = 0;
     void ensure_pinned(size_t bytes);
     ScanCounters host_counters_{};             // the slices' counters summed (list counters: of slice 0 for one-slice scans)
     ScanCounters* host_slices_ = nullptr;      // pinned: MAX_SLICES counter blocks as read back
-    uint32_t last_len_ = 0;
-    const uint8_t* last_ptr_ = nullptr;
-    bool last_lookup_ = false, last_fork_ = false, last_forked_ = false;
+    bool last_forked_ = false;
     bool single_ = false;
     bool profile_ = false;
     hipEvent_t ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
