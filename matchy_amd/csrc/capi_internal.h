@@ -1,0 +1,24 @@
+// What capi.cpp and multi_scanner.cpp share behind the C ABI, and nothing else.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/matchy_amd.h"
+
+namespace mxy {
+namespace capi {
+
+void set_error(const std::string& e);           // the calling thread's matchy_amd_last_error()
+int default_device_of(const matchy_t* db);      // the HIP device a handle's scanners use when none is named
+
+struct ScanResultInternal {
+    std::vector<matchy_scan_hit_t> hits;
+    std::vector<uint32_t> ids;
+    std::vector<int64_t> offs;
+    bool on_device = false;   // MATCHY_SCAN_FETCH_DEVICE: the result's arrays are device pointers
+};
+
+}  // namespace capi
+}  // namespace mxy

@@ -42,6 +42,7 @@
 #include "../../include/matchy_amd.h"
 #include "data_codec.h"
 #include "db_builder.h"
+#include "batch_reader.h"
 #include "db_image.h"
 
 using namespace mxy;
@@ -290,20 +291,8 @@ struct Totals {
 // regular files are mapped, .gz / stdin are read), the batch hook renders a batch's matches on the worker that scanned it, and the
 // printer emits the rendered batches in sequence order, so the output is the same for every device list (line blocks
 // are independent, the database is replicated, the host gathers the hit records and sums the counters; no collective).
-// bytes without the value-initialisation of std::vector (a 256 MiB batch buffer would be zeroed before every read)
-struct RawBuf {
-    std::unique_ptr<uint8_t[]> p;
-    size_t cap = 0;
-    explicit RawBuf(size_t n = 0) : p(n ? new uint8_t[n] : nullptr), cap(n) {}
-    uint8_t* data() { return p.get(); }
-    void grow(size_t n, size_t keep) {
-        std::unique_ptr<uint8_t[]> q(new uint8_t[n]);
-        if (keep) memcpy(q.get(), p.get(), keep);
-        p = std::move(q); cap = n;
-    }
-};
 // `ptr` points into `own` (inputs that are read: stdin, .gz) or into a file mapping that outlives the batch
-struct Batch { size_t input = 0; RawBuf own; const uint8_t* ptr = nullptr; size_t len = 0; bool mapped = false;
+struct Batch { size_t input = 0; Bytes own; const uint8_t* ptr = nullptr; size_t len = 0; bool mapped = false;
                const void* reg = nullptr; };   // reg: page range of a mapped batch the reader pinned ahead of the scan (unpinned by the worker)
 // what a batch contributes to the output: `text` / `text_len` is the buffer matchy_scan_result_to_ndjson returned (written to stdout as
 // it is and released by the printer: 200 bytes per match are not copied again on the way), `out` what --follow builds from it
@@ -452,28 +441,10 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
             const uint8_t* base = (const uint8_t*)m;
             size_t last_seq = 0;
             for (size_t pos = 0; pos < size;) {
-                size_t end = std::min(size, pos + batch_bytes);
-                if (end < size) {   // newline-aligned cut; a line longer than the batch extends it to that line's end
-                    const void* nl = memrchr(base + pos, '\n', end - pos);
-                    if (nl) end = (const uint8_t*)nl - base + 1;
-                    else {
-                        const void* fw = memchr(base + end, '\n', size - end);
-                        end = fw ? (size_t)((const uint8_t*)fw - base) + 1 : size;
-                    }
-                }
+                const size_t end = newline_cut(base, pos, size, batch_bytes);
                 Batch b;
                 b.input = input; b.ptr = base + pos; b.len = end - pos; b.mapped = true;
-                // This (reader) thread faults the batch's pages in and pins them; the workers only copy, scan and post-process. With
-                // every worker doing its own page faults and pinning, the address-space lock of the process was the limit
-                // (four workers: 28-31 GB/s; with the reader feeding them: 42-45). MATCHY_AMD_NO_FEEDER=1 restores that.
-                static const bool feeder = getenv("MATCHY_AMD_NO_FEEDER") == nullptr;
-                if (feeder && b.len >= ((size_t)4 << 20)) {
-                    const uintptr_t a = ((uintptr_t)b.ptr + 4095) & ~(uintptr_t)4095, z = ((uintptr_t)b.ptr + b.len) & ~(uintptr_t)4095;
-#ifdef MADV_POPULATE_READ
-                    (void)madvise((void*)((uintptr_t)b.ptr & ~(uintptr_t)4095), (uintptr_t)b.ptr + b.len - ((uintptr_t)b.ptr & ~(uintptr_t)4095), MADV_POPULATE_READ);
-#endif
-                    if (z > a && matchy_amd_host_register((const void*)a, z - a) == MATCHY_SUCCESS) b.reg = (const void*)a;
-                }
+                b.reg = prefault_and_pin(b.ptr, b.len);
                 last_seq = pl.submit(std::move(b));
                 pos = end;
             }
@@ -488,39 +459,23 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
         if (!zf) { fprintf(stderr, "[ERROR] Failed to process %s: cannot start gzip decoder\n", path.c_str()); close(fd); return false; }
         gzbuffer(zf, 1u << 20);
     }
-    RawBuf buf(batch_bytes + 16);
-    size_t have = 0, total_read = 0;
-    bool ok = true;
-    auto send = [&](RawBuf&& data, size_t len) {
-        Batch b;
-        b.input = input; b.own = std::move(data); b.ptr = b.own.data(); b.len = len;
-        pl.submit(std::move(b));
-    };
-    for (;;) {
-        if (have == buf.cap - 16) buf.grow(buf.cap * 2, have);  // a single line longer than the batch: grow
-        const size_t room = buf.cap - 16 - have;
-        ssize_t n;
-        if (gz) {
-            n = gzread(zf, buf.data() + have, (unsigned)std::min<size_t>(room, 1u << 30));
-            if (n < 0) { int e; fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), gzerror(zf, &e)); ok = false; break; }
-        } else {
-            n = read(fd, buf.data() + have, room);
-            if (n < 0) { fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), strerror(errno)); ok = false; break; }
-        }
-        have += (size_t)n;
-        total_read += (size_t)n;
-        if (n == 0) { send(std::move(buf), have); break; }
-        if (have < batch_bytes) continue;
-        // newline-aligned cut: scan up to the last '\n', carry the rest into the next batch's buffer
-        const void* nl = memrchr(buf.data(), '\n', have);
-        if (!nl) continue;
-        const size_t cut = (const uint8_t*)nl - buf.data() + 1;
-        RawBuf nxt(std::max(batch_bytes, have - cut) + 16);
-        memcpy(nxt.data(), buf.data() + cut, have - cut);
-        send(std::move(buf), cut);
-        buf = std::move(nxt);
-        have -= cut;
-    }
+    size_t total_read = 0;
+    const StreamEnd e = read_batches(
+        [&](void* p, size_t n) {
+            const ssize_t r = gz ? (ssize_t)gzread(zf, p, (unsigned)n) : read(fd, p, n);
+            if (r < 0 && gz) errno = EIO;   // the decoder keeps its error: a retry would fail again
+            return r;
+        },
+        batch_bytes,
+        [&](Bytes&& data, size_t len, uint64_t) {
+            Batch b;
+            b.input = input; b.ptr = data.get(); b.len = len; b.own = std::move(data);
+            pl.submit(std::move(b));
+            total_read += len;
+            return true;
+        });
+    const bool ok = e == StreamEnd::DONE;
+    if (!ok) { int ze; fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), gz && errno == EIO ? gzerror(zf, &ze) : strerror(errno)); }
     if (gz) gzclose(zf);   // closes fd as well
     else if (fd) close(fd);
     if (ok && !gz && fd != 0 && input < pl.consumed.size()) pl.consumed[input] = (long long)total_read;
@@ -565,10 +520,11 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
             if (fd < 0) continue;
             Batch b;
             b.input = tl.input;
-            b.own = RawBuf((size_t)(sb.st_size - tl.pos) + 16);
+            b.own.reset((uint8_t*)malloc((size_t)(sb.st_size - tl.pos) + 16));
+            if (!b.own) { close(fd); continue; }
             size_t have = 0;
             while (have < (size_t)(sb.st_size - tl.pos)) {
-                const ssize_t n = pread(fd, b.own.data() + have, (size_t)(sb.st_size - tl.pos) - have, tl.pos + (off_t)have);
+                const ssize_t n = pread(fd, b.own.get() + have, (size_t)(sb.st_size - tl.pos) - have, tl.pos + (off_t)have);
                 if (n <= 0) break;
                 have += (size_t)n;
             }
@@ -576,7 +532,7 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
             tl.pos += (off_t)have;
             if (!have) continue;
             any = true;
-            b.ptr = b.own.data(); b.len = have;
+            b.ptr = b.own.get(); b.len = have;
             Done d;
             pl.run_batch(sc, b, d);
             if (d.text_len) d.out.assign(d.text, d.text_len);
@@ -1004,22 +960,11 @@ int cmd_extract(int argc, char** argv) {
     for (const std::string& path : inputs) {
         int fd = path == "-" ? 0 : open(path.c_str(), O_RDONLY);
         if (fd < 0) { fprintf(stderr, "Error: Failed to open file: %s\n", path.c_str()); ok = false; break; }
-        std::vector<uint8_t> buf(batch_bytes + 16);
-        size_t have = 0;
-        for (;;) {
-            if (have == buf.size() - 16) buf.resize(buf.size() * 2);
-            const ssize_t n = read(fd, buf.data() + have, buf.size() - 16 - have);
-            if (n < 0) { fprintf(stderr, "Error: read failed on %s: %s\n", path.c_str(), strerror(errno)); ok = false; break; }
-            have += (size_t)n;
-            if (n == 0) { ok = extract_batch(ex, buf.data(), have, fmt, show_cand, unique ? &seen_sorted : nullptr, seen_new, st) && ok; break; }
-            if (have < batch_bytes) continue;
-            const void* nlp = memrchr(buf.data(), '\n', have);
-            if (!nlp) continue;
-            const size_t cut = (const uint8_t*)nlp - buf.data() + 1;
-            if (!extract_batch(ex, buf.data(), cut, fmt, show_cand, unique ? &seen_sorted : nullptr, seen_new, st)) { ok = false; break; }
-            memmove(buf.data(), buf.data() + cut, have - cut);
-            have -= cut;
-        }
+        const StreamEnd e = read_batches([&](void* p, size_t n) { return read(fd, p, n); }, batch_bytes, [&](Bytes&& data, size_t len, uint64_t) {
+            return extract_batch(ex, data.get(), len, fmt, show_cand, unique ? &seen_sorted : nullptr, seen_new, st);
+        });
+        if (e == StreamEnd::FAILED) fprintf(stderr, "Error: read failed on %s: %s\n", path.c_str(), strerror(errno));
+        ok = e == StreamEnd::DONE;
         if (fd) close(fd);
         if (!ok) break;
     }

@@ -1,4 +1,5 @@
 #include "engine.h"
+#include "batch_reader.h"
 #include "unicode_lower.h"
 
 #include <dlfcn.h>
@@ -1348,12 +1349,8 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     if (cand_bases) cand_bases->clear();
     if (fin) { fin->clear(); fin_ids->clear(); fin_offs->clear(); }
     do {
-        size_t n = std::min(MAXC, len - pos);
-        if (pos + n < len) {
-            const void* nl = memrchr(data + pos, '\n', n);
-            if (!nl) throw HipError{"scan_host: a single line exceeds 1 GiB"};
-            n = (const uint8_t*)nl - (data + pos) + 1;
-        }
+        const size_t n = newline_cut(data, pos, len, MAXC) - pos;
+        if (n > MAXC) throw HipError{"scan_host: a single line exceeds 1 GiB"};
         if (staging_.n < n + 16) staging_.alloc(n + 16 + n / 8);
         // Pageable host memory (a mapped file, a heap buffer) reaches the device through the runtime's own pinned staging at
         // ~20 GB/s; pinned for the duration of the copy (hipHostRegister: ~5 ms per GB, tools/ubench/h2d_rate2.cpp) the DMA
@@ -1370,11 +1367,11 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         bool mine = false;   // this call pinned the range (and unpins it)
         static const bool no_reg = getenv("MATCHY_AMD_NO_REGISTER") != nullptr;
         if (!no_reg && n >= ((size_t)4 << 20)) {
-            const uintptr_t a = ((uintptr_t)src + 4095) & ~(uintptr_t)4095, b = ((uintptr_t)src + n) & ~(uintptr_t)4095;
+            uintptr_t a, b;
             // pins::acquire: the whole range is covered by a pin of this library (the caller's, or another scanner's transient one —
             // its count goes up, so it stays pinned until this copy is done too), or it is pinned now. Anything else (memory someone
             // else pinned, a partial overlap, a failed registration) takes the one plain copy below.
-            if (b > a && pins::acquire(a, b)) { reg_lo = (const uint8_t*)a; reg_len = b - a; mine = true; }
+            if (inner_pages(src, n, a, b) && pins::acquire(a, b)) { reg_lo = (const uint8_t*)a; reg_len = b - a; mine = true; }
         }
         struct Unreg { uintptr_t a, b; ~Unreg() { if (b > a) pins::release(a, b); } } unreg{mine ? (uintptr_t)reg_lo : 0, mine ? (uintptr_t)reg_lo + reg_len : 0};
         const double t_reg = ms_since(th0);
@@ -1397,17 +1394,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         }
         out.lines += part.lines; out.n_cand += part.n_cand; out.n_hits += part.n_hits;
         for (int t = 0; t < IT_COUNT; ++t) out.by_type[t] += part.by_type[t];
-        if (fin && part.n_fin) {
-            const uint32_t id_shift = (uint32_t)fin_ids->size();
-            for (size_t i = 0; i < part.n_fin; ++i) {
-                FinalHit h = part.fin[i];
-                h.start += (uint32_t)pos;   // len < 4 GiB is checked by the caller
-                if (h.kind == 3) h.value += id_shift;
-                fin->push_back(h);
-            }
-            fin_ids->insert(fin_ids->end(), part.fin_ids, part.fin_ids + part.n_fin_ids);
-            fin_offs->insert(fin_offs->end(), part.fin_offs, part.fin_offs + part.n_fin_ids);
-        }
+        if (fin && part.n_fin) append_shifted(part.fin, part.n_fin, part.fin_ids, part.fin_offs, part.n_fin_ids, (uint32_t)pos, *fin, *fin_ids, *fin_offs);
         for (const Candidate& c : part.cands) { all_cands.push_back(c); if (cand_bases) cand_bases->push_back(pos); }
         pos += n;
     } while (pos < len);

@@ -127,6 +127,22 @@ int add_caller(const void* ptr, size_t bytes);
 void remove_caller(const void* ptr);
 }
 
+// Merge the dense records of a piece that starts `base` bytes into the whole: starts move by `base`, a glob record (kind 3: `value`
+// is the index of its id list) moves behind the ids gathered so far. Hit is FinalHit or matchy_scan_hit_t (same layout, capi.cpp).
+template <class Hit, class Off, class OffOut>
+void append_shifted(const Hit* hits, size_t n_hits, const uint32_t* ids, const Off* offs, size_t n_ids, uint32_t base,
+                    std::vector<Hit>& all_hits, std::vector<uint32_t>& all_ids, std::vector<OffOut>& all_offs) {
+    const uint32_t id_shift = (uint32_t)all_ids.size();
+    for (size_t i = 0; i < n_hits; ++i) {
+        Hit h = hits[i];
+        h.start += base;   // the whole is below 4 GiB (checked by the callers)
+        if (h.kind == 3) h.value += id_shift;
+        all_hits.push_back(h);
+    }
+    all_ids.insert(all_ids.end(), ids, ids + n_ids);
+    all_offs.insert(all_offs.end(), offs, offs + n_ids);
+}
+
 // What Scanner::scan_device scans and how. `ptr` is `len` bytes resident in device memory (16-byte aligned), len < 2^31.
 struct ScanRequest {
     const uint8_t* ptr = nullptr;

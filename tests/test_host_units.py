@@ -23,6 +23,15 @@ def test_xxh64_stream(tmp_path):
     assert "xxh64 stream ok" in out
 
 
+def test_batch_reader_cuts_and_pages(tmp_path):
+    # batch_reader.h under AddressSanitizer + UBSan, alone (no library): newline_cut on random buffers (empty, no newline, only
+    # newlines, lines of several batches, exact multiples of the batch) covers the input, ends every batch but the last in a newline
+    # and exceeds the batch only by one line; the stream batcher, fed random short reads and EINTR, cuts where newline_cut cuts the
+    # whole buffer; inner_pages holds exactly the whole pages of unaligned ranges shorter and longer than a page
+    out = _build_and_run("tests/cpp/test_batch_reader.cpp", tmp_path, extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
+    assert "batch_reader ok: 6000 buffers" in out
+
+
 def test_mutated_database_files_under_sanitizers(tmp_path):
     # The host side of the .mxy reader under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): mutated
     # copies of builder-made and handmade databases are either rejected with a message or opened and then walked the way the
