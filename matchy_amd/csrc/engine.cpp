@@ -1055,23 +1055,24 @@ namespace {
 size_t grown(uint32_t n) { return (size_t)n + n / 4 + 1024; }
 }  // namespace
 
-// Every work list of slice `w` with the counter of its entries in `s`: f(capacity, count, grow), grow() reallocates the list for the
-// count. glob_work and spill count only while allocated, glob_work_d only with the early glob pass; the domain list is counted in
+// Every work list of slice `w` with the counter of its entries in `s`: f(name, capacity, count, grow), grow() reallocates the list for
+// the count. glob_work and spill count only while allocated, glob_work_d only with the early glob pass; the domain list is counted in
 // slots and allocated in planes; hits holds at least a quarter of the candidate list (visited behind it: its regrow counts).
 template <class F>
 void Scanner::each_list(Work& w, const ScanCounters& s, F&& f) {
-    auto list = [&](auto& b, uint32_t n) { f(b.n, n, [&b, n] { b.alloc(grown(n)); }); };
-    list(w.cands, s.n_cand); list(w.cands_a, s.n_cand_a); list(w.cands_m, s.n_cand_m); list(w.cands_r, s.n_cand_r); list(w.cands_d, s.n_cand_d);
-    list(w.rare, s.n_rare); list(w.rare_dom, s.n_rare_dom); list(w.tok, s.n_tok); list(w.heavy, s.n_heavy);
-    if (w.glob_work.n) list(w.glob_work, s.n_glob_work);
-    if (early_glob_) list(w.glob_work_d, s.n_glob_work_d);
-    if (w.spill.n) list(w.spill, s.n_spill);
-    f(w.dom_slots, s.n_dom, [&] {
+    auto list = [&](const char* name, auto& b, uint32_t n) { f(name, b.n, n, [&b, n] { b.alloc(grown(n)); }); };
+    list("cands", w.cands, s.n_cand); list("cands_a", w.cands_a, s.n_cand_a); list("cands_m", w.cands_m, s.n_cand_m);
+    list("cands_r", w.cands_r, s.n_cand_r); list("cands_d", w.cands_d, s.n_cand_d);
+    list("rare", w.rare, s.n_rare); list("rare_dom", w.rare_dom, s.n_rare_dom); list("tok", w.tok, s.n_tok); list("heavy", w.heavy, s.n_heavy);
+    if (w.glob_work.n) list("glob_work", w.glob_work, s.n_glob_work);
+    if (early_glob_) list("glob_work_d", w.glob_work_d, s.n_glob_work_d);
+    if (w.spill.n) list("spill", w.spill, s.n_spill);
+    f("dom_list", w.dom_slots, s.n_dom, [&] {
         w.dom_slots = (((size_t)s.n_dom + s.n_dom / 4 + ANCHOR_CHUNK) / ANCHOR_CHUNK) * ANCHOR_CHUNK;
         w.dom_list.alloc(w.dom_slots * DOM_PLANES);
     });
-    f(w.hits.n, std::max<size_t>(s.n_hits, w.cands.n / 4), [&] { w.hits.alloc(std::max<size_t>(grown(s.n_hits), w.cands.n / 4)); });
-    list(w.ids, s.n_ids);
+    f("hits", w.hits.n, std::max<size_t>(s.n_hits, w.cands.n / 4), [&] { w.hits.alloc(std::max<size_t>(grown(s.n_hits), w.cands.n / 4)); });
+    list("ids", w.ids, s.n_ids);
 }
 
 // Wait for the stream. poll: the scan behind it is about a millisecond (device-resident input), and the runtime's blocking wait
@@ -1096,7 +1097,14 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     const int ns = n_slices_;
-    for (int attempt = 0;; ++attempt) {
+    // `attempt` counts the regrows of this fetch. While a list is over, its consumers see min(counter, capacity) entries and everything
+    // downstream of it under-counts; the most upstream list that is over has an exact count (nothing in front of it was cut), so every
+    // regrow settles at least one more stage of the chain for good. The longest chain of lists is dom_list -> rare_dom -> cands_d ->
+    // glob_work -> spill -> ids -> final_ids_ -> c4_ (the other roads are shorter): a scan whose kernels count right needs at most
+    // MAX_REGROWS regrows, and one that is still over after that many is a miscount, not a dense batch. The spill pass reads the
+    // counters again without regrowing anything and is not counted.
+    constexpr int MAX_REGROWS = 8;
+    for (int attempt = 0;;) {
         // k_finish: the counter blocks go to pinned host memory and are cleared on the device for the next scan
         launch_finish(counters_.p, host_slices_, ns, expect_chains_, dom_want_, stream);
         // side chains that report to k_finish end behind the last event scan_device recorded: the interval ends behind k_finish then
@@ -1122,8 +1130,22 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             const ScanCounters& s = host_slices_[k];
             c.lines += s.lines; c.cand_true += s.cand_true; c.hits_true += s.hits_true; c.error |= s.error;
         }
-        bool over = c.n_final > final_.n || c.n_final_ids > final_ids_.n || (compact_ && c.n_c4 > c4_.n);
-        for (int k = 0; k < ns; ++k) each_list(work_[k], host_slices_[k], [&](size_t cap, size_t need, auto&&) { over = over || need > cap; });
+        bool over = false;
+        std::string over_names;   // trace only: " <list> <demand>><capacity>" of every list that is over (slice k > 0: "<list>[k]")
+        auto test = [&](const char* name, int k, size_t cap, size_t need) {
+            if (need <= cap) return;
+            over = true;
+            if (!trace) return;
+            char b[96];
+            if (k) snprintf(b, sizeof b, " %s[%d] %zu>%zu", name, k, need, cap);
+            else snprintf(b, sizeof b, " %s %zu>%zu", name, need, cap);
+            over_names += b;
+        };
+        for (int k = 0; k < ns; ++k)
+            each_list(work_[k], host_slices_[k], [&](const char* name, size_t cap, size_t need, auto&&) { test(name, k, cap, need); });
+        test("final_", 0, final_.n, c.n_final);
+        test("final_ids_", 0, final_ids_.n, c.n_final_ids);
+        if (compact_) test("c4_", 0, c4_.n, c.n_c4);
         if (!over) {
             // candidates the glob pass could not hold (more results / deeper star nesting than a lane stores): normally none.
             // If there are, the spill pass runs now — its scratch (one bit per pattern id per thread) is allocated only here — and
@@ -1147,13 +1169,14 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             if (trace) fprintf(stderr, "[matchy_amd] %u candidates to the spill pass\n", n_spill);
             continue;
         }
-        if (trace) fprintf(stderr, "[matchy_amd] work buffers overflow (attempt %d): regrow and rescan\n", attempt);
+        if (trace) fprintf(stderr, "[matchy_amd] work buffers overflow (attempt %d): regrow and rescan:%s\n", attempt, over_names.c_str());
         if (single_) throw HipError{"lookup_one: work buffers overflow"};
-        if (attempt >= 5) throw HipError{"scan: work buffers still overflow after regrowing"};
+        if (attempt >= MAX_REGROWS) throw HipError{"scan: work buffers still overflow after regrowing"};
+        ++attempt;
         // grow and run again: the kernels count past the capacity without writing, so the counts are exact demands
         size_t recs = 0, ids = 0;
         for (int k = 0; k < ns; ++k) {
-            each_list(work_[k], host_slices_[k], [](size_t cap, size_t need, auto&& grow) { if (need > cap) grow(); });
+            each_list(work_[k], host_slices_[k], [](const char*, size_t cap, size_t need, auto&& grow) { if (need > cap) grow(); });
             recs += work_[k].hits.n; ids += work_[k].ids.n;
         }
         if (final_.n < recs || c.n_final > final_.n) final_.alloc(std::max<size_t>(recs, grown(c.n_final)));

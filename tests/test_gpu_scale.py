@@ -1,6 +1,12 @@
-"""GPU tests at scale (-m gpu): dense / pathological inputs that overflow the work lists and force the regrow-and-rescan
-path, and the BASELINE configs[1] workload at a size that exercises the > 1 GiB host path, checked against the oracle
-and through size-independent properties (idempotence, sharding invariance, additivity of the line count)."""
+"""GPU tests at scale (-m gpu): dense / pathological inputs, and the BASELINE configs[1] workload at a size that exercises the
+> 1 GiB host path, checked against the oracle and through size-independent properties (idempotence, sharding invariance,
+additivity of the line count).
+
+What the dense inputs do and do not force: test_dense_pathological_inputs goes through the extractor (no lookup: one stream, one
+slice, no hits / ids / glob_work / spill / final arrays, no mirror). Several of its inputs overflow the extraction lists of a fresh
+scanner and so run the regrow-and-rescan path, but nothing here observes that a rescan happened or for which list, and whether a
+lookup scan of this file overflows anything depends on the capacity formulas of Work::ensure. The overflow path is tested on purpose,
+list by list and entry by entry, in tests/test_gpu_overflow.py; the list writers alone in tests/test_gpu_list_writers.py."""
 import os
 from pathlib import Path
 
