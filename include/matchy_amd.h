@@ -315,6 +315,30 @@ char *matchy_scan_hit_to_json(const matchy_scanner_t *scanner, const matchy_scan
  * matchy_free_string. The scanner caches the rendered data payloads by data offset (not thread-safe per scanner, like its scans). */
 int32_t matchy_scan_result_to_ndjson(matchy_scanner_t *scanner, const matchy_scan_result_t *result, const uint8_t *text,
                                      const char *source, char **out, size_t *out_len);
+/* ---- Line context (opt-in, off by default: with it off a scan launches and allocates nothing more and returns what it always did).
+ * For every hit of a scan: the 0-based index of its line in the scanned buffer (= number of '\n' bytes in front of the hit), where
+ * that line starts, and where it ends (the position of its '\n', or the length of the buffer for an unterminated last line; a '\r'
+ * in front of the '\n' belongs to the line). Per scan: the number of distinct lines with at least one hit (WorkerStats::
+ * lines_with_matches). All of it is computed on the GPU from the batch that is resident there. */
+typedef struct matchy_scan_line_t { uint32_t line, line_start, line_end, reserved; } matchy_scan_line_t;
+/* Applies to the scanner's next scan through every entry (matchy_scanner_scan, _scan_device, _submit_device: read at submit). A result
+ * of a scan with line context owns a small block even where its arrays are borrowed: release it with matchy_scan_result_free. */
+void matchy_scanner_set_line_context(matchy_scanner_t *scanner, bool enabled);
+bool matchy_scanner_line_context(const matchy_scanner_t *scanner);
+/* lines[i] belongs to result->hits[i]; ip4_lines[i] to result->ip4_hits[i] (NULL without compact records). Same ownership and
+ * lifetime as the hit arrays of that result (borrowed / owned / device pointers for MATCHY_SCAN_FETCH_DEVICE; NULL for
+ * MATCHY_SCAN_FETCH_COUNTS, which still delivers lines_with_matches). MATCHY_ERROR_INVALID_PARAM if the result was produced with
+ * line context off. Any out pointer may be NULL. */
+int32_t matchy_scan_result_lines(const matchy_scan_result_t *result, const matchy_scan_line_t **lines,
+                                 const matchy_scan_line_t **ip4_lines, uint64_t *lines_with_matches);
+/* matchy_scan_result_to_ndjson with "line_number" (line_base + line + 1: 1-based when line_base is the number of lines in front of
+ * the scanned buffer) and, if with_input_line, "input_line" in every record: the bytes of the line, converted like
+ * String::from_utf8_lossy (one U+FFFD per maximal ill-formed subsequence). Keys stay sorted: cidr, data, input_line, line_number,
+ * match_type, ... . The result must come from a scan with line context and be host-resident. */
+int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t *scanner, const matchy_scan_result_t *result, const uint8_t *text,
+                                           const char *source, uint64_t line_base, bool with_input_line, char **out, size_t *out_len);
+/* With matchy_scanner_set_profile: milliseconds of the streaming '\n' count, the prefix sum, and resolve + distinct set of the last scan. */
+void matchy_scanner_get_line_timing(const matchy_scanner_t *scanner, float out_ms[3]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -418,6 +442,9 @@ int32_t matchy_multi_scanner_scan(matchy_multi_scanner_t *ms, const uint8_t *dat
  * `fn` (may be NULL) sees every batch in file order on the calling thread, tag = offset of the batch in the input; totals may be NULL. */
 int32_t matchy_multi_scanner_scan_file(matchy_multi_scanner_t *ms, const char *path, size_t batch_bytes, matchy_multi_ordered_fn fn,
                                        void *user, matchy_multi_totals_t *totals);
+/* Line context for the scanner of every worker (from the next batch a worker takes). Batches from _next carry values relative to
+ * their batch; matchy_multi_scanner_scan merges them into values relative to `data`, like matchy_scanner_scan. */
+void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t *ms, bool enabled);
 /* Deterministic builds for tests: fixes the build_epoch metadata value. */
 int32_t matchy_builder_set_build_epoch(matchy_builder_t *b, uint64_t epoch);
 

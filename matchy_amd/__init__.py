@@ -49,7 +49,14 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_pending", "matchy_multi_scanner_max_pending", "matchy_multi_scanner_submit_near", "matchy_multi_scanner_worker_numa",
     "matchy_amd_unbind_thread",
     "matchy_multi_scanner_scan_file", "matchy_scan_result_to_ndjson",
+    "matchy_scanner_set_line_context", "matchy_scanner_line_context", "matchy_scan_result_lines", "matchy_multi_scanner_set_line_context",
+    "matchy_scan_result_to_ndjson_lines", "matchy_scanner_get_line_timing",
 ]
+
+# bytes per tile of the '\n' count array and tiles per workgroup of its prefix sum (csrc/line_index.h): the sizes at which the line
+# kernels take another path
+LINE_TILE = 1024
+LINE_SCAN_CHUNK = 2048
 
 
 class _Result(C.Structure):
@@ -101,6 +108,11 @@ class _ScanResult(C.Structure):
                 ("data_offsets", C.POINTER(C.c_int64)), ("n_ids", C.c_size_t), ("lines", C.c_uint64),
                 ("candidates", C.c_uint64), ("bytes", C.c_uint64), ("ip4_hits", C.POINTER(C.c_uint32 * 2)),
                 ("n_ip4_hits", C.c_size_t), ("_internal", C.c_void_p)]
+
+
+class _ScanLine(C.Structure):
+    # matchy_scan_line_t (16 bytes)
+    _fields_ = [("line", C.c_uint32), ("line_start", C.c_uint32), ("line_end", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 _lib = None
@@ -209,6 +221,12 @@ def lib():
         "matchy_amd_unbind_thread": (C.c_int32, []),
         "matchy_multi_scanner_scan": (C.c_int32, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(_ScanResult)]),
         "matchy_multi_scanner_scan_file": (C.c_int32, [vp, cp, C.c_size_t, _MULTI_ORDERED_FN, vp, C.POINTER(_MultiTotals)]),
+        "matchy_scanner_set_line_context": (None, [vp, C.c_bool]),
+        "matchy_scanner_line_context": (C.c_bool, [vp]),
+        "matchy_scan_result_lines": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "matchy_multi_scanner_set_line_context": (None, [vp, C.c_bool]),
+        "matchy_scan_result_to_ndjson_lines": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, cp, C.c_uint64, C.c_bool, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_scanner_get_line_timing": (None, [vp, C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -479,6 +497,69 @@ class ScanResult:
                             ip_data_offset=h.value if h.kind == 2 else 0, ids=ids, offs=offs))
         return out
 
+    def _line_arrays(self):
+        """(lines pointer, ip4_lines pointer, lines_with_matches) of a result scanned with line context, else None"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        if lib().matchy_scan_result_lines(C.byref(self._raw), C.byref(a), C.byref(b), C.byref(n)) != 0:
+            return None
+        return a.value or 0, b.value or 0, int(n.value)
+
+    @property
+    def has_lines(self):
+        return self._line_arrays() is not None
+
+    @property
+    def lines_with_matches(self):
+        """distinct lines with at least one hit (line context); None for a result scanned without it"""
+        la = self._line_arrays()
+        return None if la is None else la[2]
+
+    @property
+    def lines_ptr(self):
+        """address of the matchy_scan_line_t array parallel to the hit records (a device address when on_device), 0 when there is none"""
+        la = self._line_arrays()
+        return 0 if la is None else la[0]
+
+    @property
+    def ip4_lines_ptr(self):
+        la = self._line_arrays()
+        return 0 if la is None else la[1]
+
+    def _line_list(self, ptr, n):
+        if self.on_device:
+            raise RuntimeError("the line records of this result are in device memory (fetch_mode 4): read them on the GPU (lines_ptr)")
+        if not ptr or not n:
+            return []
+        arr = C.cast(ptr, C.POINTER(_ScanLine))
+        return [(arr[i].line, arr[i].line_start, arr[i].line_end) for i in range(n)]
+
+    @property
+    def line_records(self):
+        """[(line, line_start, line_end)] parallel to the 16-byte hit records (hits() lists them behind the compact ones); None without
+        line context. (`lines` is taken: it is the '\\n' count of the scan.)"""
+        la = self._line_arrays()
+        return None if la is None else self._line_list(la[0], self._raw.n_hits if self._raw.hits else 0)
+
+    @property
+    def ip4_lines(self):
+        """[(line, line_start, line_end)] parallel to the compact IPv4 records"""
+        la = self._line_arrays()
+        return None if la is None else self._line_list(la[1], self._raw.n_ip4_hits if self._raw.ip4_hits else 0)
+
+    def ndjson_lines_text(self, text: bytes, source="-", line_base=0, with_input_line=False) -> bytes:
+        """ndjson_text with "line_number" (and "input_line") in every record (matchy_scan_result_to_ndjson_lines)"""
+        L = lib()
+        out, n = C.c_void_p(), C.c_size_t()
+        rc = L.matchy_scan_result_to_ndjson_lines(self._scanner._h, C.byref(self._raw), text, source.encode(), line_base, with_input_line, C.byref(out), C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scan_result_to_ndjson_lines failed ({rc}): " + last_error())
+        try:
+            return C.string_at(out.value, n.value)
+        finally:
+            L.matchy_free_string(out)
+
     def ndjson(self, text: bytes, source="-"):
         L = lib()
         if self.on_device:
@@ -562,6 +643,18 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_wait failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def set_line_context(self, on: bool):
+        """line context for the next scans: ScanResult.line_records / ip4_lines / lines_with_matches (off by default)"""
+        lib().matchy_scanner_set_line_context(self._h, bool(on))
+
+    def line_context(self) -> bool:
+        return bool(lib().matchy_scanner_line_context(self._h))
+
+    def line_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_line_timing(self._h, out)
+        return dict(count=out[0], prefix=out[1], resolve=out[2])
+
     def set_slices(self, n: int):
         """scan_device cuts large batches into slices (tail of one slice beside the streaming pass of the next): 0 = default, 1 = never, n = n equal slices."""
         lib().matchy_scanner_set_slices(self._h, n)
@@ -614,6 +707,10 @@ class MultiScanner:
             raise RuntimeError(f"matchy_multi_scanner_scan failed ({rc}): " + last_error())
         return ScanResult(_WorkerScanner(lib().matchy_multi_scanner_worker_scanner(self._h, 0)), raw)
 
+    def set_line_context(self, on: bool):
+        """line context for every worker's scanner, from the next batch on"""
+        lib().matchy_multi_scanner_set_line_context(self._h, bool(on))
+
     def submit_ptr(self, host_ptr: int, nbytes: int, tag: int = 0, numa_node: int = -1):
         """queue one newline-aligned batch that lives at a host address (e.g. a pinned torch tensor); take it back with next().
         Blocks while max_pending() batches are out: a caller that submits and gathers on one thread calls next() when
@@ -650,6 +747,10 @@ class MultiScanner:
         r = ScanResult(_WorkerScanner(lib().matchy_multi_scanner_worker_scanner(self._h, b.worker)), b.result)
         if want_hits:
             out["hits"] = r.hits()
+        if r.has_lines:   # relative to the batch
+            out["lines_with_matches"] = r.lines_with_matches
+            if want_hits:
+                out["line_records"] = r.line_records
         r.close()
         return out
 

@@ -19,6 +19,7 @@
 #include "engine.h"
 #include "host_lookup.h"
 #include "netaddr.h"
+#include "utf8_lossy.h"
 
 #include <deque>
 #include <list>
@@ -249,6 +250,27 @@ void fill_device_result(Scanner& sc, const ScanOutput& so, uint64_t bytes, match
     auto* in = new ScanResultInternal();   // marks the residency: host-side readers of the result refuse device pointers
     in->on_device = true;
     out->_internal = in;
+}
+
+static_assert(sizeof(LineRec) == sizeof(matchy_scan_line_t) && offsetof(LineRec, line_end) == offsetof(matchy_scan_line_t, line_end), "k_line_resolve writes matchy_scan_line_t records directly");
+
+// Line context of a scan_device / wait result: the result gets (or keeps) its internal block; the arrays follow the hit arrays of the
+// same result — device pointers, the scanner's pinned block, or an owned copy.
+void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, matchy_scan_result_t* out) {
+    if (!so.has_lines) return;
+    if (!out->_internal) out->_internal = new ScanResultInternal();
+    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    in->has_lines = true;
+    in->lines_with_matches = so.lines_with_matches;
+    if (device) {
+        in->lines = out->n_hits ? reinterpret_cast<const matchy_scan_line_t*>(sc.device_lines()) : nullptr;
+    } else if (owned) {
+        if (so.fin_lines) in->lines_own.assign(reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines), reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines) + so.n_fin);
+        in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
+    } else {
+        in->lines = reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines);
+        in->ip4_lines = reinterpret_cast<const matchy_scan_line_t*>(so.c4_lines);
+    }
 }
 
 }  // namespace
@@ -789,6 +811,20 @@ void matchy_scanner_free(matchy_scanner_t* s) { delete reinterpret_cast<ScannerH
 void matchy_scanner_set_profile(matchy_scanner_t* s, bool on) { if (s) reinterpret_cast<ScannerH*>(s)->sc->set_profile(on); }
 void matchy_scanner_set_slices(matchy_scanner_t* s, int32_t n) { if (s) reinterpret_cast<ScannerH*>(s)->sc->set_slices(n); }
 int32_t matchy_scanner_last_slices(const matchy_scanner_t* s) { return s ? reinterpret_cast<const ScannerH*>(s)->sc->last_slice_count() : 0; }
+void matchy_scanner_set_line_context(matchy_scanner_t* s, bool on) { if (s) reinterpret_cast<ScannerH*>(s)->sc->set_line_context(on); }
+bool matchy_scanner_line_context(const matchy_scanner_t* s) { return s && reinterpret_cast<const ScannerH*>(s)->sc->line_context(); }
+void matchy_scanner_get_line_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->line_timing(out);
+}
+int32_t matchy_scan_result_lines(const matchy_scan_result_t* r, const matchy_scan_line_t** lines, const matchy_scan_line_t** ip4_lines, uint64_t* lines_with_matches) {
+    if (!r) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_lines) { set_error("matchy_scan_result_lines: the result was produced with line context off"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (lines) *lines = in->lines;
+    if (ip4_lines) *ip4_lines = in->ip4_lines;
+    if (lines_with_matches) *lines_with_matches = in->lines_with_matches;
+    return MATCHY_SUCCESS;
+}
 void matchy_scanner_get_timing(const matchy_scanner_t* s, float out[5]) {
     if (!s || !out) return;
     const ScanTiming& t = reinterpret_cast<const ScannerH*>(s)->sc->timing();
@@ -803,8 +839,16 @@ int32_t matchy_scanner_scan(matchy_scanner_t* s, const uint8_t* data, size_t len
         std::vector<FinalHit> fin;
         std::vector<uint32_t> fids;
         std::vector<long long> foffs;
-        h->sc->scan_host(data, len, true, false, so, nullptr, &fin, &fids, &foffs);
+        std::vector<LineRec> flines;
+        h->sc->scan_host(data, len, true, false, so, nullptr, &fin, &fids, &foffs, &flines);
         fill_result(fin.data(), fin.size(), fids.data(), foffs.data(), fids.size(), so.lines, so.n_cand, len, false, true, out);
+        if (so.has_lines) {
+            auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+            in->has_lines = true;
+            in->lines_with_matches = so.lines_with_matches;
+            in->lines_own.assign(reinterpret_cast<const matchy_scan_line_t*>(flines.data()), reinterpret_cast<const matchy_scan_line_t*>(flines.data()) + flines.size());
+            in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
+        }
         return MATCHY_SUCCESS;
     } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
@@ -820,13 +864,15 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
         ScanRequest rq;
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
+        rq.lines = h->sc->line_context();
         h->sc->scan_device(rq, st);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
+        attach_lines(*h->sc, so, false, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
@@ -843,7 +889,7 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: several batches in flight (ScanRequest::fork)
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode); rq.lines = h->sc->line_context();
         h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
         return MATCHY_SUCCESS;
@@ -861,10 +907,11 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
         hipStream_t st = reinterpret_cast<hipStream_t>(h->pending_stream);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, h->pending_len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
+        attach_lines(*h->sc, so, false, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
@@ -928,8 +975,14 @@ char* matchy_scan_hit_to_json(const matchy_scanner_t* s, const matchy_scan_resul
 // fixed parts of a line are appended as literals, so a line costs a few memcpy instead of a decode of the MMDB value, a dozen
 // std::string temporaries and a strdup: the renderer was what bounded the command line with --format json (~6 GB/s of log against
 // 40+ with --format summary).
-int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, char** out, size_t* out_len) {
+// with_lines: "line_number" (and "input_line") from the result's line arrays go between "data" and "match_type" (keys stay sorted)
+static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, bool with_lines, uint64_t line_base,
+                                bool with_input_line, char** out, size_t* out_len) {
     if (!s || !r || !out || !out_len || (!text && (r->n_hits || r->n_ip4_hits))) return MATCHY_ERROR_INVALID_PARAM;
+    const matchy_scan_line_t* lines = nullptr;
+    const matchy_scan_line_t* ip4_lines = nullptr;
+    if (with_lines && matchy_scan_result_lines(r, &lines, &ip4_lines, nullptr) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
+    if (with_lines && ((r->hits && r->n_hits && !lines) || (r->ip4_hits && r->n_ip4_hits && !ip4_lines))) { set_error("matchy_scan_result_to_ndjson_lines: the result has no line records"); return MATCHY_ERROR_INVALID_PARAM; }
     if (matchy_scan_result_on_device(r)) { set_error("matchy_scan_result_to_ndjson: the records of this result are in device memory (MATCHY_SCAN_FETCH_DEVICE)"); return MATCHY_ERROR_INVALID_PARAM; }
     ScannerH* sh = reinterpret_cast<ScannerH*>(s);
     const DbImage& img = sh->sc->image();
@@ -978,11 +1031,28 @@ int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_resu
             if (plain) { o.push_back('"'); o.append(p, len); o.push_back('"'); }
             else json_escape(std::string(p, len), o);
         };
+        std::string raw_line;
+        char num64[24];
         for (size_t i = i0; i < i1; ++i) {
             const bool in_hits = r->hits && i < r->n_hits;
             const matchy_scan_hit_t h = in_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - (r->hits ? r->n_hits : 0)]);
             const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
             const char* mt = (const char*)text + h.start;
+            auto append_line_keys = [&] {
+                if (!with_lines) return;
+                const matchy_scan_line_t ln = in_hits ? lines[i] : ip4_lines[i - (r->hits ? r->n_hits : 0)];
+                if (with_input_line) {
+                    o += "\"input_line\":";
+                    raw_line.clear();
+                    utf8_lossy_append(text + ln.line_start, ln.line_end - ln.line_start, raw_line);
+                    json_escape(raw_line, o);
+                    o.push_back(',');
+                }
+                o += "\"line_number\":";
+                const int k = snprintf(num64, sizeof(num64), "%llu", (unsigned long long)(line_base + ln.line + 1));
+                o.append(num64, (size_t)k);
+                o.push_back(',');
+            };
             if (h.kind == 2) {
                 IpAddr ip;
                 o += "{\"cidr\":";
@@ -991,7 +1061,9 @@ int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_resu
                 else { std::string c(mt, hlen); c += "/"; c += std::to_string((unsigned)h.prefix_len); json_escape(c, o); }
                 o += ",\"data\":";
                 o += data_json(h.value);
-                o += ",\"match_type\":\"ip\",\"matched_text\":";
+                o.push_back(',');
+                append_line_keys();
+                o += "\"match_type\":\"ip\",\"matched_text\":";
                 append_quoted(mt, hlen);
                 o += ",\"prefix_len\":";
                 append_uint((unsigned)h.prefix_len);
@@ -1006,6 +1078,7 @@ int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_resu
                     any = true;
                 }
                 if (any) o += "],";
+                append_line_keys();
                 o += "\"match_type\":\"pattern\",\"matched_text\":";
                 append_quoted(mt, hlen);
                 o += ",\"pattern_count\":";
@@ -1068,6 +1141,14 @@ int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_resu
     buf[total] = 0;
     *out = buf; *out_len = total;
     return MATCHY_SUCCESS;
+}
+
+int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, char** out, size_t* out_len) {
+    return result_to_ndjson(s, r, text, source, false, 0, false, out, out_len);
+}
+int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, uint64_t line_base,
+                                           bool with_input_line, char** out, size_t* out_len) {
+    return result_to_ndjson(s, r, text, source, true, line_base, with_input_line, out, out_len);
 }
 
 }  // extern "C"

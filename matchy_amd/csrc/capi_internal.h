@@ -18,6 +18,13 @@ struct ScanResultInternal {
     std::vector<uint32_t> ids;
     std::vector<int64_t> offs;
     bool on_device = false;   // MATCHY_SCAN_FETCH_DEVICE: the result's arrays are device pointers
+    // line context (matchy_scan_result_lines): `lines` / `ip4_lines` point at the owned vector, at the scanner's pinned block
+    // (borrowed results) or into device memory (on_device), like the hit arrays of the same result
+    bool has_lines = false;
+    std::vector<matchy_scan_line_t> lines_own;
+    const matchy_scan_line_t* lines = nullptr;
+    const matchy_scan_line_t* ip4_lines = nullptr;
+    uint64_t lines_with_matches = 0;
 };
 
 }  // namespace capi

@@ -54,6 +54,7 @@ int usage() {
             "usage:\n"
             "  matchy build <INPUT>... -o <FILE> [-f text|csv|json] [-t TYPE] [-d DESC] [--desc-lang LANG] [-i] [-v]\n"
             "  matchy match <DATABASE> <INPUT>... [--format json|summary] [-s] [--batch-bytes N] [--extractors LIST] [--device N | --devices LIST|all] [-j N|auto] [-f]\n"
+            "               [--line-numbers] [--input-line]   (\"line_number\" / \"input_line\" in every record, computed on the GPU)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -320,6 +321,12 @@ struct MatchPipeline {
     std::atomic<bool> reader_done{false};
     bool json = true;
     std::vector<std::string> sources;
+    // --line-numbers / --input-line: the scanners run with line context. "Lines with matches" is the device's count, and the records
+    // carry "line_number" (1-based per input) — which needs the number of lines in front of the batch, known only in sequence order:
+    // such batches are rendered by the ordered printer (line_base: '\n' bytes of the input's earlier batches; batches end at newlines),
+    // not by the batch hook.
+    bool line_ctx = false, input_line = false;
+    std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
 
     // the batch goes to the library's queue; its Batch object travels as the tag and comes back with the result
     size_t submit(Batch&& b) {
@@ -357,6 +364,12 @@ struct MatchPipeline {
         d.input = input;
         Totals& t = d.t;
         t.lines += r.lines; t.candidates += r.candidates; t.bytes += len; t.matches += r.n_hits;
+        if (line_ctx) {
+            uint64_t lwm = 0;
+            if (matchy_scan_result_lines(&r, nullptr, nullptr, &lwm) == MATCHY_SUCCESS) t.lines_with_matches += lwm;
+            else { fprintf(stderr, "[ERROR] no line context in a scan result: %s\n", matchy_amd_last_error()); d.ok = false; }
+            return;   // the records: render_numbered, in sequence order
+        }
         // lines with matches: hits come sorted by offset; a new line starts when a '\n' lies between two hit starts
         const std::string& source = sources[input];
         size_t prev = (size_t)-1;
@@ -371,6 +384,14 @@ struct MatchPipeline {
             if (matchy_scan_result_to_ndjson(sc, &r, data, source.c_str(), &text, &n) == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
             else { fprintf(stderr, "[ERROR] rendering failed: %s\n", matchy_amd_last_error()); d.ok = false; }
         }
+    }
+    // the records of a batch of a scan with line context; `base` = lines of its input in front of it
+    void render_numbered(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, size_t input, unsigned long long base, Done& d) {
+        if (!json || !r.n_hits || !d.ok) return;
+        char* text = nullptr;
+        size_t n = 0;
+        if (matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[input].c_str(), base, input_line, &text, &n) == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
+        else { fprintf(stderr, "[ERROR] rendering failed: %s\n", matchy_amd_last_error()); d.ok = false; }
     }
     static void* batch_hook(void* user, size_t, matchy_scanner_t* sc, const matchy_scan_result_t* r, const uint8_t* data, size_t len, void* tag) {
         MatchPipeline* pl = (MatchPipeline*)user;
@@ -390,6 +411,10 @@ struct MatchPipeline {
             return;
         }
         render(sc, r, b.ptr, b.len, b.input, d);
+        if (line_ctx) {   // --follow: batches of an input come one after the other, the count continues across the polls
+            render_numbered(sc, r, b.ptr, b.input, line_base[b.input], d);
+            line_base[b.input] += r.lines;
+        }
         matchy_scan_result_free(&r);
     }
     // takes the batches back in sequence order and prints them, until the reader is done and nothing is pending
@@ -409,6 +434,10 @@ struct MatchPipeline {
                 fprintf(stderr, "[ERROR] scan failed: %s\n", matchy_amd_last_error());
                 input_failed[hb->input] = 1;
             } else if (d) {
+                if (line_ctx) {   // the worker's scanner renders here: with line context its hook renders nothing, so one thread at a time uses it
+                    render_numbered(matchy_multi_scanner_worker_scanner(ms, b.worker), b.result, b.data, hb->input, line_base[hb->input], *d);
+                    line_base[hb->input] += b.result.lines;
+                }
                 if (!d->ok) input_failed[hb->input] = 1;   // rendering failed in the batch hook: the batch's matches are missing, exit status says so
                 if (d->text_len) write_all_stdout(d->text, d->text_len);
                 total.lines += d->t.lines; total.lines_with_matches += d->t.lines_with_matches; total.matches += d->t.matches;
@@ -514,7 +543,7 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
                 continue;
             }
             tl.gone = false;
-            if (sb.st_size < tl.pos) tl.pos = 0;          // truncated: start over
+            if (sb.st_size < tl.pos) { tl.pos = 0; if (tl.input < pl.line_base.size()) pl.line_base[tl.input] = 0; }   // truncated: start over
             if (sb.st_size == tl.pos) continue;
             const int fd = open(tl.path.c_str(), O_RDONLY);
             if (fd < 0) continue;
@@ -566,7 +595,7 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false;
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
     int jobs = 0;   // -j N|auto (matchy.rs:98-103: worker threads): scanners here; auto = 2 (summary) / 4 (json) per device listed once
@@ -592,6 +621,8 @@ int cmd_match(int argc, char** argv) {
         else if (a == "-j") { const std::string j = next("-j"); jobs = j == "auto" ? 0 : std::max(0, atoi(j.c_str())); }
         else if (a == "-p" || a == "--progress" || a == "--debug-routing") {}
         else if (a == "-f" || a == "--follow") follow = true;
+        else if (a == "--line-numbers") line_numbers = true;
+        else if (a == "--input-line") input_line = true;
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
@@ -676,6 +707,9 @@ int cmd_match(int argc, char** argv) {
     MatchPipeline pl;
     pl.ms = ms;
     pl.json = format == "json";
+    pl.line_ctx = line_numbers || input_line;
+    pl.input_line = input_line;
+    if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
     std::vector<std::string> paths;
     bool stdin_seen = false;
@@ -690,6 +724,7 @@ int cmd_match(int argc, char** argv) {
     Totals t;
     std::vector<char> input_failed(paths.size(), 0);
     std::vector<char> read_failed(paths.size(), 0);   // written by this thread only (input_failed belongs to the printer until it is joined)
+    pl.line_base.assign(paths.size(), 0);
     std::thread printer([&] { pl.printer(t, input_failed); });
     pl.consumed.assign(paths.size(), -1);
     for (size_t i = 0; i < paths.size(); ++i)
@@ -704,7 +739,7 @@ int cmd_match(int argc, char** argv) {
     if (follow) {
         matchy_scanner_t* fsc = matchy_scanner_create(db, mask, devs[0]);
         if (!fsc) fprintf(stderr, "Error: Failed to create the GPU scanner on device %d: %s\n", devs[0], matchy_amd_last_error());
-        else { follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
+        else { matchy_scanner_set_line_context(fsc, pl.line_ctx); follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
     }
     size_t failed = 0;
     for (char f : input_failed) failed += f != 0;

@@ -501,6 +501,8 @@ Scanner::~Scanner() {
     if (mirror_c4_) (void)hipHostFree(mirror_c4_);
     if (pinned_c4_) (void)hipHostFree(pinned_c4_);
     if (host_slices_) (void)hipHostFree(host_slices_);
+    if (pinned_lines_) (void)hipHostFree(pinned_lines_);
+    for (auto& e : ev_line_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_anchor_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_misc_) if (e) (void)hipEventDestroy(e);
@@ -1231,6 +1233,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     out.fin = nullptr; out.fin_ids = nullptr; out.fin_offs = nullptr; out.n_fin = 0; out.n_fin_ids = 0;
     out.c4 = nullptr; out.n_c4 = 0;
     const bool had_mirror = mirror_used_;
+    const FinalHit* dev_recs = final_.p;   // the records the caller gets, in its order, in device memory (line context)
     Work& w0 = work_[0];   // raw hits and candidate lists are read by one-slice scans only (single queries, extraction)
     const bool get_raw = last_.lookup && hit_mode == HITS_RAW && c.n_hits;
     const bool get_fin = last_.lookup && hit_mode == HITS_FINAL && c.n_final;
@@ -1268,6 +1271,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             if (sort_tmp_.n < tb) sort_tmp_.alloc(tb + tb / 4 + 4096);
             MXY_HIP(sort_hits(final_.p, n, sort_keys_.p, sort_vals_.p, sort_tmp_.p, tb, final_sorted_.p, stream));
             src = final_sorted_.p;
+            dev_recs = src;
         }
         MXY_HIP(hipMemcpyAsync(base, src, hb, hipMemcpyDeviceToHost, stream));
         if (c.n_final_ids) {
@@ -1297,7 +1301,13 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         if (c.n_cand_a) MXY_HIP(hipMemcpyAsync(out.cands.data(), w0.cands_a.p, (size_t)c.n_cand_a * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
         if (c.n_cand) MXY_HIP(hipMemcpyAsync(out.cands.data() + c.n_cand_a, w0.cands.p, (size_t)c.n_cand * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     }
+    out.has_lines = false; out.fin_lines = nullptr; out.c4_lines = nullptr; out.lines_with_matches = 0;
+    if (last_.lines && last_.lookup && !single_) resolve_lines(out, dev_recs, hit_mode == HITS_FINAL, stream);
     wait_stream(stream, last_.fork);
+    if (out.has_lines) {
+        out.lines_with_matches = *reinterpret_cast<const uint32_t*>(pinned_lines_);
+        if (profile_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&line_ms_[k], ev_line_[k], ev_line_[k + 1]));
+    }
     if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
     // drop the padding slots of partially filled chunks
     if (get_raw) {
@@ -1312,6 +1322,62 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     }
     for (auto& t : out.by_type) t = 0;
     if (want_cands) for (const Candidate& cd : out.cands) { uint32_t ty = cd.len_type >> 24; if (ty < IT_COUNT) out.by_type[ty]++; }
+}
+
+// Line context of the last scan (line_index.hip): runs once per fetch, behind the regrow loop — a rescan never counts the batch twice —
+// and behind the sort, over the records in the order the caller gets them. Every array is written again for exactly the records of
+// this scan. to_host: the line records come back into pinned memory like the hit records; otherwise they stay on the device and only
+// the distinct-line count crosses the bus.
+void Scanner::resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream) {
+    const ScanCounters& c = host_counters_;
+    const uint32_t n_fin = c.n_final, n_c4 = compact_ ? c.n_c4 : 0u;
+    const size_t n = (size_t)n_fin + n_c4;
+    const uint32_t tiles = line_tiles(last_.len), chunks = line_chunks(tiles);
+    if (line_counts_.n < tiles || !line_prefix_.p) { line_counts_.alloc(grown(tiles)); line_prefix_.alloc(line_counts_.n + 1); }
+    if (line_chunks_.n < chunks) line_chunks_.alloc((size_t)chunks + 64);
+    if (!line_ctr_.p) line_ctr_.alloc(1);
+    if (line_recs_.n < n_fin) line_recs_.alloc(grown(n_fin));
+    if (line_c4_.n < n_c4) line_c4_.alloc(grown(n_c4));
+    size_t slots = 1024;
+    while (slots < 2 * n) slots <<= 1;
+    if (line_set_.n < slots) line_set_.alloc(slots);
+    const size_t head = sizeof(LineCounters), want = head + (to_host ? n * sizeof(LineRec) : 0);
+    if (pinned_lines_bytes_ < want) {
+        if (pinned_lines_) (void)hipHostFree(pinned_lines_);
+        pinned_lines_ = nullptr;
+        pinned_lines_bytes_ = want + want / 4 + (1 << 16);
+        MXY_HIP(hipHostMalloc(&pinned_lines_, pinned_lines_bytes_, hipHostMallocDefault));
+    }
+    if (profile_) {
+        for (auto& e : ev_line_) if (!e) MXY_HIP(hipEventCreate(&e));
+        MXY_HIP(hipEventRecord(ev_line_[0], stream));
+    }
+    MXY_HIP(hipMemsetAsync(line_ctr_.p, 0, sizeof(LineCounters), stream));
+    if (n) MXY_HIP(hipMemsetAsync(line_set_.p, 0xFF, slots * 4, stream));
+    MXY_HIP(line_index_build(last_.ptr, last_.len, line_counts_.p, line_chunks_.p, line_prefix_.p, n_cu_, stream, profile_ ? ev_line_[1] : nullptr));
+    if (profile_) { if (!tiles) MXY_HIP(hipEventRecord(ev_line_[1], stream)); MXY_HIP(hipEventRecord(ev_line_[2], stream)); }
+    MXY_HIP(line_index_resolve(last_.ptr, last_.len, line_prefix_.p, recs, sizeof(FinalHit), n_fin, line_recs_.p, line_set_.p, (uint32_t)slots, &line_ctr_.p->distinct, stream));
+    MXY_HIP(line_index_resolve(last_.ptr, last_.len, line_prefix_.p, c4_.p, sizeof(uint2), n_c4, line_c4_.p, line_set_.p, (uint32_t)slots, &line_ctr_.p->distinct, stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_line_[3], stream));
+    uint8_t* pb = (uint8_t*)pinned_lines_;
+    MXY_HIP(hipMemcpyAsync(pb, line_ctr_.p, sizeof(LineCounters), hipMemcpyDeviceToHost, stream));
+    if (to_host) {
+        if (n_fin) MXY_HIP(hipMemcpyAsync(pb + head, line_recs_.p, (size_t)n_fin * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
+        if (n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)n_fin * sizeof(LineRec), line_c4_.p, (size_t)n_c4 * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
+        out.fin_lines = n_fin ? (const LineRec*)(pb + head) : nullptr;
+        out.c4_lines = n_c4 ? (const LineRec*)(pb + head) + n_fin : nullptr;
+    }
+    out.has_lines = true;
+}
+
+size_t host_piece_bytes() {
+    static const size_t v = [] {
+        const unsigned long long maxc = 1ull << 30;
+        const char* e = getenv("MATCHY_AMD_HOST_PIECE_BYTES");
+        if (!e || !*e) return (size_t)maxc;
+        return (size_t)std::min(std::max(strtoull(e, nullptr, 10), 1ull), maxc);
+    }();
+    return v;
 }
 
 // Spill pass of the glob lookup (k_lookup_spill): list of candidate indices per slice; the per-thread scratch (one bit per
@@ -1357,9 +1423,9 @@ void Scanner::lookup_one(const std::string& text, Candidate c, ScanOutput& out) 
 }
 
 void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_cands, ScanOutput& out, std::vector<uint64_t>* cand_bases,
-                        std::vector<FinalHit>* fin, std::vector<uint32_t>* fin_ids, std::vector<long long>* fin_offs) {
+                        std::vector<FinalHit>* fin, std::vector<uint32_t>* fin_ids, std::vector<long long>* fin_offs, std::vector<LineRec>* fin_lines) {
     // Cut into < 2^30-byte pieces at newlines (N4 in SURVEY §8a: no candidate class admits '\n').
-    const size_t MAXC = (size_t)1 << 30;
+    const size_t MAXC = host_piece_bytes();
     // the calling thread may be another one than last time (its current device is thread state): allocations below must land
     // on this scanner's device
     MXY_HIP(hipSetDevice(ddb_->device));
@@ -1371,9 +1437,10 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     std::vector<Candidate> all_cands;
     if (cand_bases) cand_bases->clear();
     if (fin) { fin->clear(); fin_ids->clear(); fin_offs->clear(); }
+    if (fin_lines) fin_lines->clear();
     do {
         const size_t n = newline_cut(data, pos, len, MAXC) - pos;
-        if (n > MAXC) throw HipError{"scan_host: a single line exceeds 1 GiB"};
+        if (n > ((size_t)1 << 30)) throw HipError{"scan_host: a single line exceeds 1 GiB"};
         if (staging_.n < n + 16) staging_.alloc(n + 16 + n / 8);
         // Pageable host memory (a mapped file, a heap buffer) reaches the device through the runtime's own pinned staging at
         // ~20 GB/s; pinned for the duration of the copy (hipHostRegister: ~5 ms per GB, tools/ubench/h2d_rate2.cpp) the DMA
@@ -1405,7 +1472,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             if (tail) MXY_HIP(hipMemcpyAsync(staging_.p + head + reg_len, reg_lo + reg_len, tail, hipMemcpyHostToDevice, host_stream_));
         } else if (n) MXY_HIP(hipMemcpyAsync(staging_.p, src, n, hipMemcpyHostToDevice, host_stream_));
         ScanRequest rq;
-        rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup;
+        rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = line_ctx_ && lookup;
         scan_device(rq, host_stream_);
         ScanOutput part;
         const double t_launch = ms_since(th0);
@@ -1414,6 +1481,11 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             static const auto t_proc = std::chrono::steady_clock::now();
             fprintf(stderr, "[matchy_amd] t=%.1f ms scan_host piece %zu B: registered %zu B in %.3f ms, launches done after %.3f ms, results after %.3f ms\n",
                     ms_since(t_proc), n, reg_len, t_reg, t_launch, ms_since(th0));
+        }
+        // a line never spans a cut: the pieces' distinct lines add up, and a piece's line numbers continue the count of the earlier pieces
+        if (part.has_lines) {
+            out.has_lines = true; out.lines_with_matches += part.lines_with_matches;
+            if (fin_lines && part.n_fin) append_shifted_lines(part.fin_lines, part.n_fin, (uint32_t)pos, (uint32_t)out.lines, *fin_lines);
         }
         out.lines += part.lines; out.n_cand += part.n_cand; out.n_hits += part.n_hits;
         for (int t = 0; t < IT_COUNT; ++t) out.by_type[t] += part.by_type[t];

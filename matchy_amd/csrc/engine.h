@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "db_image.h"
+#include "line_index.h"
 #include "scan_types.h"
 
 namespace mxy {
@@ -110,6 +111,12 @@ struct ScanOutput {
     uint64_t lines = 0;
     uint32_t n_cand = 0, n_hits = 0;
     uint64_t by_type[IT_COUNT] = {0};
+    // line context (ScanRequest::lines): one record per entry of fin / c4, BORROWED like them (HITS_FINAL; otherwise the arrays stay
+    // on the device: Scanner::device_lines), and the number of distinct lines that carry a hit
+    bool has_lines = false;
+    const LineRec* fin_lines = nullptr;
+    const LineRec* c4_lines = nullptr;
+    uint64_t lines_with_matches = 0;
 };
 
 // Process-wide registry of the host ranges this library pinned (hipHostRegister): the caller's (matchy_amd_host_register, kept until
@@ -157,7 +164,22 @@ struct ScanRequest {
     bool fork = false;
     int slices = 0;            // with fork: cut the batch into that many slices (see Scanner::MAX_SLICES); 0 = the default (one slice)
     bool compact = false;      // IPv4 results leave as 8-byte records (ScanOutput::c4, scan_types.h c4_pack) when compact_possible()
+    bool lines = false;        // line context: fetch() resolves every final record to its line (line_index.hip); needs `lookup`
 };
+
+// Moves the line records of a piece that starts `base` bytes and `line_base` lines into the whole (append_shifted for the line array).
+template <class Line>
+void append_shifted_lines(const Line* lines, size_t n, uint32_t base, uint32_t line_base, std::vector<Line>& all) {
+    for (size_t i = 0; i < n; ++i) {
+        Line l = lines[i];
+        l.line += line_base; l.line_start += base; l.line_end += base;
+        all.push_back(l);
+    }
+}
+
+// Bytes of a piece of Scanner::scan_host: below 1 GiB, or what MATCHY_AMD_HOST_PIECE_BYTES says (read once, clamped to that maximum; tests
+// of the piece arithmetic).
+size_t host_piece_bytes();
 
 // A scan session: owns the per-launch work buffers on one device. Not thread-safe; create one per thread/stream.
 class Scanner {
@@ -177,11 +199,19 @@ public:
     const uint32_t* device_final_ids() const { return final_ids_.p; }
     const long long* device_final_offs() const { return final_offs_.p; }
     size_t device_final_id_count() const { return host_counters_.n_final_ids; }
+    // line context: scans launched through scan_host resolve lines when set (scan_device callers pass ScanRequest::lines)
+    void set_line_context(bool on) { line_ctx_ = on; }
+    bool line_context() const { return line_ctx_; }
+    // the line records of the last scan with line context as the kernel left them in device memory, parallel to device_final() / the compact array
+    const LineRec* device_lines() const { return line_recs_.p; }
+    const LineRec* device_c4_lines() const { return line_c4_.p; }
+    // with set_profile: milliseconds of the streaming count kernel, of the prefix sum, and of resolve + distinct set of the last fetch
+    void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = line_ms_[k]; }
     void lookup_one(const std::string& text, Candidate c, ScanOutput& out);
     // Convenience: host buffer -> internal device buffer -> scan -> fetch (chunks of < 2^31 bytes).
     // `fin*` vectors receive owned copies of the final hits of all pieces, positions made absolute.
     void scan_host(const uint8_t* data, size_t len, bool lookup, bool want_cands, ScanOutput& out, std::vector<uint64_t>* cand_bases,
-                   std::vector<FinalHit>* fin, std::vector<uint32_t>* fin_ids, std::vector<long long>* fin_offs);
+                   std::vector<FinalHit>* fin, std::vector<uint32_t>* fin_ids, std::vector<long long>* fin_offs, std::vector<LineRec>* fin_lines = nullptr);
     void set_profile(bool on) { profile_ = on; }
     // slices of the forked scan_device: 0 = default for the batch size (one slice), 1 = never cut, n = n equal slices
     void set_slices(int n) { slices_ = n < 0 ? 0 : n; }
@@ -278,6 +308,18 @@ private:
     DevBuf<uint8_t> sort_tmp_;
     DevBuf<FinalHit> final_sorted_;
     DevBuf<ScanCounters> counters_;            // MAX_SLICES entries
+    // line context (line_index.hip), grown on demand and reused between scans like the sort buffers: '\n' counts per tile, sums per
+    // chunk of tiles, exclusive prefix; one line record per final / compact record; the distinct-line set and its counter; the pinned
+    // block the line records (and the counter, in front of them) come back in
+    bool line_ctx_ = false;
+    DevBuf<uint32_t> line_counts_, line_chunks_, line_prefix_, line_set_;
+    DevBuf<LineRec> line_recs_, line_c4_;
+    DevBuf<LineCounters> line_ctr_;
+    void* pinned_lines_ = nullptr;
+    size_t pinned_lines_bytes_ = 0;
+    hipEvent_t ev_line_[4] = {nullptr, nullptr, nullptr, nullptr};
+    float line_ms_[3] = {0, 0, 0};
+    void resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
     DevBuf<uint32_t> spill_scratch_;           // per-thread scratch of k_lookup_spill (allocated when a scan first spills)
     DevBuf<uint8_t> staging_;  // scan_host only
     // pinned mirror of the final records written by the lookup kernels themselves: FinalHit[mirror_cap_] | u32 ids[mirror_ids_cap_] | i64 offs[..]

@@ -46,6 +46,7 @@ struct MultiScanner {
     // taken. Without it a slow consumer of next() (a blocked stdout) lets the reader buffer the whole input and every result.
     size_t max_inflight = 4;
     bool closing = false;
+    bool line_ctx = false;   // matchy_multi_scanner_set_line_context: every worker sets its scanner to it before a scan
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
     std::string first_error;   // of a worker (scanner creation, scan): reported through matchy_amd_last_error by next()
@@ -64,6 +65,7 @@ struct MultiScanner {
         }
         for (;;) {
             MultiJob j;
+            bool want_lines = false;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return closing || !q.empty(); });
@@ -75,6 +77,7 @@ struct MultiScanner {
                 j = *it;
                 q.erase(it);
                 cv_space.notify_one();
+                want_lines = line_ctx;
             }
             MultiDone d;
             d.data = j.data; d.len = j.len; d.tag = j.tag; d.worker = w;
@@ -82,6 +85,7 @@ struct MultiScanner {
             std::string err;
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
             else if (j.len) {
+                matchy_scanner_set_line_context(scanners[w], want_lines);
                 d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
@@ -148,6 +152,12 @@ size_t matchy_multi_scanner_workers(const matchy_multi_scanner_t* h) { return h 
 matchy_scanner_t* matchy_multi_scanner_worker_scanner(const matchy_multi_scanner_t* h, size_t worker) {
     const MultiScanner* ms = reinterpret_cast<const MultiScanner*>(h);
     return ms && worker < ms->scanners.size() ? ms->scanners[worker] : nullptr;
+}
+void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t* h, bool enabled) {
+    if (!h) return;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    ms->line_ctx = enabled;
 }
 void matchy_multi_scanner_set_batch_hook(matchy_multi_scanner_t* h, matchy_multi_batch_fn fn, void* user) {
     if (!h) return;
@@ -224,6 +234,12 @@ int32_t matchy_multi_scanner_scan(matchy_multi_scanner_t* h, const uint8_t* data
             else {
                 append_shifted(b.result.hits, b.result.n_hits, b.result.pattern_ids, b.result.data_offsets, b.result.n_ids, (uint32_t)(b.data - data),
                                in->hits, in->ids, in->offs);
+                // batches come back in submission order and end at line ends: a batch's lines continue the count of the earlier ones
+                const ScanResultInternal* bi = reinterpret_cast<const ScanResultInternal*>(b.result._internal);
+                if (bi && bi->has_lines) {
+                    in->has_lines = true; in->lines_with_matches += bi->lines_with_matches;
+                    if (bi->lines) append_shifted_lines(bi->lines, b.result.n_hits, (uint32_t)(b.data - data), (uint32_t)lines, in->lines_own);
+                }
                 lines += b.result.lines; cands += b.result.candidates;
             }
             matchy_scan_result_free(&b.result);
@@ -244,6 +260,8 @@ int32_t matchy_multi_scanner_scan(matchy_multi_scanner_t* h, const uint8_t* data
     out->lines = lines; out->candidates = cands; out->bytes = len;
     out->n_hits = in->hits.size(); out->n_ids = in->ids.size();
     out->hits = in->hits.data(); out->pattern_ids = in->ids.data(); out->data_offsets = in->offs.data();
+    if (in->has_lines) in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
+    else if (len == 0) { std::lock_guard<std::mutex> lk(ms->mu); in->has_lines = ms->line_ctx; }   // no batch: the answer is still "0 lines"
     out->_internal = in.release();
     return MATCHY_SUCCESS;
 }
