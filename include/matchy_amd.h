@@ -357,6 +357,17 @@ char *matchy_amd_query_json(const matchy_t *db, const char *query, int32_t *foun
 /* matchy_extractor_create with ExtractorBuilder::min_domain_labels (matchy-extractor/src/lib.rs:101-104;
  * `matchy extract --min-labels`); 0 = the default of 2. */
 matchy_extractor_t *matchy_amd_extractor_create(uint32_t flags, uint32_t min_domain_labels);
+/* Distinct candidates (`matchy extract --unique`). While enabled, matchy_extractor_extract_chunk returns only the candidates that are
+ * the first occurrence of their text — the raw bytes data[start, end), case-sensitive, whatever the item type; for IP addresses the
+ * text in the log, not the canonical value — since the handle was created or reset; order and fields are as without it. The set of
+ * texts lives in device memory, owned by the handle, across calls; among the occurrences of a text in one call the one with the
+ * least (start, extractor order) stays. Disabled (the default) nothing is allocated, launched or copied for it; switching it off
+ * keeps the set, _reset_unique empties it (and keeps its allocations), matchy_extractor_free releases it. _unique_count: distinct
+ * texts seen since creation or reset. Like extract_chunk these serialise on the handle. */
+void matchy_amd_extractor_set_unique(matchy_extractor_t *extractor, bool enabled);
+bool matchy_amd_extractor_unique(const matchy_extractor_t *extractor);
+void matchy_amd_extractor_reset_unique(matchy_extractor_t *extractor);
+uint64_t matchy_amd_extractor_unique_count(const matchy_extractor_t *extractor);
 const char *matchy_amd_last_error(void);
 /* Diagnostics: states of the flattened Aho-Corasick automaton on the handle's default device; 0 = the database has no glob
  * section or its automaton is walked node by node (flattened table above MATCHY_AMD_DFA_MAX_MB, default 8192), -1 = error. */

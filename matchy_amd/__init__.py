@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_scan_file", "matchy_scan_result_to_ndjson",
     "matchy_scanner_set_line_context", "matchy_scanner_line_context", "matchy_scan_result_lines", "matchy_multi_scanner_set_line_context",
     "matchy_scan_result_to_ndjson_lines", "matchy_scanner_get_line_timing",
+    "matchy_amd_extractor_set_unique", "matchy_amd_extractor_unique", "matchy_amd_extractor_reset_unique", "matchy_amd_extractor_unique_count",
 ]
 
 # bytes per tile of the '\n' count array and tiles per workgroup of its prefix sum (csrc/line_index.h): the sizes at which the line
@@ -173,6 +174,10 @@ def lib():
         "matchy_extractor_extract_chunk": (C.c_int32, [vp, cp, C.c_size_t, C.POINTER(_Matches)]),
         "matchy_matches_free": (None, [C.POINTER(_Matches)]),
         "matchy_extractor_free": (None, [vp]),
+        "matchy_amd_extractor_set_unique": (None, [vp, C.c_bool]),
+        "matchy_amd_extractor_unique": (C.c_bool, [vp]),
+        "matchy_amd_extractor_reset_unique": (None, [vp]),
+        "matchy_amd_extractor_unique_count": (C.c_uint64, [vp]),
         "matchy_item_type_name": (cp, [C.c_uint8]),
         "matchy_scanner_create": (vp, [vp, C.c_uint32, C.c_int32]),
         "matchy_scanner_free": (None, [vp]),
@@ -425,14 +430,33 @@ class Database:
 
 
 class Extractor:
-    """Extractor::extract_from_chunk on the GPU (matchy_extractor_*). Returns (type_name, start, end, value)."""
+    """Extractor::extract_from_chunk on the GPU (matchy_extractor_*). Returns (type_name, start, end, value).
 
-    def __init__(self, flags=EXTRACT_ALL, min_domain_labels=2):
+    unique: only the first occurrence of every candidate text (the raw bytes data[start:end]) since creation or reset_unique() is
+    returned; the set of texts lives on the GPU, across calls (matchy_amd_extractor_set_unique)."""
+
+    def __init__(self, flags=EXTRACT_ALL, min_domain_labels=2, unique=False):
         # min_domain_labels: ExtractorBuilder::min_domain_labels (matchy-extractor/src/lib.rs:101-104), through the additive entry
         self._h = (lib().matchy_extractor_create(flags) if min_domain_labels == 2
                    else lib().matchy_amd_extractor_create(flags, min_domain_labels))
         if not self._h:
             raise RuntimeError("matchy_extractor_create failed: " + last_error())
+        if unique:
+            self.set_unique(True)
+
+    def set_unique(self, on=True):
+        lib().matchy_amd_extractor_set_unique(self._h, bool(on))
+
+    @property
+    def unique(self):
+        return bool(lib().matchy_amd_extractor_unique(self._h))
+
+    def reset_unique(self):
+        lib().matchy_amd_extractor_reset_unique(self._h)
+
+    @property
+    def unique_count(self):
+        return int(lib().matchy_amd_extractor_unique_count(self._h))
 
     def extract_from_chunk(self, data: bytes):
         L = lib()

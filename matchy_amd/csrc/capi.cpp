@@ -738,6 +738,31 @@ matchy_extractor_t* matchy_amd_extractor_create(uint32_t flags, uint32_t min_dom
     catch (const std::exception& e) { set_error(e.what()); return nullptr; }
 }
 void matchy_extractor_free(matchy_extractor_t* e) { delete reinterpret_cast<ExtractorH*>(e); }
+// distinct candidate texts (Scanner::set_unique, distinct.hip): the set is the handle's, under the handle's lock
+void matchy_amd_extractor_set_unique(matchy_extractor_t* ec, bool enabled) {
+    if (!ec) return;
+    ExtractorH* e = reinterpret_cast<ExtractorH*>(ec);
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->scanner->set_unique(enabled);
+}
+bool matchy_amd_extractor_unique(const matchy_extractor_t* ec) {
+    if (!ec) return false;
+    ExtractorH* e = const_cast<ExtractorH*>(reinterpret_cast<const ExtractorH*>(ec));
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->scanner->unique();
+}
+void matchy_amd_extractor_reset_unique(matchy_extractor_t* ec) {
+    if (!ec) return;
+    ExtractorH* e = reinterpret_cast<ExtractorH*>(ec);
+    std::lock_guard<std::mutex> lk(e->mu);
+    try { e->scanner->reset_unique(); } catch (const HipError& ex) { set_error(ex.what); }
+}
+uint64_t matchy_amd_extractor_unique_count(const matchy_extractor_t* ec) {
+    if (!ec) return 0;
+    ExtractorH* e = const_cast<ExtractorH*>(reinterpret_cast<const ExtractorH*>(ec));
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->scanner->unique_count();
+}
 const char* matchy_item_type_name(uint8_t t) { return item_type_name(t); }
 
 int32_t matchy_extractor_extract_chunk(const matchy_extractor_t* ec, const uint8_t* data, uintptr_t len, matchy_matches_t* out) {

@@ -844,8 +844,7 @@ inline int line_rank(uint8_t t) {
         default: return 4;   // the hash types
     }
 }
-bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, bool show_cand, std::vector<std::string>* seen_sorted,
-                   std::vector<std::string>& seen_new, ExtractStats& st) {
+bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, bool show_cand, ExtractStats& st) {
     if (!len) return true;
     // line table: [start, end) of every trimmed, non-empty line
     std::vector<std::pair<size_t, size_t>> lines;
@@ -885,16 +884,6 @@ bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, b
         if (show_cand) {
             const size_t ls = it.line < lines.size() ? lines[it.line].first : 0;
             fprintf(stderr, "[CANDIDATE] %s at %zu-%zu: %s\n", tname.c_str(), (size_t)mt.start - ls, (size_t)mt.end - ls, text.c_str());
-        }
-        if (seen_sorted) {
-            if (std::binary_search(seen_sorted->begin(), seen_sorted->end(), text)) continue;
-            if (std::find(seen_new.begin(), seen_new.end(), text) != seen_new.end()) continue;
-            seen_new.push_back(text);
-            if (seen_new.size() >= 4096) {   // fold the recent ones into the sorted set
-                seen_sorted->insert(seen_sorted->end(), seen_new.begin(), seen_new.end());
-                std::sort(seen_sorted->begin(), seen_sorted->end());
-                seen_new.clear();
-            }
         }
         for (char& ch : tname) ch = (char)tolower((unsigned char)ch);
         out.clear();
@@ -989,14 +978,15 @@ int cmd_extract(int argc, char** argv) {
     }
     const auto t0 = std::chrono::steady_clock::now();
     ExtractStats st;
-    std::vector<std::string> seen_sorted, seen_new;
+    // --unique (extract_cmd.rs:133, 241-246: a set of every text printed): the handle keeps the set on the GPU and returns first occurrences only
+    if (unique) matchy_amd_extractor_set_unique(ex, true);
     if (fmt == 1) fputs("type,value\n", stdout);
     bool ok = true;
     for (const std::string& path : inputs) {
         int fd = path == "-" ? 0 : open(path.c_str(), O_RDONLY);
         if (fd < 0) { fprintf(stderr, "Error: Failed to open file: %s\n", path.c_str()); ok = false; break; }
         const StreamEnd e = read_batches([&](void* p, size_t n) { return read(fd, p, n); }, batch_bytes, [&](Bytes&& data, size_t len, uint64_t) {
-            return extract_batch(ex, data.get(), len, fmt, show_cand, unique ? &seen_sorted : nullptr, seen_new, st);
+            return extract_batch(ex, data.get(), len, fmt, show_cand, st);
         });
         if (e == StreamEnd::FAILED) fprintf(stderr, "Error: read failed on %s: %s\n", path.c_str(), strerror(errno));
         ok = e == StreamEnd::DONE;

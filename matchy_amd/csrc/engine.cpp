@@ -1,5 +1,6 @@
 #include "engine.h"
 #include "batch_reader.h"
+#include "distinct.h"
 #include "unicode_lower.h"
 
 #include <dlfcn.h>
@@ -517,6 +518,21 @@ Scanner::~Scanner() {
     if (dom_stream_) (void)hipStreamDestroy(dom_stream_);
     if (host_stream_) (void)hipStreamDestroy(host_stream_);
 }
+
+void Scanner::set_unique(bool on) {
+    if (on && !distinct_) {
+        distinct_ = std::make_unique<DistinctSet>();
+        // MATCHY_AMD_TRACE: fetch prints the device time of the dedup kernels beside the extraction kernels' of the same batch
+        if (getenv("MATCHY_AMD_TRACE")) { distinct_->set_profile(true); profile_ = true; }
+    }
+    unique_ = on;
+}
+void Scanner::reset_unique() {
+    if (!distinct_) return;
+    MXY_HIP(hipSetDevice(ddb_->device));
+    distinct_->reset();
+}
+uint64_t Scanner::unique_count() const { return distinct_ ? distinct_->count() : 0; }
 
 // work lists of one slice for `len` bytes of log
 void Scanner::Work::ensure(uint32_t len) {
@@ -1296,13 +1312,20 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         }
         out.n_c4 = c.n_c4;
     }
-    if (want_cands && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
+    const bool dedup = want_cands && unique_;
+    if (want_cands && !dedup && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
         out.cands.resize((size_t)c.n_cand_a + c.n_cand);
         if (c.n_cand_a) MXY_HIP(hipMemcpyAsync(out.cands.data(), w0.cands_a.p, (size_t)c.n_cand_a * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
         if (c.n_cand) MXY_HIP(hipMemcpyAsync(out.cands.data() + c.n_cand_a, w0.cands.p, (size_t)c.n_cand * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     }
     out.has_lines = false; out.fin_lines = nullptr; out.c4_lines = nullptr; out.lines_with_matches = 0;
     if (last_.lines && last_.lookup && !single_) resolve_lines(out, dev_recs, hit_mode == HITS_FINAL, stream);
+    // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
+    if (dedup) {
+        distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);
+        if (trace) fprintf(stderr, "[matchy_amd] distinct: %zu of %u candidates are new, dedup %.3f ms behind %.3f ms of extraction kernels\n", out.cands.size(), c.cand_true,
+                           distinct_->last_ms(), timing_.total_ms);
+    }
     wait_stream(stream, last_.fork);
     if (out.has_lines) {
         out.lines_with_matches = *reinterpret_cast<const uint32_t*>(pinned_lines_);

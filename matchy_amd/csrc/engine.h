@@ -30,6 +30,8 @@ uint32_t spill_threads();
 void launch_ip_l24(const uint2* nodes, uint32_t node_count, uint32_t v4_start, uint2* l24, uint32_t* bm24, uint32_t* n_undecided, hipStream_t s);
 void launch_ip_leaf(const uint2* nodes, uint32_t node_count, uint2* l24, uint32_t* next, uint32_t n_leaf, uint32_t* leaf_node, uint2* leaf, hipStream_t s);
 
+class DistinctSet;   // distinct.h
+
 struct HipError { std::string what; };
 #define MXY_HIP(expr)                                                                                   \
     do {                                                                                                \
@@ -207,6 +209,13 @@ public:
     const LineRec* device_c4_lines() const { return line_c4_.p; }
     // with set_profile: milliseconds of the streaming count kernel, of the prefix sum, and of resolve + distinct set of the last fetch
     void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = line_ms_[k]; }
+    // Distinct candidate texts (distinct.hip), for extractor handles: while on, a fetch with want_cands returns only the candidates whose
+    // text this scanner has not returned since it was created or reset — the set lives in device memory across scans and pieces, and only
+    // the survivors are copied back. Off (the default), nothing of it is allocated, launched or copied.
+    void set_unique(bool on);
+    bool unique() const { return unique_; }
+    void reset_unique();
+    uint64_t unique_count() const;
     void lookup_one(const std::string& text, Candidate c, ScanOutput& out);
     // Convenience: host buffer -> internal device buffer -> scan -> fetch (chunks of < 2^31 bytes).
     // `fin*` vectors receive owned copies of the final hits of all pieces, positions made absolute.
@@ -320,6 +329,8 @@ private:
     hipEvent_t ev_line_[4] = {nullptr, nullptr, nullptr, nullptr};
     float line_ms_[3] = {0, 0, 0};
     void resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
+    bool unique_ = false;
+    std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
     DevBuf<uint32_t> spill_scratch_;           // per-thread scratch of k_lookup_spill (allocated when a scan first spills)
     DevBuf<uint8_t> staging_;  // scan_host only
     // pinned mirror of the final records written by the lookup kernels themselves: FinalHit[mirror_cap_] | u32 ids[mirror_ids_cap_] | i64 offs[..]
