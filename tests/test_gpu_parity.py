@@ -3,9 +3,12 @@ same inputs. Integer/byte work: every comparison is exact."""
 import json
 import os
 import random
+import sys
 from pathlib import Path
 
 import pytest
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 pytestmark = pytest.mark.gpu
 
@@ -1474,6 +1477,180 @@ def test_monero_hits_through_scans_and_a_hash_dense_batch(M, oracle):
     assert res.hits() == want
     res.close()
     _device_entries(sc, dense, want, None, (st.lines, st.candidates), slices=(3,))
+    sc.close(); db.close()
+
+
+def test_btc_eth_accept_branches_against_constructed_vectors(M, gpu_extractor, oracle):
+    """The accept branches of val_btc_base58, val_btc_bech32 and val_eth (lib.rs:1269-1361, 1799-1892) with vectors CONSTRUCTED from
+    the rule (tests/golden/make_btc_eth_kat.py), through matchy_extractor_extract_chunk: GPU == oracle == the construction.
+
+    Base58Check at every length 26..62 with both first characters, runs of leading '1' up to 56, all-zero payloads with 54 / 55 / 56
+    hashed bytes (one SHA-256 block / two) and numbers of 9..12 limbs; Bech32 and Bech32m at every length; EIP-55 with every (hex
+    position, polarity) pair. Every accept in six wrappers — one puts " 0OIl" behind the token, the four symbols the Base58 prefilter
+    of k_validate<4> looks for, beyond its length mask — and glued to a token character; constructed rejects and one-symbol mutants
+    (tests/address_cases.py decides each by decoding) as one token per line, one buffer per class; a pick of eight across the row,
+    block and segment edges of the streaming pass and as the unterminated last token; every byte value directly in front of and
+    behind three tokens — the 62-character Base58Check one, the 45-character Bech32m one (no plain Bech32 token gets this sweep) and
+    the first EIP-55 address — against the oracle alone (Bitcoin wants word boundaries, Ethereum `is_boundary_fast` bytes or the
+    buffer's end): there the test only adds that each type was seen both accepted and rejected.
+
+    Not pinned (as in the generator's docstring): what `bech32::decode` of crate 0.11 does with the padding bits of the data when it
+    regroups them into bytes; oracle and kernel look at the checksum only, and the crate's source is not available to this project."""
+    import address_cases as A
+
+    def both(buf, what):
+        got = norm(gpu_extractor.extract_from_chunk(buf))
+        assert got == norm(oracle.extract(buf)), what
+        return got
+
+    for kind, a in A.accepts():
+        ab, ty = a.encode(), "Ethereum" if kind == "eth" else "Bitcoin"
+        for pre, post in A.WRAPPERS:
+            got = both(pre + ab + post, (pre, a, post))
+            assert A.coins(got) == [(ty, len(pre), len(pre) + len(a), a)], (pre, a, post)
+        assert A.coins(both(b"x" + ab, a)) == [], a
+    by_kind = {}
+    for r in A.KAT["reject"]:
+        by_kind.setdefault(r["kind"], []).append(r["text"])
+    classes = dict(A.mutants(), **{"reject " + kd: toks for kd, toks in by_kind.items()})
+    classes["accepts"] = [a for _, a in A.accepts()]
+    for cls, toks in classes.items():
+        buf, want = A.batch(toks)
+        assert A.coins(both(buf, cls)) == want, cls
+        if cls.startswith("reject") or cls in ("b58 outside alphabet", "bech32 case", "bech32 1", "bech32 b"):
+            assert want == [], cls
+        elif cls.startswith("eth"):      # a replaced digit or a flip to all-lower / all-upper leaves some of them valid
+            assert 0 < len(want) < len(toks), cls
+        elif cls == "accepts":
+            assert len(want) == len(toks)
+
+    b58 = sorted(A.KAT["b58"], key=lambda e: (len(e["text"]), e["text"]))
+    bech = sorted(A.KAT["bech32"], key=lambda e: (len(e["text"]), e["variant"]))
+    picks = [b58[0]["text"], b58[-1]["text"], [e["text"] for e in b58 if e["class"] == "zero+1"][0], bech[0]["text"], bech[-2]["text"],
+             [e["text"] for e in bech if e["variant"] == "bech32m" and len(e["text"]) == 45][0]] + [e["text"] for e in A.KAT["eth"][:2]]
+    assert (len(picks[0]), len(picks[1]), len(picks[3]), len(picks[4])) == (26, 62, 26, 62) and len(set(picks)) == 8
+    for edge in (64, 256, 2048, 8192, 16384):
+        for a in picks:
+            ab, ty = a.encode(), A.classify(a)
+            for shift in (0, 1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, len(ab) - 5, len(ab) - 4, len(ab) - 1, len(ab), len(ab) + 1):
+                pre = edge - shift
+                if pre < 1:
+                    continue
+                got = both(b"a" * (pre - 1) + b" " + ab + b" tail\n", (edge, a, shift))
+                assert A.coins(got) == [(ty, pre, pre + len(ab), a)], (edge, a, shift)
+    for a in picks:
+        for pad in (0, 1, 15, 63, 64, 2047, 2048 - len(a)):
+            got = both(b"x" * pad + b" " + a.encode(), (a, pad))
+            assert A.coins(got) == [(A.classify(a), pad + 1, pad + 1 + len(a), a)], (a, pad)
+    seen = {"Bitcoin": set(), "Ethereum": set()}
+    for a in (picks[1], picks[5], picks[6]):
+        for v in range(256):
+            for buf in (b"id " + bytes([v]) + a.encode() + b" end\n", b"id " + a.encode() + bytes([v]) + b" end\n"):
+                got = both(buf, (a, v))
+                seen[A.classify(a)].add(bool(A.coins(got)))
+    assert seen == {"Bitcoin": {False, True}, "Ethereum": {False, True}}
+
+
+def test_btc_eth_hits_through_scans_and_a_full_checksum_pass(M, oracle, tmp_path, monkeypatch, capfd):
+    """The constructed vectors as DATABASE KEYS and log tokens. A small log through every scan entry (host buffer, device-resident
+    forked / sliced / submitted / compact) and, in a child process with MATCHY_AMD_NO_FORK=1, through the one-stream schedule. Then a
+    log of 72 000 lines, one token each, that cycles through accepts and mutants of Base58Check, Bech32, Ethereum and Monero with
+    the kinds interleaved line by line, so that every wave of k_rare holds all four: more than 65 536 tokens pass the prefix tests
+    of k_validate<4>, counted from the construction AND read from the scanner (MATCHY_AMD_TRACE, which fetch() looks up on every
+    call: the overflow line of the first scan, whose `heavy` list starts at len / 256 entries, and the n_heavy counter of both
+    scans). That is more than one entry per resident lane of k_rare (256 CUs x 4 workgroups x 64 lanes): its grid-stride loop goes
+    round again with the lanes' token / decode buffers reused across kinds. Only the host-buffer entry runs that second trip: it
+    scans the log as one slice; the three slices of the device-resident entries behind it hold about 22 000 entries each and
+    check the same records without it. Every accept that is a key must be a hit, in order, nothing else."""
+    import re
+    import subprocess
+    import address_cases as A
+    accepts = [a for _, a in A.accepts()]
+    keys = accepts[::2]
+    xkeys = A.XMR["accept"][::2]
+    b = M.DatabaseBuilder(build_epoch=1)
+    for i, a in enumerate(keys + xkeys):
+        b.add_entry(a, {"coin": A.classify(a) or "xmr", "n": i})
+    b.add_entry("evil.com", {"why": "bad"})
+    b.add_entry("8.8.8.8", {"who": "dns"})
+    blob = b.build()
+    keyset = set(keys + xkeys)
+
+    def hit_texts(hits, text):
+        out = {}
+        for h in hits:
+            if h["type"] in ("Bitcoin", "Ethereum", "Monero"):
+                out.setdefault(h["type"], []).append(text[h["start"]:h["end"]].decode())
+        return out
+
+    def want_texts(tokens):
+        out = {}
+        for t in tokens:
+            if t in keyset:
+                out.setdefault(A.classify(t) or "Monero", []).append(t)
+        return out
+
+    rows = [f"203.0.113.{i % 250} paid {a} via evil.com" for i, a in enumerate(accepts)]
+    rows += [f"8.8.8.8 refused {r['text']}" for r in A.KAT["reject"]]
+    text = ("\n".join(rows) + "\n").encode()
+    gh, gl, gs, wh, wl, ws = _scan_both(M, oracle, blob, text)
+    assert gs == ws and gh == wh and gl == wl
+    assert hit_texts(gh, text) == want_texts(accepts) == {"Bitcoin": [k for k in keys if A.classify(k) == "Bitcoin"],
+                                                           "Ethereum": [k for k in keys if A.classify(k) == "Ethereum"]}
+    (tmp_path / "db.mxy").write_bytes(blob)
+    (tmp_path / "small.log").write_bytes(text)
+    code = r"""
+import ctypes, json, sys
+sys.path.insert(0, ".")
+import matchy_amd as M
+db = M.Database(open(sys.argv[1], "rb").read())
+log = open(sys.argv[2], "rb").read()
+sc = M.Scanner(db)
+hip = ctypes.CDLL("libamdhip64.so")
+d = ctypes.c_void_p()
+assert hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(len(log) + 64)) == 0
+assert hip.hipMemcpy(d, log, ctypes.c_size_t(len(log)), 1) == 0
+r = sc.scan_device(d.value, len(log), fetch_mode=3)
+print(json.dumps([r.lines, r.candidates, r.hits()]))
+"""
+    env = dict(os.environ, MATCHY_AMD_NO_FORK="1")
+    out = subprocess.run([sys.executable, "-c", code, str(tmp_path / "db.mxy"), str(tmp_path / "small.log")], cwd=ROOT, env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines, cands, hits = json.loads(out.stdout.strip().splitlines()[-1])
+    assert (lines, cands) == ws and hits == wh
+
+    muts = A.mutants()
+    per_kind = [accepts_of + muts_of for accepts_of, muts_of in (
+        ([e["text"] for e in A.KAT["b58"]], muts["b58 symbol"] + muts["b58 outside alphabet"][::64]),
+        ([e["text"] for e in A.KAT["bech32"]], muts["bech32 symbol"] + muts["bech32 case"] + muts["bech32 1"] + muts["bech32 b"]),
+        ([e["text"] for e in A.KAT["eth"]], muts["eth symbol"] + muts["eth case"]),
+        (A.XMR["accept"], [r["text"] for r in A.XMR["reject"]]))]
+    tokens = [per_kind[j % 4][(j // 4) % len(per_kind[j % 4])] for j in range(72000)]
+    assert sum(1 for t in tokens if A.passes_prefix(t)) > 65536
+    big = "".join(t + "\n" for t in tokens).encode()
+    assert 3_000_000 < len(big) < 6_000_000
+    db = M.Database(blob); sc = M.Scanner(db)
+    want, _, st = oracle.Database(blob).scan(big, threads=min(len(os.sched_getaffinity(0)), 16), cache=0, want_json=False)
+    assert hit_texts(want, big) == want_texts(tokens)
+    assert set().union(*map(set, want_texts(tokens).values())) == keyset      # every key occurs, of all three types
+    n_model = sum(1 for t in tokens if A.passes_prefix(t))
+    capfd.readouterr()
+    monkeypatch.setenv("MATCHY_AMD_TRACE", "1")
+    for nth in range(2):     # the first scan finds the list of k_rare too small and runs again; the second fits
+        res = sc.scan(big)
+        assert (res.lines, res.candidates) == (st.lines, st.candidates)
+        assert res.hits() == want
+        res.close()
+        err = capfd.readouterr().err
+        print(err)
+        over = [int(d) for d, c in re.findall(r"regrow and rescan:.* heavy (\d+)>(\d+)", err)]
+        final = [int(n) for n in re.findall(r"slices=1 .* n_heavy=(\d+) ", err)]
+        assert len(final) == 1 and final[0] > 65536 and final[0] == n_model, err
+        # the overflow line that names `heavy` last gives its exact demand (the lists in front of it fit by then); the second scan fits
+        assert (over[-1:] == final) if nth == 0 else (over == []), err
+    monkeypatch.delenv("MATCHY_AMD_TRACE")
+    _device_entries(sc, big, want, None, (st.lines, st.candidates), slices=(3,))
     sc.close(); db.close()
 
 

@@ -1,9 +1,12 @@
 """CPU: the oracle restatement against the known-answer vectors the reference's own tests hold
 (tests/golden/extractor_kat.json; transcribed by tests/golden/make_extractor_kat.py)."""
 import json
+import sys
 from pathlib import Path
 
 import pytest
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 GOLD = Path(__file__).parent / "golden"
 CASES = json.loads((GOLD / "extractor_kat.json").read_text())["cases"]
@@ -113,3 +116,66 @@ def test_monero_constructed_accepts_and_rejects(oracle):
     for r in k["reject"]:
         buf = b"pay " + r["text"].encode() + b" now"
         assert not [m for m in oracle.extract(buf) if m[0] == "Monero"], r
+
+
+def test_btc_eth_constructed_accepts_and_rejects(oracle):
+    """Bitcoin (Base58Check, Bech32, Bech32m) and Ethereum (EIP-55) tokens constructed from the rule itself
+    (tests/golden/make_btc_eth_kat.py; crates/matchy-extractor/src/lib.rs:1269-1361, 1799-1892): oracle == construction for every
+    accept in every wrapper, for the constructed rejects and for every one-symbol mutant tests/address_cases.py derives, and the
+    fixture covers what it promises."""
+    import address_cases as A
+    k = A.KAT
+    # coverage: every length with both first characters, hashed lengths on both sides of the second SHA-256 length byte (32) and of
+    # the second block (56), the decoder's limbs 9..12, runs of leading '1', and all 80 (hex position, polarity) pairs of EIP-55
+    for first in "13":
+        assert {len(e["text"]) for e in k["b58"] if e["text"][0] == first} >= set(range(26, 63)), first
+    hashed = {e["hashed_len"] for e in k["b58"]}
+    assert hashed >= {31, 32, 33, 54, 55, 56} and min(hashed) <= 21
+    assert {e["hashed_len"] for e in k["b58"] if e["class"] == "zero"} >= {54, 55, 56}
+    assert [(len(e["text"]), e["hashed_len"], e["zeros"]) for e in k["b58"] if e["class"] == "zero+1"] == [(62, 56, 55)]
+    assert {e["limbs"] for e in k["b58"]} >= {9, 10, 11, 12} and {e["limbs"] for e in k["b58"] if e["class"] == "wide"} == {9, 10, 11, 12}
+    runs = {e["zeros"] for e in k["b58"] if e["class"] == "run"}
+    assert runs >= {2, 5, 14, 20, 30} and max(runs) >= 55
+    for e in k["b58"]:     # the recorded figures are those of the text
+        d = A.G.b58decode(e["text"])
+        assert (e["payload_len"], e["hashed_len"], e["zeros"]) == (len(d), len(d) - 4, len(d) - len(d.lstrip(b"\0"))), e
+        assert e["limbs"] == (int.from_bytes(d, "big").bit_length() + 31) // 32
+    for variant in ("bech32", "bech32m"):
+        assert {len(e["text"]) for e in k["bech32"] if e["variant"] == variant} == set(range(26, 63))
+        want = A.G.BECH32_CONST if variant == "bech32" else A.G.BECH32M_CONST
+        assert all(A.G.bech32_decode(e["text"]) == ("bc", want) for e in k["bech32"] if e["variant"] == variant)
+    pairs = set()
+    for e in k["eth"]:
+        if e["class"] in ("spec", "random"):
+            pairs |= set(A.G.eip55_pairs(e["text"]))
+    assert pairs == {(i, q) for i in range(40) for q in (0, 1)}
+    assert {e["class"] for e in k["eth"]} == {"spec", "random", "all-lower", "all-upper", "all-digit", "one-letter", "two-letters"}
+
+    def got(buf):
+        return A.coins(oracle.extract(buf))
+
+    n = {"b58": 0, "bech32": 0, "eth": 0}
+    for kind, a in A.accepts():
+        ty = A.classify(a)
+        assert ty == ("Ethereum" if kind == "eth" else "Bitcoin"), a
+        n[kind] += 1
+        for pre, post in A.WRAPPERS:
+            assert got(pre + a.encode() + post) == [(ty, len(pre), len(pre) + len(a), a)], (pre, a, post)
+        assert got(b"x" + a.encode()) == [], a      # glued to a token character: a longer token / no boundary in front of "0x"
+    assert n["b58"] >= 2 * 37 + 6 + 3 + 1 + 4 and n["bech32"] == 2 * 37 and n["eth"] >= 4 + 32 + 6
+    for r in k["reject"]:
+        assert A.classify(r["text"]) is None, r
+        assert got(b"pay " + r["text"].encode() + b" now") == [], r
+    assert {r["why"].split(", ")[-1] for r in k["reject"] if r["kind"] == "b58"} >= {"first character " + c for c in "25KLm"}
+    muts = A.mutants()
+    assert all(muts.values())
+    for cls, toks in muts.items():
+        buf, want = A.batch(toks)
+        assert got(buf) == want, cls
+        if cls in ("b58 outside alphabet", "bech32 case", "bech32 1", "bech32 b"):
+            assert want == [], cls
+    # a case flip is a reject unless what it gives is all-lower or all-upper
+    for t in muts["eth case"]:
+        letters = [c for c in t[2:] if c.isalpha()]
+        assert (A.classify(t) == "Ethereum") == (all(c.islower() for c in letters) or all(c.isupper() for c in letters)), t
+    assert sum(1 for t in muts["eth case"] if A.classify(t)) >= 2 and sum(1 for t in muts["eth case"] if not A.classify(t)) > 400
