@@ -456,6 +456,33 @@ int32_t matchy_multi_scanner_scan_file(matchy_multi_scanner_t *ms, const char *p
 /* Line context for the scanner of every worker (from the next batch a worker takes). Batches from _next carry values relative to
  * their batch; matchy_multi_scanner_scan merges them into values relative to `data`, like matchy_scanner_scan. */
 void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t *ms, bool enabled);
+
+/* ---- Hit tally (opt-in, off by default: with it never enabled a scanner allocates, launches and copies nothing more and every output
+ * stays as it is). How often every distinct matched value hit: a table in device memory, owned by the scanner, keyed by (item type,
+ * matched text) — the raw bytes data[start, start + length) of a hit record, case-sensitive, not NUL-terminated; for IP addresses the
+ * text in the log — fed from the hit records of every lookup scan while its batch is still resident, whatever the entry and the fetch
+ * mode (counts only, records, sorted, device-resident, compact), kept across scans, and read out as a top-N list: only counters and the
+ * rows of the report cross the bus. Pattern ids are deliberately not the key: `pattern_ids` mixes literal and glob ids, which both start
+ * at 0, and many networks share one data offset; matchy_amd_query_json(text) gives a reported value's cidr / data / patterns back.
+ * _set_tally applies from the next scan; switching it off keeps what was counted, _reset_tally empties it (and keeps its allocations),
+ * matchy_scanner_free releases it. A NULL handle is harmless. */
+void matchy_scanner_set_tally(matchy_scanner_t *scanner, bool enabled);
+bool matchy_scanner_tally(const matchy_scanner_t *scanner);
+void matchy_scanner_reset_tally(matchy_scanner_t *scanner);
+typedef struct matchy_tally_entry_t { const uint8_t *text; uint32_t len; uint8_t item_type; uint64_t count; } matchy_tally_entry_t;
+typedef struct matchy_tally_t { const matchy_tally_entry_t *entries; size_t n_entries; uint64_t distinct, matches; void *_internal; } matchy_tally_t;
+/* The first `limit` entries (0 = all) ordered by count descending, then by the extractor order of the type (IPv6, IPv4, e-mail, domain,
+ * hashes, Bitcoin, Ethereum, Monero), then by text bytewise ascending; `distinct` = entries in the table, `matches` = hits counted (the
+ * sum of all counts). The selection is made from the counts; only the texts of the chosen entries are copied back. Release with
+ * matchy_tally_free. MATCHY_ERROR_INVALID_PARAM for a scanner that never enabled the tally. */
+int32_t matchy_scanner_tally_top(matchy_scanner_t *scanner, size_t limit, matchy_tally_t *out);
+/* The same for every worker's scanner of a multi-device scanner: _set_tally applies from the next batch a worker takes. _tally_top
+ * and _reset_tally need matchy_multi_scanner_pending() == 0 (MATCHY_ERROR_INVALID_PARAM otherwise; _reset_tally then does nothing):
+ * _tally_top exports every worker's whole table, merges by (type, text) on the host, then orders and cuts. */
+int32_t matchy_multi_scanner_set_tally(matchy_multi_scanner_t *ms, bool enabled);
+int32_t matchy_multi_scanner_tally_top(matchy_multi_scanner_t *ms, size_t limit, matchy_tally_t *out);
+void matchy_multi_scanner_reset_tally(matchy_multi_scanner_t *ms);
+void matchy_tally_free(matchy_tally_t *tally);
 /* Deterministic builds for tests: fixes the build_epoch metadata value. */
 int32_t matchy_builder_set_build_epoch(matchy_builder_t *b, uint64_t epoch);
 

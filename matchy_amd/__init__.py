@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_set_line_context", "matchy_scanner_line_context", "matchy_scan_result_lines", "matchy_multi_scanner_set_line_context",
     "matchy_scan_result_to_ndjson_lines", "matchy_scanner_get_line_timing",
     "matchy_amd_extractor_set_unique", "matchy_amd_extractor_unique", "matchy_amd_extractor_reset_unique", "matchy_amd_extractor_unique_count",
+    "matchy_scanner_set_tally", "matchy_scanner_tally", "matchy_scanner_reset_tally", "matchy_scanner_tally_top",
+    "matchy_multi_scanner_set_tally", "matchy_multi_scanner_tally_top", "matchy_multi_scanner_reset_tally", "matchy_tally_free",
 ]
 
 # bytes per tile of the '\n' count array and tiles per workgroup of its prefix sum (csrc/line_index.h): the sizes at which the line
@@ -114,6 +116,16 @@ class _ScanResult(C.Structure):
 class _ScanLine(C.Structure):
     # matchy_scan_line_t (16 bytes)
     _fields_ = [("line", C.c_uint32), ("line_start", C.c_uint32), ("line_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _TallyEntry(C.Structure):
+    # matchy_tally_entry_t
+    _fields_ = [("text", C.POINTER(C.c_uint8)), ("len", C.c_uint32), ("item_type", C.c_uint8), ("count", C.c_uint64)]
+
+
+class _Tally(C.Structure):
+    _fields_ = [("entries", C.POINTER(_TallyEntry)), ("n_entries", C.c_size_t), ("distinct", C.c_uint64), ("matches", C.c_uint64),
+                ("_internal", C.c_void_p)]
 
 
 _lib = None
@@ -232,6 +244,14 @@ def lib():
         "matchy_multi_scanner_set_line_context": (None, [vp, C.c_bool]),
         "matchy_scan_result_to_ndjson_lines": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, cp, C.c_uint64, C.c_bool, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_line_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_set_tally": (None, [vp, C.c_bool]),
+        "matchy_scanner_tally": (C.c_bool, [vp]),
+        "matchy_scanner_reset_tally": (None, [vp]),
+        "matchy_scanner_tally_top": (C.c_int32, [vp, C.c_size_t, C.POINTER(_Tally)]),
+        "matchy_multi_scanner_set_tally": (C.c_int32, [vp, C.c_bool]),
+        "matchy_multi_scanner_tally_top": (C.c_int32, [vp, C.c_size_t, C.POINTER(_Tally)]),
+        "matchy_multi_scanner_reset_tally": (None, [vp]),
+        "matchy_tally_free": (None, [C.POINTER(_Tally)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -618,6 +638,27 @@ class ScanResult:
             pass
 
 
+def _read_tally(fn, handle, limit, what):
+    """[(text bytes, item type name, count)] in read-out order through matchy_*_tally_top; .distinct / .matches ride on the list"""
+    t = _Tally()
+    rc = fn(handle, int(limit), C.byref(t))
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): " + last_error())
+    try:
+        out = TallyList((C.string_at(t.entries[i].text, t.entries[i].len), ITEM_TYPE_NAMES[t.entries[i].item_type], int(t.entries[i].count))
+                        for i in range(t.n_entries))
+        out.distinct, out.matches = int(t.distinct), int(t.matches)
+        return out
+    finally:
+        lib().matchy_tally_free(C.byref(t))
+
+
+class TallyList(list):
+    """what Scanner.tally() returns: a list of (bytes, item_type, count) with the totals of the whole table as attributes"""
+    distinct = 0
+    matches = 0
+
+
 class Scanner:
     """Bulk scan session (the device-side Worker). One per thread / stream."""
 
@@ -679,6 +720,20 @@ class Scanner:
         lib().matchy_scanner_get_line_timing(self._h, out)
         return dict(count=out[0], prefix=out[1], resolve=out[2])
 
+    def set_tally(self, on=True):
+        """hit tally for the next scans: matches per distinct (item type, matched text), counted on the GPU across scans (off by default)"""
+        lib().matchy_scanner_set_tally(self._h, bool(on))
+
+    def tally_enabled(self) -> bool:
+        return bool(lib().matchy_scanner_tally(self._h))
+
+    def reset_tally(self):
+        lib().matchy_scanner_reset_tally(self._h)
+
+    def tally(self, limit=0):
+        """the first `limit` entries (0 = all) as (bytes, item_type, count): count descending, extractor order of the type, text ascending"""
+        return _read_tally(lib().matchy_scanner_tally_top, self._h, limit, "matchy_scanner_tally_top")
+
     def set_slices(self, n: int):
         """scan_device cuts large batches into slices (tail of one slice beside the streaming pass of the next): 0 = default, 1 = never, n = n equal slices."""
         lib().matchy_scanner_set_slices(self._h, n)
@@ -734,6 +789,19 @@ class MultiScanner:
     def set_line_context(self, on: bool):
         """line context for every worker's scanner, from the next batch on"""
         lib().matchy_multi_scanner_set_line_context(self._h, bool(on))
+
+    def set_tally(self, on=True):
+        """hit tally on every worker's scanner, from the next batch on"""
+        rc = lib().matchy_multi_scanner_set_tally(self._h, bool(on))
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_set_tally failed ({rc}): " + last_error())
+
+    def reset_tally(self):
+        lib().matchy_multi_scanner_reset_tally(self._h)
+
+    def tally(self, limit=0):
+        """the workers' tallies merged by (type, text), then ordered and cut like Scanner.tally; needs pending() == 0"""
+        return _read_tally(lib().matchy_multi_scanner_tally_top, self._h, limit, "matchy_multi_scanner_tally_top")
 
     def submit_ptr(self, host_ptr: int, nbytes: int, tag: int = 0, numa_node: int = -1):
         """queue one newline-aligned batch that lives at a host address (e.g. a pinned torch tensor); take it back with next().

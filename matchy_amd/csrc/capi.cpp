@@ -277,6 +277,35 @@ void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, ma
 
 int mxy::capi::default_device_of(const matchy_t* db) { return reinterpret_cast<const Db*>(db)->default_device; }
 
+// hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
+namespace {
+struct TallyInternal {
+    std::vector<TallyEntry> rows;
+    std::vector<matchy_tally_entry_t> entries;
+};
+}  // namespace
+bool mxy::capi::scanner_tally_top(matchy_scanner_t* s, size_t limit, std::vector<TallyEntry>& rows, uint64_t& distinct, uint64_t& matches) {
+    Scanner& sc = *reinterpret_cast<ScannerH*>(s)->sc;
+    rows.clear();
+    if (!sc.hit_tally()) return false;
+    sc.tally_top(limit, rows);
+    distinct = sc.hit_tally()->distinct(); matches = sc.hit_tally()->matches();
+    return true;
+}
+void mxy::capi::fill_tally(std::vector<TallyEntry>&& rows, uint64_t distinct, uint64_t matches, matchy_tally_t* out) {
+    auto in = std::make_unique<TallyInternal>();
+    in->rows = std::move(rows);
+    in->entries.resize(in->rows.size());
+    for (size_t i = 0; i < in->rows.size(); ++i) {
+        const TallyEntry& r = in->rows[i];
+        in->entries[i] = matchy_tally_entry_t{reinterpret_cast<const uint8_t*>(r.text.data()), (uint32_t)r.text.size(), r.item_type, r.count};
+    }
+    out->entries = in->entries.empty() ? nullptr : in->entries.data();
+    out->n_entries = in->entries.size();
+    out->distinct = distinct; out->matches = matches;
+    out->_internal = in.release();
+}
+
 extern "C" {
 
 const char* matchy_amd_last_error(void) { return g_last_error.c_str(); }
@@ -850,6 +879,35 @@ int32_t matchy_scan_result_lines(const matchy_scan_result_t* r, const matchy_sca
     if (lines_with_matches) *lines_with_matches = in->lines_with_matches;
     return MATCHY_SUCCESS;
 }
+
+// hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
+void matchy_scanner_set_tally(matchy_scanner_t* s, bool on) {
+    if (!s) return;
+    try { reinterpret_cast<ScannerH*>(s)->sc->set_tally(on); } catch (const HipError& e) { set_error(e.what); }
+}
+bool matchy_scanner_tally(const matchy_scanner_t* s) { return s && reinterpret_cast<const ScannerH*>(s)->sc->tally(); }
+void matchy_scanner_reset_tally(matchy_scanner_t* s) {
+    if (!s) return;
+    try { reinterpret_cast<ScannerH*>(s)->sc->reset_tally(); } catch (const HipError& e) { set_error(e.what); }
+}
+int32_t matchy_scanner_tally_top(matchy_scanner_t* s, size_t limit, matchy_tally_t* out) {
+    if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    try {
+        std::vector<TallyEntry> rows;
+        uint64_t distinct = 0, matches = 0;
+        if (!scanner_tally_top(s, limit, rows, distinct, matches)) { set_error("matchy_scanner_tally_top: the tally was never enabled on this scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+        fill_tally(std::move(rows), distinct, matches, out);
+        return MATCHY_SUCCESS;
+    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+void matchy_tally_free(matchy_tally_t* t) {
+    if (!t) return;
+    delete reinterpret_cast<TallyInternal*>(t->_internal);
+    memset(t, 0, sizeof(*t));
+}
+
 void matchy_scanner_get_timing(const matchy_scanner_t* s, float out[5]) {
     if (!s || !out) return;
     const ScanTiming& t = reinterpret_cast<const ScannerH*>(s)->sc->timing();

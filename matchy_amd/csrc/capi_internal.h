@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/matchy_amd.h"
+#include "tally.h"
 
 namespace mxy {
 namespace capi {
@@ -26,6 +27,12 @@ struct ScanResultInternal {
     const matchy_scan_line_t* ip4_lines = nullptr;
     uint64_t lines_with_matches = 0;
 };
+
+// hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top
+// the first `limit` entries of a scanner's tally (0 = all) and its totals; false when the scanner never enabled it. Throws what the engine throws.
+bool scanner_tally_top(matchy_scanner_t* s, size_t limit, std::vector<TallyEntry>& rows, uint64_t& distinct, uint64_t& matches);
+// hands `rows` (in their final order) to the caller as a matchy_tally_t that owns them
+void fill_tally(std::vector<TallyEntry>&& rows, uint64_t distinct, uint64_t matches, matchy_tally_t* out);
 
 }  // namespace capi
 }  // namespace mxy

@@ -13,6 +13,7 @@
 // stderr (commands/match_cmd.rs:514-581). Every batch is scanned on the GPU through the C ABI (matchy_scanner_scan);
 // there is no CPU scan path. Flags that only tune the reference's CPU thread pool (-j, --readers, --cache-size, -p,
 // --debug-routing) are accepted and ignored; .gz inputs are decompressed on the host (zlib); -f/--follow polls the files.
+// --tally[=N] adds, behind the match records, {"count","item_type","matched_text","result"} per distinct matched value (tally.hip).
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -55,6 +56,8 @@ int usage() {
             "  matchy build <INPUT>... -o <FILE> [-f text|csv|json] [-t TYPE] [-d DESC] [--desc-lang LANG] [-i] [-v]\n"
             "  matchy match <DATABASE> <INPUT>... [--format json|summary] [-s] [--batch-bytes N] [--extractors LIST] [--device N | --devices LIST|all] [-j N|auto] [-f]\n"
             "               [--line-numbers] [--input-line]   (\"line_number\" / \"input_line\" in every record, computed on the GPU)\n"
+            "               [--tally[=N]]   (behind the matches: one JSON line per distinct matched value with its hit count, the N most frequent; default 20,\n"
+            "                                0 = all; counted on the GPU; with --format summary nothing else is printed; not with --follow)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -595,7 +598,8 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false;
+    size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
     int jobs = 0;   // -j N|auto (matchy.rs:98-103: worker threads): scanners here; auto = 2 (summary) / 4 (json) per device listed once
@@ -623,11 +627,18 @@ int cmd_match(int argc, char** argv) {
         else if (a == "-f" || a == "--follow") follow = true;
         else if (a == "--line-numbers") line_numbers = true;
         else if (a == "--input-line") input_line = true;
+        else if (a == "--tally") tally = true;
+        else if (a.compare(0, 8, "--tally=") == 0) {
+            const std::string n = a.substr(8);
+            if (n.empty() || n.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "error: --tally=N needs a number, got '%s'\n", n.c_str()); return 2; }
+            tally = true; tally_limit = strtoull(n.c_str(), nullptr, 10);
+        }
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
     if (pos.size() < 2) return usage();
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
+    if (follow && tally) { fprintf(stderr, "Error: --tally is not supported with --follow (the report is printed after the last batch)\n"); return 1; }
     if (follow && stats) fprintf(stderr, "[INFO] Processing existing file content...\n");
     if (follow) for (size_t i = 1; i < pos.size(); ++i) if (pos[i] == "-") { fprintf(stderr, "Error: --follow mode not supported with stdin\n"); return 1; }
     // device list: one worker (scanner) per entry; an entry may repeat (two scanners on one GPU overlap one batch's
@@ -710,6 +721,7 @@ int cmd_match(int argc, char** argv) {
     pl.line_ctx = line_numbers || input_line;
     pl.input_line = input_line;
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
+    if (tally) matchy_multi_scanner_set_tally(ms, true);
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
     std::vector<std::string> paths;
     bool stdin_seen = false;
@@ -733,6 +745,36 @@ int cmd_match(int argc, char** argv) {
     printer.join();
     for (size_t i = 0; i < paths.size(); ++i) if (read_failed[i]) input_failed[i] = 1;
     for (size_t i : pl.rejected_inputs) if (i < input_failed.size()) input_failed[i] = 1;
+    // --tally: the workers' tables merged, one JSON line per distinct matched value behind the match records; what the database holds for
+    // a value is asked of it now (a host query per row of the report)
+    bool tally_failed = false;
+    uint64_t tally_distinct = 0;
+    if (tally) {
+        matchy_tally_t tl;
+        if (matchy_multi_scanner_tally_top(ms, tally_limit, &tl) != MATCHY_SUCCESS) {
+            fprintf(stderr, "Error: Failed to read the hit tally: %s\n", matchy_amd_last_error());
+            tally_failed = true;
+        } else {
+            tally_distinct = tl.distinct;
+            std::string line;
+            for (size_t i = 0; i < tl.n_entries; ++i) {
+                const matchy_tally_entry_t& e = tl.entries[i];
+                const std::string text((const char*)e.text, e.len);
+                line = "{\"count\":" + std::to_string((unsigned long long)e.count) + ",\"item_type\":";
+                json_escape(matchy_item_type_name(e.item_type), line);
+                line += ",\"matched_text\":";
+                json_escape(text, line);
+                line += ",\"result\":";
+                int32_t found = 0;
+                char* js = matchy_amd_query_json(db, text.c_str(), &found);
+                line += js ? js : "[]";
+                if (js) matchy_free_string(js);
+                line += "}\n";
+                fwrite(line.data(), 1, line.size(), stdout);
+            }
+            matchy_tally_free(&tl);
+        }
+    }
     fflush(stdout);
     if (trace) fprintf(stderr, "[matchy] all batches done after %.1f ms\n", since0());
     pl.release_mappings((size_t)-1);
@@ -756,6 +798,7 @@ int cmd_match(int argc, char** argv) {
                 t.lines ? 100.0 * (double)t.lines_with_matches / (double)t.lines : 0.0);
         fprintf(stderr, "[INFO] Total matches: %s\n", fmt_num(t.matches).c_str());
         fprintf(stderr, "[INFO] Candidates tested: %s\n", fmt_num(t.candidates).c_str());
+        if (tally && !tally_failed) fprintf(stderr, "[INFO] Distinct matched values: %s\n", fmt_num(tally_distinct).c_str());
         fprintf(stderr, "[INFO] Throughput: %.2f MB/s\n", secs > 0 ? (double)t.bytes / 1e6 / secs : 0.0);
         fprintf(stderr, "[INFO] Total time: %.2fs\n", secs);
         fprintf(stderr, "[INFO] Query rate: %.0f queries/s\n", secs > 0 ? (double)t.candidates / secs : 0.0);
@@ -768,7 +811,7 @@ int cmd_match(int argc, char** argv) {
     matchy_close(db);
     if (trace) fprintf(stderr, "[matchy] cleaned up after %.1f ms\n", since0());
     if (failed) { fprintf(stderr, "Error: %zu file(s) failed to process\n", failed); return 1; }
-    return 0;
+    return tally_failed ? 1 : 0;
 }
 
 // serde_json::to_string_pretty of a compact JSON text: two spaces per level, "key": value, empty containers stay "[]" / "{}"

@@ -1,6 +1,7 @@
 #include "engine.h"
 #include "batch_reader.h"
 #include "distinct.h"
+#include "tally.h"
 #include "unicode_lower.h"
 
 #include <dlfcn.h>
@@ -533,6 +534,22 @@ void Scanner::reset_unique() {
     distinct_->reset();
 }
 uint64_t Scanner::unique_count() const { return distinct_ ? distinct_->count() : 0; }
+
+void Scanner::set_tally(bool on) {
+    if (on && !tally_) tally_ = std::make_unique<HitTally>();
+    tally_on_ = on;
+}
+void Scanner::reset_tally() {
+    if (!tally_) return;
+    MXY_HIP(hipSetDevice(ddb_->device));
+    tally_->reset();
+}
+void Scanner::tally_top(size_t limit, std::vector<TallyEntry>& out) {
+    out.clear();
+    if (!tally_) return;
+    MXY_HIP(hipSetDevice(ddb_->device));
+    tally_->top(limit, out, nullptr);   // the null stream: every add() ended with its scan's stream synchronised, nothing is in flight
+}
 
 // work lists of one slice for `len` bytes of log
 void Scanner::Work::ensure(uint32_t len) {
@@ -1320,6 +1337,18 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     }
     out.has_lines = false; out.fin_lines = nullptr; out.c4_lines = nullptr; out.lines_with_matches = 0;
     if (last_.lines && last_.lookup && !single_) resolve_lines(out, dev_recs, hit_mode == HITS_FINAL, stream);
+    // hit tally: the records of the batch are counted where they lie, once per fetch — behind the regrow loop and the spill pass. With
+    // set_profile or MATCHY_AMD_TRACE the pass times its kernels (one more host wait between them)
+    if (tally_on_ && last_.lookup && !single_) {
+        tally_->set_profile(profile_ || trace);
+        tally_->add(last_.ptr, last_.len, final_.p, c.n_final, compact_ ? c4_.p : nullptr, compact_ ? c.n_c4 : 0u, stream);
+        if (trace) {
+            const HitTally::Events& ev = tally_->last_events();
+            fprintf(stderr, "[matchy_amd] tally: %u records, %llu distinct (+%u), rehashes=%u pool_regrows=%u direct_adds=%u, claim %.3f ms publish %.3f ms total %.3f ms\n",
+                    c.n_final + (compact_ ? c.n_c4 : 0u), (unsigned long long)tally_->distinct(), ev.new_entries, ev.rehashes, ev.pool_regrows, ev.direct_adds,
+                    tally_->last_claim_ms(), tally_->last_publish_ms(), tally_->last_ms());
+        }
+    }
     // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
     if (dedup) {
         distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);

@@ -31,6 +31,8 @@ void launch_ip_l24(const uint2* nodes, uint32_t node_count, uint32_t v4_start, u
 void launch_ip_leaf(const uint2* nodes, uint32_t node_count, uint2* l24, uint32_t* next, uint32_t n_leaf, uint32_t* leaf_node, uint2* leaf, hipStream_t s);
 
 class DistinctSet;   // distinct.h
+class HitTally;      // tally.h
+struct TallyEntry;
 
 struct HipError { std::string what; };
 #define MXY_HIP(expr)                                                                                   \
@@ -216,6 +218,14 @@ public:
     bool unique() const { return unique_; }
     void reset_unique();
     uint64_t unique_count() const;
+    // Hit tally (tally.hip): while on, every fetch of a lookup scan counts the final records of its batch per distinct (item type, matched
+    // text) in a table that lives in device memory across scans and pieces; tally_top reads the first `limit` entries out (0 = all). Off
+    // (the default), nothing of it is allocated, launched or copied; switching it off keeps what was counted.
+    void set_tally(bool on);
+    bool tally() const { return tally_on_; }
+    void reset_tally();
+    const HitTally* hit_tally() const { return tally_.get(); }   // null until the tally was first enabled
+    void tally_top(size_t limit, std::vector<TallyEntry>& out);
     void lookup_one(const std::string& text, Candidate c, ScanOutput& out);
     // Convenience: host buffer -> internal device buffer -> scan -> fetch (chunks of < 2^31 bytes).
     // `fin*` vectors receive owned copies of the final hits of all pieces, positions made absolute.
@@ -331,6 +341,8 @@ private:
     void resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
+    bool tally_on_ = false;
+    std::unique_ptr<HitTally> tally_;          // created by the first set_tally(true), kept (with its counts) while the feature is switched off
     DevBuf<uint32_t> spill_scratch_;           // per-thread scratch of k_lookup_spill (allocated when a scan first spills)
     DevBuf<uint8_t> staging_;  // scan_host only
     // pinned mirror of the final records written by the lookup kernels themselves: FinalHit[mirror_cap_] | u32 ids[mirror_ids_cap_] | i64 offs[..]

@@ -47,6 +47,7 @@ struct MultiScanner {
     size_t max_inflight = 4;
     bool closing = false;
     bool line_ctx = false;   // matchy_multi_scanner_set_line_context: every worker sets its scanner to it before a scan
+    bool tally = false, tally_ever = false;   // matchy_multi_scanner_set_tally: likewise
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
     std::string first_error;   // of a worker (scanner creation, scan): reported through matchy_amd_last_error by next()
@@ -65,7 +66,7 @@ struct MultiScanner {
         }
         for (;;) {
             MultiJob j;
-            bool want_lines = false;
+            bool want_lines = false, want_tally = false, touch_tally = false;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return closing || !q.empty(); });
@@ -78,6 +79,7 @@ struct MultiScanner {
                 q.erase(it);
                 cv_space.notify_one();
                 want_lines = line_ctx;
+                want_tally = tally; touch_tally = tally_ever;
             }
             MultiDone d;
             d.data = j.data; d.len = j.len; d.tag = j.tag; d.worker = w;
@@ -86,6 +88,7 @@ struct MultiScanner {
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
             else if (j.len) {
                 matchy_scanner_set_line_context(scanners[w], want_lines);
+                if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
                 d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
@@ -158,6 +161,51 @@ void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t* h, bool enabl
     MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
     std::lock_guard<std::mutex> lk(ms->mu);
     ms->line_ctx = enabled;
+}
+// Hit tally: the workers switch their scanners' tallies before a scan, like line context; the read-out and the reset touch the scanners
+// themselves and therefore need the workers idle (nothing pending).
+int32_t matchy_multi_scanner_set_tally(matchy_multi_scanner_t* h, bool enabled) {
+    if (!h) return MATCHY_ERROR_INVALID_PARAM;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    ms->tally = enabled;
+    if (enabled) ms->tally_ever = true;
+    return MATCHY_SUCCESS;
+}
+int32_t matchy_multi_scanner_tally_top(matchy_multi_scanner_t* h, size_t limit, matchy_tally_t* out) {
+    if (!h || !out) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    {
+        std::lock_guard<std::mutex> lk(ms->mu);
+        if (ms->taken != ms->submitted) { set_error("matchy_multi_scanner_tally_top: batches are still pending"); return MATCHY_ERROR_INVALID_PARAM; }
+        if (!ms->tally_ever) { set_error("matchy_multi_scanner_tally_top: the tally was never enabled on this scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    }
+    try {
+        // every worker's whole table, merged by (type, text), then ordered and cut
+        std::vector<std::vector<TallyEntry>> parts;
+        uint64_t matches = 0;
+        for (matchy_scanner_t* sc : ms->scanners) {
+            if (!sc) continue;
+            std::vector<TallyEntry> rows;
+            uint64_t d = 0, m = 0;
+            if (!scanner_tally_top(sc, 0, rows, d, m)) continue;   // a worker that has not scanned since the tally was enabled
+            matches += m;
+            parts.push_back(std::move(rows));
+        }
+        std::vector<TallyEntry> all = tally_merge(parts);
+        const uint64_t distinct = all.size();
+        tally_order(all, limit);
+        fill_tally(std::move(all), distinct, matches, out);
+        return MATCHY_SUCCESS;
+    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+void matchy_multi_scanner_reset_tally(matchy_multi_scanner_t* h) {
+    if (!h) return;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    { std::lock_guard<std::mutex> lk(ms->mu); if (ms->taken != ms->submitted) { set_error("matchy_multi_scanner_reset_tally: batches are still pending"); return; } }
+    for (matchy_scanner_t* sc : ms->scanners) if (sc) matchy_scanner_reset_tally(sc);
 }
 void matchy_multi_scanner_set_batch_hook(matchy_multi_scanner_t* h, matchy_multi_batch_fn fn, void* user) {
     if (!h) return;
