@@ -339,6 +339,40 @@ int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t *scanner, const matc
                                            const char *source, uint64_t line_base, bool with_input_line, char **out, size_t *out_len);
 /* With matchy_scanner_set_profile: milliseconds of the streaming '\n' count, the prefix sum, and resolve + distinct set of the last scan. */
 void matchy_scanner_get_line_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* ---- Segmented scans: many small inputs as one batch.
+ * The caller describes a buffer as a sequence of segments (the files of a pack): the scan runs once, as for any buffer, and a pass
+ * behind it attributes every hit record to its segment on the GPU and counts per segment. '\n' is a boundary for every extractor, so
+ * scanning "A\nB\n" finds exactly the matches of "A\n" and of "B\n". */
+typedef struct matchy_scan_segment_t {
+  uint32_t start, len;          /* as given (len = next start - start; the last one ends at the buffer's end) */
+  uint32_t hits;                /* matches whose start lies in the segment (records of `hits` and `ip4_hits` together) */
+  uint32_t line_base;           /* '\n' bytes in front of `start`            — line context only, else 0 */
+  uint32_t lines;               /* '\n' bytes inside the segment              — line context only, else 0 */
+  uint32_t lines_with_matches;  /* distinct lines of the segment with a hit   — line context only, else 0 */
+  uint32_t reserved[2];
+} matchy_scan_segment_t;
+/* Copies the table; it applies to the scanner's NEXT scan only, through every entry (matchy_scanner_scan, _scan_device,
+ * _submit_device: read at submit), and that scan consumes it whether it succeeds or not. n == 0 or starts == NULL clears a pending
+ * table. Required: starts[0] == 0, non-decreasing (equal neighbours are empty segments), every start <= the scan's len, and every
+ * non-empty segment in front of the last ends in '\n'. A table that breaks a rule fails that scan with MATCHY_ERROR_INVALID_PARAM
+ * and a message (the newline rule is checked on the device, one byte per segment; the message names the first offending segment);
+ * the scanner stays usable. Extraction-only scans and single queries ignore segments. */
+int32_t matchy_scanner_set_segments(matchy_scanner_t *scanner, const uint32_t *starts, size_t n);
+/* segment_of_hit[i] belongs to result->hits[i], segment_of_ip4_hit[i] to result->ip4_hits[i]: the LAST segment whose start is <= the
+ * hit's start (an empty segment never owns a hit). Ownership, lifetime and residency follow the hit arrays of the result, as for
+ * matchy_scan_result_lines (NULL for MATCHY_SCAN_FETCH_COUNTS). `segments` is host memory owned by the result, n_segments entries,
+ * filled for every fetch mode. The line of a hit inside its segment is lines[i].line - segments[s].line_base. MATCHY_ERROR_INVALID_PARAM
+ * for a result of a scan without segments. Any out pointer may be NULL. */
+int32_t matchy_scan_result_segments(const matchy_scan_result_t *result, const uint32_t **segment_of_hit, const uint32_t **segment_of_ip4_hit,
+                                    const matchy_scan_segment_t **segments, size_t *n_segments);
+/* matchy_scan_result_to_ndjson with sources[segment] as the source of each record. line_bases != NULL: the result must carry line
+ * context, and the records are those of matchy_scan_result_to_ndjson_lines with
+ * "line_number" = line_bases[s] + (line - segments[s].line_base) + 1. */
+int32_t matchy_scan_result_to_ndjson_segments(matchy_scanner_t *scanner, const matchy_scan_result_t *result, const uint8_t *text,
+                                              const char *const *sources, const uint64_t *line_bases, bool with_input_line,
+                                              char **out, size_t *out_len);
+/* With matchy_scanner_set_profile: milliseconds of the segment pass, the record passes and the lines-with-matches pass of the last scan. */
+void matchy_scanner_get_segment_timing(const matchy_scanner_t *scanner, float out_ms[3]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -439,6 +473,10 @@ int32_t matchy_multi_scanner_submit(matchy_multi_scanner_t *ms, const uint8_t *d
  * that node takes it first, a worker of another node only when it has nothing of its own. */
 int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, void *tag, const void *pinned_range,
                                          int32_t numa_node);
+/* matchy_multi_scanner_submit of a batch of n segments (matchy_scanner_set_segments: `starts` is copied): the worker that takes the
+ * batch sets the table on its scanner before the scan, and the batch from _next answers matchy_scan_result_segments. */
+int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, const uint32_t *starts, size_t n,
+                                             void *tag, const void *pinned_range);
 /* NUMA node of a worker's GPU (-1 = unknown) and the number of CPUs its thread bound itself to (0 = not bound); valid once the
  * worker thread has started (after the first _next at the latest). */
 int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t *ms, size_t worker, int32_t *node, int32_t *cpus_bound);

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "matchy_amd_extractor_set_unique", "matchy_amd_extractor_unique", "matchy_amd_extractor_reset_unique", "matchy_amd_extractor_unique_count",
     "matchy_scanner_set_tally", "matchy_scanner_tally", "matchy_scanner_reset_tally", "matchy_scanner_tally_top",
     "matchy_multi_scanner_set_tally", "matchy_multi_scanner_tally_top", "matchy_multi_scanner_reset_tally", "matchy_tally_free",
+    "matchy_scanner_set_segments", "matchy_scan_result_segments", "matchy_scan_result_to_ndjson_segments",
+    "matchy_multi_scanner_submit_segments", "matchy_scanner_get_segment_timing",
 ]
 
 # bytes per tile of the '\n' count array and tiles per workgroup of its prefix sum (csrc/line_index.h): the sizes at which the line
@@ -116,6 +118,12 @@ class _ScanResult(C.Structure):
 class _ScanLine(C.Structure):
     # matchy_scan_line_t (16 bytes)
     _fields_ = [("line", C.c_uint32), ("line_start", C.c_uint32), ("line_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _ScanSegment(C.Structure):
+    # matchy_scan_segment_t (32 bytes)
+    _fields_ = [("start", C.c_uint32), ("len", C.c_uint32), ("hits", C.c_uint32), ("line_base", C.c_uint32), ("lines", C.c_uint32),
+                ("lines_with_matches", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class _TallyEntry(C.Structure):
@@ -244,6 +252,12 @@ def lib():
         "matchy_multi_scanner_set_line_context": (None, [vp, C.c_bool]),
         "matchy_scan_result_to_ndjson_lines": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, cp, C.c_uint64, C.c_bool, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_line_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_set_segments": (C.c_int32, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
+        "matchy_scan_result_segments": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_scan_result_to_ndjson_segments": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, C.POINTER(cp), C.POINTER(C.c_uint64), C.c_bool,
+                                                              C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_multi_scanner_submit_segments": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, vp, vp]),
+        "matchy_scanner_get_segment_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_scanner_set_tally": (None, [vp, C.c_bool]),
         "matchy_scanner_tally": (C.c_bool, [vp]),
         "matchy_scanner_reset_tally": (None, [vp]),
@@ -541,6 +555,71 @@ class ScanResult:
                             ip_data_offset=h.value if h.kind == 2 else 0, ids=ids, offs=offs))
         return out
 
+    def _segment_arrays(self):
+        """(segment_of_hit pointer, segment_of_ip4_hit pointer, table pointer, n_segments) of a segmented scan, else None"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        a, b, t, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        if lib().matchy_scan_result_segments(C.byref(self._raw), C.byref(a), C.byref(b), C.byref(t), C.byref(n)) != 0:
+            return None
+        return a.value or 0, b.value or 0, t.value or 0, int(n.value)
+
+    @property
+    def has_segments(self):
+        return self._segment_arrays() is not None
+
+    @property
+    def segments(self):
+        """[dict(start, len, hits, line_base, lines, lines_with_matches)] per segment (host memory for every fetch mode); None for a
+        scan without segments"""
+        sa = self._segment_arrays()
+        if sa is None:
+            return None
+        arr = C.cast(sa[2], C.POINTER(_ScanSegment))
+        return [dict(start=arr[i].start, len=arr[i].len, hits=arr[i].hits, line_base=arr[i].line_base, lines=arr[i].lines,
+                     lines_with_matches=arr[i].lines_with_matches) for i in range(sa[3])]
+
+    def _segment_list(self, ptr, n):
+        if n and self.on_device:
+            raise RuntimeError("the segment indices of this result are in device memory (fetch_mode 4): read them on the GPU (segment_of_ptr)")
+        if not ptr or not n:
+            return []
+        arr = C.cast(ptr, C.POINTER(C.c_uint32))
+        return [arr[i] for i in range(n)]
+
+    @property
+    def segment_of_ptr(self):
+        """address of the uint32 array parallel to the hit records (a device address when on_device), 0 when there is none"""
+        sa = self._segment_arrays()
+        return None if sa is None else sa[0]
+
+    @property
+    def segment_of(self):
+        """segment index per 16-byte hit record (hits() lists them behind the compact ones); None for a scan without segments"""
+        sa = self._segment_arrays()
+        return None if sa is None else self._segment_list(sa[0], self._raw.n_hits if self._raw.hits else 0)
+
+    @property
+    def segment_of_ip4(self):
+        """segment index per compact IPv4 record"""
+        sa = self._segment_arrays()
+        return None if sa is None else self._segment_list(sa[1], self._raw.n_ip4_hits if self._raw.ip4_hits else 0)
+
+    def ndjson_segments_text(self, text: bytes, sources, line_bases=None, with_input_line=False) -> bytes:
+        """ndjson_text with sources[segment] as the source of every record; line_bases (one per segment) adds "line_number" counted
+        inside the segment (matchy_scan_result_to_ndjson_segments)"""
+        L = lib()
+        out, n = C.c_void_p(), C.c_size_t()
+        src = (C.c_char_p * len(sources))(*[x.encode() if isinstance(x, str) else x for x in sources])
+        lb = None if line_bases is None else (C.c_uint64 * len(line_bases))(*line_bases)
+        rc = L.matchy_scan_result_to_ndjson_segments(self._scanner._h, C.byref(self._raw), text, src, lb, with_input_line, C.byref(out), C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scan_result_to_ndjson_segments failed ({rc}): " + last_error())
+        try:
+            return C.string_at(out.value, n.value)
+        finally:
+            L.matchy_free_string(out)
+
     def _line_arrays(self):
         """(lines pointer, ip4_lines pointer, lines_with_matches) of a result scanned with line context, else None"""
         if self._raw is None:
@@ -720,6 +799,19 @@ class Scanner:
         lib().matchy_scanner_get_line_timing(self._h, out)
         return dict(count=out[0], prefix=out[1], resolve=out[2])
 
+    def set_segments(self, starts):
+        """the NEXT scan's buffer is len(starts) segments that begin at these offsets (matchy_scanner_set_segments): the result then
+        has .segments / .segment_of / .segment_of_ip4. An empty list clears a pending table."""
+        arr = (C.c_uint32 * len(starts))(*starts)
+        rc = lib().matchy_scanner_set_segments(self._h, arr, len(starts))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_set_segments failed ({rc}): " + last_error())
+
+    def segment_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_segment_timing(self._h, out)
+        return dict(build=out[0], records=out[1], lines=out[2])
+
     def set_tally(self, on=True):
         """hit tally for the next scans: matches per distinct (item type, matched text), counted on the GPU across scans (off by default)"""
         lib().matchy_scanner_set_tally(self._h, bool(on))
@@ -811,6 +903,13 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit failed ({rc}): " + last_error())
 
+    def submit_segments_ptr(self, host_ptr: int, nbytes: int, starts, tag: int = 0):
+        """submit_ptr of a batch of len(starts) segments (matchy_multi_scanner_submit_segments); next() then carries the segment table"""
+        arr = (C.c_uint32 * len(starts))(*starts)
+        rc = lib().matchy_multi_scanner_submit_segments(self._h, host_ptr, nbytes, arr, len(starts), tag, None)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_segments failed ({rc}): " + last_error())
+
     def pending(self) -> int:
         return lib().matchy_multi_scanner_pending(self._h)
 
@@ -843,6 +942,10 @@ class MultiScanner:
             out["lines_with_matches"] = r.lines_with_matches
             if want_hits:
                 out["line_records"] = r.line_records
+        if r.has_segments:
+            out["segments"] = r.segments
+            if want_hits:
+                out["segment_of"] = r.segment_of
         r.close()
         return out
 

@@ -273,6 +273,29 @@ void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, ma
     }
 }
 
+static_assert(sizeof(SegmentRec) == sizeof(matchy_scan_segment_t) && offsetof(SegmentRec, lines_with_matches) == offsetof(matchy_scan_segment_t, lines_with_matches),
+              "k_seg_build writes matchy_scan_segment_t records directly");
+
+// Segments of a result: the table is copied into the result's internal block (created when the arrays are borrowed); the per-record
+// indices are device pointers, the scanner's pinned block, or an owned copy, like the hit arrays of the same result.
+void attach_segments(Scanner& sc, const ScanOutput& so, bool device, bool owned, matchy_scan_result_t* out) {
+    if (!so.has_segments) return;
+    if (!out->_internal) out->_internal = new ScanResultInternal();
+    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    in->has_segments = true;
+    const matchy_scan_segment_t* t = reinterpret_cast<const matchy_scan_segment_t*>(so.segments);
+    in->segments.assign(t, t + so.n_segments);
+    if (device) {
+        in->segment_of_hit = out->n_hits ? sc.device_segment_of() : nullptr;
+    } else if (owned) {
+        if (so.seg_of_fin) in->segment_of_own.assign(so.seg_of_fin, so.seg_of_fin + out->n_hits);   // one per record of the result (scan_host gathers them itself)
+        in->segment_of_hit = in->segment_of_own.empty() ? nullptr : in->segment_of_own.data();
+    } else {
+        in->segment_of_hit = so.seg_of_fin;
+        in->segment_of_ip4_hit = so.seg_of_c4;
+    }
+}
+
 }  // namespace
 
 int mxy::capi::default_device_of(const matchy_t* db) { return reinterpret_cast<const Db*>(db)->default_device; }
@@ -880,6 +903,28 @@ int32_t matchy_scan_result_lines(const matchy_scan_result_t* r, const matchy_sca
     return MATCHY_SUCCESS;
 }
 
+// segmented scans (Scanner::set_segments, segments.hip)
+int32_t matchy_scanner_set_segments(matchy_scanner_t* s, const uint32_t* starts, size_t n) {
+    if (!s) return MATCHY_ERROR_INVALID_PARAM;
+    try { reinterpret_cast<ScannerH*>(s)->sc->set_segments(starts, n); return MATCHY_SUCCESS; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_OUT_OF_MEMORY; }
+}
+int32_t matchy_scan_result_segments(const matchy_scan_result_t* r, const uint32_t** segment_of_hit, const uint32_t** segment_of_ip4_hit,
+                                    const matchy_scan_segment_t** segments, size_t* n_segments) {
+    if (!r) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_segments) { set_error("matchy_scan_result_segments: the result was produced by a scan without segments"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (segment_of_hit) *segment_of_hit = in->segment_of_hit;
+    if (segment_of_ip4_hit) *segment_of_ip4_hit = in->segment_of_ip4_hit;
+    if (segments) *segments = in->segments.data();
+    if (n_segments) *n_segments = in->segments.size();
+    return MATCHY_SUCCESS;
+}
+
+void matchy_scanner_get_segment_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->segment_timing(out);
+}
+
 // hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
 void matchy_scanner_set_tally(matchy_scanner_t* s, bool on) {
     if (!s) return;
@@ -932,8 +977,10 @@ int32_t matchy_scanner_scan(matchy_scanner_t* s, const uint8_t* data, size_t len
             in->lines_own.assign(reinterpret_cast<const matchy_scan_line_t*>(flines.data()), reinterpret_cast<const matchy_scan_line_t*>(flines.data()) + flines.size());
             in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
         }
+        attach_segments(*h->sc, so, false, true, out);
         return MATCHY_SUCCESS;
-    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
 
@@ -948,16 +995,19 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
         rq.lines = h->sc->line_context();
+        h->sc->arm_segments(len, st);
         h->sc->scan_device(rq, st);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
         attach_lines(*h->sc, so, false, sorted, out);
+        attach_segments(*h->sc, so, false, sorted, out);
         return MATCHY_SUCCESS;
-    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
 
@@ -973,10 +1023,12 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
         ScanRequest rq;   // not forked: several batches in flight (ScanRequest::fork)
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode); rq.lines = h->sc->line_context();
+        h->sc->arm_segments(len, reinterpret_cast<hipStream_t>(stream));
         h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
         return MATCHY_SUCCESS;
-    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    } catch (const ParamError& e) { set_error(e.what); return MATCHY_ERROR_INVALID_PARAM; }
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
 int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
@@ -990,13 +1042,15 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
         hipStream_t st = reinterpret_cast<hipStream_t>(h->pending_stream);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, h->pending_len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
         attach_lines(*h->sc, so, false, sorted, out);
+        attach_segments(*h->sc, so, false, sorted, out);
         return MATCHY_SUCCESS;
-    } catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
 
@@ -1059,9 +1113,17 @@ char* matchy_scan_hit_to_json(const matchy_scanner_t* s, const matchy_scan_resul
 // std::string temporaries and a strdup: the renderer was what bounded the command line with --format json (~6 GB/s of log against
 // 40+ with --format summary).
 // with_lines: "line_number" (and "input_line") from the result's line arrays go between "data" and "match_type" (keys stay sorted)
+// sources != NULL (matchy_scan_result_to_ndjson_segments): the result of a segmented scan; the source of a record is sources[its segment],
+// and with lines its number counts inside its segment: line_bases[s] + (line - segments[s].line_base) + 1
 static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, bool with_lines, uint64_t line_base,
-                                bool with_input_line, char** out, size_t* out_len) {
+                                bool with_input_line, char** out, size_t* out_len, const char* const* sources = nullptr, const uint64_t* line_bases = nullptr) {
     if (!s || !r || !out || !out_len || (!text && (r->n_hits || r->n_ip4_hits))) return MATCHY_ERROR_INVALID_PARAM;
+    const uint32_t* seg_of_hit = nullptr;
+    const uint32_t* seg_of_ip4 = nullptr;
+    const matchy_scan_segment_t* segs = nullptr;
+    size_t n_segs = 0;
+    if (sources && matchy_scan_result_segments(r, &seg_of_hit, &seg_of_ip4, &segs, &n_segs) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
+    if (sources && ((r->hits && r->n_hits && !seg_of_hit) || (r->ip4_hits && r->n_ip4_hits && !seg_of_ip4))) { set_error("matchy_scan_result_to_ndjson_segments: the result has no segment indices"); return MATCHY_ERROR_INVALID_PARAM; }
     const matchy_scan_line_t* lines = nullptr;
     const matchy_scan_line_t* ip4_lines = nullptr;
     if (with_lines && matchy_scan_result_lines(r, &lines, &ip4_lines, nullptr) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
@@ -1074,6 +1136,12 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
         sh->json_source_of = source ? source : "-";
         sh->json_source.clear();
         json_escape(sh->json_source_of, sh->json_source);
+    }
+    // the JSON text of the source of every segment that owns a record
+    std::vector<std::string> seg_source;
+    if (sources) {
+        seg_source.resize(n_segs);
+        for (size_t k = 0; k < n_segs; ++k) if (segs[k].hits) json_escape(sources[k] ? sources[k] : "-", seg_source[k]);
     }
     // One piece of the result per thread (large results only: a 256 MiB batch of a web-server log carries ~70 K matches, ~15 MB of text; one thread
     // renders ~9 M lines a second, which is less than two scanners on one GPU deliver). While pieces are rendered side by side the cache of
@@ -1121,6 +1189,8 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
             const matchy_scan_hit_t h = in_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - (r->hits ? r->n_hits : 0)]);
             const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
             const char* mt = (const char*)text + h.start;
+            const uint32_t seg = !sources ? 0u : in_hits ? seg_of_hit[i] : seg_of_ip4[i - (r->hits ? r->n_hits : 0)];
+            if (sources && seg >= n_segs) throw std::out_of_range("matchy_scan_result_to_ndjson_segments: a segment index lies outside the table");
             auto append_line_keys = [&] {
                 if (!with_lines) return;
                 const matchy_scan_line_t ln = in_hits ? lines[i] : ip4_lines[i - (r->hits ? r->n_hits : 0)];
@@ -1132,7 +1202,8 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
                     o.push_back(',');
                 }
                 o += "\"line_number\":";
-                const int k = snprintf(num64, sizeof(num64), "%llu", (unsigned long long)(line_base + ln.line + 1));
+                const uint64_t base = sources ? line_bases[seg] - segs[seg].line_base : line_base;
+                const int k = snprintf(num64, sizeof(num64), "%llu", (unsigned long long)(base + ln.line + 1));
                 o.append(num64, (size_t)k);
                 o.push_back(',');
             };
@@ -1168,7 +1239,7 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
                 append_uint((unsigned)h.n_ids);
             }
             o += ",\"source\":";
-            o += sh->json_source;
+            o += sources ? seg_source[seg] : sh->json_source;
             o += ",\"timestamp\":\"0.000\"}\n";
         }
     };
@@ -1232,6 +1303,12 @@ int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_resu
 int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, uint64_t line_base,
                                            bool with_input_line, char** out, size_t* out_len) {
     return result_to_ndjson(s, r, text, source, true, line_base, with_input_line, out, out_len);
+}
+
+int32_t matchy_scan_result_to_ndjson_segments(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* const* sources,
+                                              const uint64_t* line_bases, bool with_input_line, char** out, size_t* out_len) {
+    if (!sources) return MATCHY_ERROR_INVALID_PARAM;
+    return result_to_ndjson(s, r, text, nullptr, line_bases != nullptr, 0, with_input_line, out, out_len, sources, line_bases);
 }
 
 }  // extern "C"

@@ -26,6 +26,13 @@ struct ScanResultInternal {
     const matchy_scan_line_t* lines = nullptr;
     const matchy_scan_line_t* ip4_lines = nullptr;
     uint64_t lines_with_matches = 0;
+    // segmented scan (matchy_scan_result_segments): the table is always owned; the per-record indices follow the hit arrays of the
+    // same result like the line arrays do
+    bool has_segments = false;
+    std::vector<matchy_scan_segment_t> segments;
+    std::vector<uint32_t> segment_of_own;
+    const uint32_t* segment_of_hit = nullptr;
+    const uint32_t* segment_of_ip4_hit = nullptr;
 };
 
 // hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top

@@ -14,6 +14,8 @@
 // there is no CPU scan path. Flags that only tune the reference's CPU thread pool (-j, --readers, --cache-size, -p,
 // --debug-routing) are accepted and ignored; .gz inputs are decompressed on the host (zlib); -f/--follow polls the files.
 // --tally[=N] adds, behind the match records, {"count","item_type","matched_text","result"} per distinct matched value (tally.hip).
+// --pack-inputs reads consecutive small input files into shared batches (input_packer.h) and scans each as one batch of segments
+// (segments.hip): the output is byte for byte what it is without the flag.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -45,6 +47,7 @@
 #include "db_builder.h"
 #include "batch_reader.h"
 #include "db_image.h"
+#include "input_packer.h"
 
 using namespace mxy;
 
@@ -58,6 +61,7 @@ int usage() {
             "               [--line-numbers] [--input-line]   (\"line_number\" / \"input_line\" in every record, computed on the GPU)\n"
             "               [--tally[=N]]   (behind the matches: one JSON line per distinct matched value with its hit count, the N most frequent; default 20,\n"
             "                                0 = all; counted on the GPU; with --format summary nothing else is printed; not with --follow)\n"
+            "               [--pack-inputs]   (consecutive small files share a batch and are told apart on the GPU; same output; not with --follow)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -297,7 +301,9 @@ struct Totals {
 // are independent, the database is replicated, the host gathers the hit records and sums the counters; no collective).
 // `ptr` points into `own` (inputs that are read: stdin, .gz) or into a file mapping that outlives the batch
 struct Batch { size_t input = 0; Bytes own; const uint8_t* ptr = nullptr; size_t len = 0; bool mapped = false;
-               const void* reg = nullptr; };   // reg: page range of a mapped batch the reader pinned ahead of the scan (unpinned by the worker)
+               const void* reg = nullptr;   // reg: page range of a batch the reader pinned ahead of the scan (unpinned by the worker)
+               // --pack-inputs: the files of a pack, one segment each (empty: an ordinary batch of `input`), and the newlines the packer added
+               std::vector<PackedInput> pack; size_t appended = 0; };
 // what a batch contributes to the output: `text` / `text_len` is the buffer matchy_scan_result_to_ndjson returned (written to stdout as
 // it is and released by the printer: 200 bytes per match are not copied again on the way), `out` what --follow builds from it
 struct Done {
@@ -331,15 +337,27 @@ struct MatchPipeline {
     bool line_ctx = false, input_line = false;
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
 
+    // every input a batch carries: its own, or the files of a pack
+    template <class F> static void each_input(const Batch& b, F&& f) {
+        if (b.pack.empty()) f(b.input);
+        else for (const PackedInput& pi : b.pack) f(pi.input);
+    }
     // the batch goes to the library's queue; its Batch object travels as the tag and comes back with the result
     size_t submit(Batch&& b) {
         Batch* hb = new Batch(std::move(b));
         size_t seq;
         { std::lock_guard<std::mutex> lk(mu); seq = submitted++; }
-        if (matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg) != MATCHY_SUCCESS) {
+        int32_t rc;
+        if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
+        else {
+            std::vector<uint32_t> starts;
+            for (const PackedInput& pi : hb->pack) starts.push_back(pi.start);
+            rc = matchy_multi_scanner_submit_segments(ms, hb->ptr, hb->len, starts.data(), starts.size(), hb, hb->reg);
+        }
+        if (rc != MATCHY_SUCCESS) {
             // not queued (cannot happen for batches below 4 GiB): the printer never sees it
             fprintf(stderr, "[ERROR] batch of %zu bytes rejected: %s\n", hb->len, matchy_amd_last_error());
-            { std::lock_guard<std::mutex> lk(mu); rejected_inputs.push_back(hb->input); }   // its matches are missing: the input counts as failed
+            { std::lock_guard<std::mutex> lk(mu); each_input(*hb, [&](size_t i) { rejected_inputs.push_back(i); }); }   // its matches are missing: the inputs count as failed
             if (hb->reg) matchy_amd_host_unregister(hb->reg);
             delete hb;
         }
@@ -363,17 +381,27 @@ struct MatchPipeline {
         for (const Mapping& m : go) munmap(m.p, m.len);
     }
     // what one batch contributes to the output: counters, and (json) its matches rendered — on the worker thread that scanned it
-    void render(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, size_t len, size_t input, Done& d) {
+    void render(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, size_t len, const Batch& b, Done& d) {
+        const size_t input = b.input;
         d.input = input;
         Totals& t = d.t;
-        t.lines += r.lines; t.candidates += r.candidates; t.bytes += len; t.matches += r.n_hits;
+        // a pack: the newlines the packer appended are not the inputs'
+        t.lines += r.lines - b.appended; t.candidates += r.candidates; t.bytes += len - b.appended; t.matches += r.n_hits;
+        if (line_ctx && !b.pack.empty()) {   // per segment, from the table the GPU filled
+            const matchy_scan_segment_t* segs = nullptr;
+            size_t n_segs = 0;
+            if (matchy_scan_result_segments(&r, nullptr, nullptr, &segs, &n_segs) == MATCHY_SUCCESS) for (size_t k = 0; k < n_segs; ++k) t.lines_with_matches += segs[k].lines_with_matches;
+            else { fprintf(stderr, "[ERROR] no segments in the scan result of a pack: %s\n", matchy_amd_last_error()); d.ok = false; }
+            return;
+        }
         if (line_ctx) {
             uint64_t lwm = 0;
             if (matchy_scan_result_lines(&r, nullptr, nullptr, &lwm) == MATCHY_SUCCESS) t.lines_with_matches += lwm;
             else { fprintf(stderr, "[ERROR] no line context in a scan result: %s\n", matchy_amd_last_error()); d.ok = false; }
             return;   // the records: render_numbered, in sequence order
         }
-        // lines with matches: hits come sorted by offset; a new line starts when a '\n' lies between two hit starts
+        // lines with matches: hits come sorted by offset; a new line starts when a '\n' lies between two hit starts (and a '\n' lies
+        // between any two segments of a pack)
         const std::string& source = sources[input];
         size_t prev = (size_t)-1;
         for (size_t i = 0; i < r.n_hits; ++i) {
@@ -384,22 +412,38 @@ struct MatchPipeline {
         if (json && r.n_hits) {   // every match of the batch in one call (the scanner caches the rendered data payloads)
             char* text = nullptr;
             size_t n = 0;
-            if (matchy_scan_result_to_ndjson(sc, &r, data, source.c_str(), &text, &n) == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
+            int32_t rc;
+            if (b.pack.empty()) rc = matchy_scan_result_to_ndjson(sc, &r, data, source.c_str(), &text, &n);
+            else { const std::vector<const char*> src = pack_sources(b); rc = matchy_scan_result_to_ndjson_segments(sc, &r, data, src.data(), nullptr, false, &text, &n); }
+            if (rc == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
             else { fprintf(stderr, "[ERROR] rendering failed: %s\n", matchy_amd_last_error()); d.ok = false; }
         }
     }
+    std::vector<const char*> pack_sources(const Batch& b) const {
+        std::vector<const char*> src;
+        for (const PackedInput& pi : b.pack) src.push_back(sources[pi.input].c_str());
+        return src;
+    }
     // the records of a batch of a scan with line context; `base` = lines of its input in front of it
-    void render_numbered(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, size_t input, unsigned long long base, Done& d) {
+    // (a packed input is whole: its lines count from zero)
+    void render_numbered(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, const Batch& b, unsigned long long base, Done& d) {
         if (!json || !r.n_hits || !d.ok) return;
         char* text = nullptr;
         size_t n = 0;
-        if (matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[input].c_str(), base, input_line, &text, &n) == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
+        int32_t rc;
+        if (b.pack.empty()) rc = matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[b.input].c_str(), base, input_line, &text, &n);
+        else {
+            const std::vector<const char*> src = pack_sources(b);
+            const std::vector<uint64_t> bases(b.pack.size(), 0);
+            rc = matchy_scan_result_to_ndjson_segments(sc, &r, data, src.data(), bases.data(), input_line, &text, &n);
+        }
+        if (rc == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
         else { fprintf(stderr, "[ERROR] rendering failed: %s\n", matchy_amd_last_error()); d.ok = false; }
     }
     static void* batch_hook(void* user, size_t, matchy_scanner_t* sc, const matchy_scan_result_t* r, const uint8_t* data, size_t len, void* tag) {
         MatchPipeline* pl = (MatchPipeline*)user;
         Done* d = new Done();
-        pl->render(sc, *r, data, len, ((const Batch*)tag)->input, *d);
+        pl->render(sc, *r, data, len, *(const Batch*)tag, *d);
         return d;
     }
     // scan one batch on the calling thread and render its matches (--follow: one scanner, batches as they appear)
@@ -413,9 +457,9 @@ struct MatchPipeline {
             d.ok = false;
             return;
         }
-        render(sc, r, b.ptr, b.len, b.input, d);
+        render(sc, r, b.ptr, b.len, b, d);
         if (line_ctx) {   // --follow: batches of an input come one after the other, the count continues across the polls
-            render_numbered(sc, r, b.ptr, b.input, line_base[b.input], d);
+            render_numbered(sc, r, b.ptr, b, line_base[b.input], d);
             line_base[b.input] += r.lines;
         }
         matchy_scan_result_free(&r);
@@ -435,13 +479,13 @@ struct MatchPipeline {
             Done* d = (Done*)b.payload;
             if (b.status != MATCHY_SUCCESS) {
                 fprintf(stderr, "[ERROR] scan failed: %s\n", matchy_amd_last_error());
-                input_failed[hb->input] = 1;
+                each_input(*hb, [&](size_t i) { input_failed[i] = 1; });
             } else if (d) {
                 if (line_ctx) {   // the worker's scanner renders here: with line context its hook renders nothing, so one thread at a time uses it
-                    render_numbered(matchy_multi_scanner_worker_scanner(ms, b.worker), b.result, b.data, hb->input, line_base[hb->input], *d);
-                    line_base[hb->input] += b.result.lines;
+                    render_numbered(matchy_multi_scanner_worker_scanner(ms, b.worker), b.result, b.data, *hb, line_base[hb->input], *d);
+                    if (hb->pack.empty()) line_base[hb->input] += b.result.lines;
                 }
-                if (!d->ok) input_failed[hb->input] = 1;   // rendering failed in the batch hook: the batch's matches are missing, exit status says so
+                if (!d->ok) each_input(*hb, [&](size_t i) { input_failed[i] = 1; });   // rendering failed: the batch's matches are missing, exit status says so
                 if (d->text_len) write_all_stdout(d->text, d->text_len);
                 total.lines += d->t.lines; total.lines_with_matches += d->t.lines_with_matches; total.matches += d->t.matches;
                 total.candidates += d->t.candidates; total.bytes += d->t.bytes;
@@ -598,7 +642,7 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -627,6 +671,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "-f" || a == "--follow") follow = true;
         else if (a == "--line-numbers") line_numbers = true;
         else if (a == "--input-line") input_line = true;
+        else if (a == "--pack-inputs") pack = true;
         else if (a == "--tally") tally = true;
         else if (a.compare(0, 8, "--tally=") == 0) {
             const std::string n = a.substr(8);
@@ -639,6 +684,7 @@ int cmd_match(int argc, char** argv) {
     if (pos.size() < 2) return usage();
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
     if (follow && tally) { fprintf(stderr, "Error: --tally is not supported with --follow (the report is printed after the last batch)\n"); return 1; }
+    if (follow && pack) { fprintf(stderr, "Error: --pack-inputs is not supported with --follow (a followed file grows; a packed one is whole)\n"); return 1; }
     if (follow && stats) fprintf(stderr, "[INFO] Processing existing file content...\n");
     if (follow) for (size_t i = 1; i < pos.size(); ++i) if (pos[i] == "-") { fprintf(stderr, "Error: --follow mode not supported with stdin\n"); return 1; }
     // device list: one worker (scanner) per entry; an entry may repeat (two scanners on one GPU overlap one batch's
@@ -739,8 +785,24 @@ int cmd_match(int argc, char** argv) {
     pl.line_base.assign(paths.size(), 0);
     std::thread printer([&] { pl.printer(t, input_failed); });
     pl.consumed.assign(paths.size(), -1);
-    for (size_t i = 0; i < paths.size(); ++i)
-        if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1;
+    PackStats packed;
+    if (pack) {
+        // runs of small files go out as packs, everything else the way it goes without the flag, in the order of the command line
+        packed = pack_inputs(
+            paths, batch_bytes,
+            [&](InputPack&& p) {
+                Batch b;
+                b.input = p.inputs[0].input; b.ptr = p.data.get(); b.len = p.len; b.own = std::move(p.data);
+                b.pack = std::move(p.inputs); b.appended = p.appended;
+                b.reg = prefault_and_pin(b.ptr, b.len);
+                pl.submit(std::move(b));
+            },
+            [&](size_t i) { if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1; },
+            [&](size_t i, int err) { fprintf(stderr, "[ERROR] Failed to process %s: %s\n", paths[i].c_str(), strerror(err)); read_failed[i] = 1; });
+    } else {
+        for (size_t i = 0; i < paths.size(); ++i)
+            if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1;
+    }
     pl.reader_done = true;
     printer.join();
     for (size_t i = 0; i < paths.size(); ++i) if (read_failed[i]) input_failed[i] = 1;
@@ -806,6 +868,7 @@ int cmd_match(int argc, char** argv) {
         for (int d : devs) { if (!dl.empty()) dl += ","; dl += std::to_string(d); }
         fprintf(stderr, "\n[INFO] === Devices ===\n[INFO] HIP devices: %s (%zu scanner%s, batches of %zu MiB)\n", dl.c_str(), n_scanners,
                 n_scanners == 1 ? "" : "s", batch_bytes >> 20);
+        if (pack) fprintf(stderr, "[INFO] Packed %zu inputs into %zu batches (%llu bytes of input in all)\n", packed.inputs, packed.packs, t.bytes);
     }
     matchy_multi_scanner_free(ms);
     matchy_close(db);

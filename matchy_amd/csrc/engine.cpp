@@ -505,6 +505,8 @@ Scanner::~Scanner() {
     if (host_slices_) (void)hipHostFree(host_slices_);
     if (pinned_lines_) (void)hipHostFree(pinned_lines_);
     for (auto& e : ev_line_) if (e) (void)hipEventDestroy(e);
+    if (pinned_seg_) (void)hipHostFree(pinned_seg_);
+    for (auto& e : ev_seg_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_anchor_) if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_misc_) if (e) (void)hipEventDestroy(e);
@@ -1349,6 +1351,9 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
                     tally_->last_claim_ms(), tally_->last_publish_ms(), tally_->last_ms());
         }
     }
+    // segmented scan: the records are attributed to the caller's segments where they lie, behind the line context it builds on
+    out.has_segments = false; out.segments = nullptr; out.n_segments = 0; out.seg_of_fin = nullptr; out.seg_of_c4 = nullptr;
+    if (seg_active_ && last_.lookup && !single_) resolve_segments(out, dev_recs, hit_mode == HITS_FINAL, stream);
     // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
     if (dedup) {
         distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);
@@ -1360,6 +1365,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         out.lines_with_matches = *reinterpret_cast<const uint32_t*>(pinned_lines_);
         if (profile_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&line_ms_[k], ev_line_[k], ev_line_[k + 1]));
     }
+    if (out.has_segments) finish_segments(out);
     if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
     // drop the padding slots of partially filled chunks
     if (get_raw) {
@@ -1393,6 +1399,7 @@ void Scanner::resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host,
     size_t slots = 1024;
     while (slots < 2 * n) slots <<= 1;
     if (line_set_.n < slots) line_set_.alloc(slots);
+    line_set_slots_ = n ? slots : 0;
     const size_t head = sizeof(LineCounters), want = head + (to_host ? n * sizeof(LineRec) : 0);
     if (pinned_lines_bytes_ < want) {
         if (pinned_lines_) (void)hipHostFree(pinned_lines_);
@@ -1420,6 +1427,97 @@ void Scanner::resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host,
         out.c4_lines = n_c4 ? (const LineRec*)(pb + head) + n_fin : nullptr;
     }
     out.has_lines = true;
+}
+
+// Segmented scans (segments.hip). The table is the caller's until arm_segments() takes it for one scan.
+void Scanner::set_segments(const uint32_t* starts, size_t n) {
+    if (!starts || !n) { seg_pending_.clear(); return; }
+    seg_pending_.assign(starts, starts + n);
+}
+
+void Scanner::arm_segments(size_t len, hipStream_t stream, bool upload) {
+    seg_active_ = false;
+    seg_index_base_ = 0;
+    seg_starts_.clear();
+    seg_starts_.swap(seg_pending_);   // consumed whether the scan succeeds or not
+    if (seg_starts_.empty()) return;
+    std::string bad;
+    if (seg_starts_.size() > 0x7FFFFFFFull) bad = "segments: too many segments";
+    else if (seg_starts_[0] != 0) bad = "segments: starts[0] must be 0";
+    for (size_t s = 0; bad.empty() && s < seg_starts_.size(); ++s) {
+        if (seg_starts_[s] > len) bad = "segments: start of segment " + std::to_string(s) + " lies behind the end of the buffer";
+        else if (s && seg_starts_[s] < seg_starts_[s - 1]) bad = "segments: start of segment " + std::to_string(s) + " lies in front of its predecessor's";
+    }
+    if (!bad.empty()) { seg_starts_.clear(); throw ParamError{bad}; }
+    seg_active_ = true;
+    if (upload) upload_segments(stream);
+}
+
+// The table of the scan about to be launched goes to the device at submit, in front of the scan's kernels: the copy of a pageable
+// vector is staged by the runtime, and behind the scan it would sit on the critical path of fetch().
+void Scanner::upload_segments(hipStream_t stream) {
+    MXY_HIP(hipSetDevice(ddb_->device));
+    const size_t n = seg_starts_.size();
+    if (seg_starts_dev_.n < n) {
+        seg_starts_dev_.alloc(grown((uint32_t)n)); seg_line_base_.alloc(seg_starts_dev_.n);
+        seg_table_.alloc(sizeof(SegHeader) + seg_starts_dev_.n * sizeof(SegmentRec));
+    }
+    MXY_HIP(hipMemcpyAsync(seg_starts_dev_.p, seg_starts_.data(), n * 4, hipMemcpyHostToDevice, stream));
+}
+
+// Segments of the last scan: runs once per fetch behind the regrow loop, the spill pass, the sort and resolve_lines (whose prefix array
+// and distinct-line set it reads), over the records in the order the caller gets them. to_host: the segment indices come back into
+// pinned memory like the hit records; otherwise they stay on the device and only header + table cross the bus, in one copy.
+void Scanner::resolve_segments(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream) {
+    const ScanCounters& c = host_counters_;
+    const uint32_t n_fin = c.n_final, n_c4 = compact_ ? c.n_c4 : 0u, n = (uint32_t)seg_starts_.size();
+    const size_t n_recs = (size_t)n_fin + n_c4;
+    if (!seg_sample_.p) seg_sample_.alloc(SEG_SAMPLES);
+    if (seg_of_fin_.n < n_fin) seg_of_fin_.alloc(grown(n_fin));
+    if (seg_of_c4_.n < n_c4) seg_of_c4_.alloc(grown(n_c4));
+    const size_t head = sizeof(SegHeader) + (size_t)n * sizeof(SegmentRec), want = head + (to_host ? n_recs * 4 : 0);
+    if (pinned_seg_bytes_ < want) {
+        if (pinned_seg_) (void)hipHostFree(pinned_seg_);
+        pinned_seg_ = nullptr;
+        pinned_seg_bytes_ = want + want / 4 + (1 << 16);
+        MXY_HIP(hipHostMalloc(&pinned_seg_, pinned_seg_bytes_, hipHostMallocDefault));
+    }
+    if (profile_) {
+        for (auto& e : ev_seg_) if (!e) MXY_HIP(hipEventCreate(&e));
+        MXY_HIP(hipEventRecord(ev_seg_[0], stream));
+    }
+    SegHeader* hdr = reinterpret_cast<SegHeader*>(seg_table_.p);
+    SegmentRec* table = reinterpret_cast<SegmentRec*>(seg_table_.p + sizeof(SegHeader));
+    MXY_HIP(segments_build(last_.ptr, last_.len, seg_starts_dev_.p, n, out.has_lines ? line_prefix_.p : nullptr, hdr, table, seg_line_base_.p, seg_sample_.p, stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[1], stream));
+    MXY_HIP(segments_attribute(recs, sizeof(FinalHit), n_fin, last_.len, seg_starts_dev_.p, n, seg_sample_.p, seg_of_fin_.p, table, stream));
+    MXY_HIP(segments_attribute(c4_.p, sizeof(uint2), n_c4, last_.len, seg_starts_dev_.p, n, seg_sample_.p, seg_of_c4_.p, table, stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[2], stream));
+    if (out.has_lines && line_set_slots_) MXY_HIP(segments_count_lines(line_set_.p, (uint32_t)line_set_slots_, seg_line_base_.p, n, table, stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[3], stream));
+    uint8_t* pb = (uint8_t*)pinned_seg_;
+    MXY_HIP(hipMemcpyAsync(pb, seg_table_.p, head, hipMemcpyDeviceToHost, stream));
+    if (to_host) {
+        if (n_fin) MXY_HIP(hipMemcpyAsync(pb + head, seg_of_fin_.p, (size_t)n_fin * 4, hipMemcpyDeviceToHost, stream));
+        if (n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)n_fin * 4, seg_of_c4_.p, (size_t)n_c4 * 4, hipMemcpyDeviceToHost, stream));
+        out.seg_of_fin = n_fin ? (const uint32_t*)(pb + head) : nullptr;
+        out.seg_of_c4 = n_c4 ? (const uint32_t*)(pb + head) + n_fin : nullptr;
+    }
+    out.segments = reinterpret_cast<const SegmentRec*>(pb + sizeof(SegHeader));
+    out.n_segments = n;
+    out.has_segments = true;
+}
+
+// behind the wait of fetch(): the error word, and the lines of every segment from neighbouring line_base values and the batch's total
+void Scanner::finish_segments(ScanOutput& out) {
+    uint8_t* pb = (uint8_t*)pinned_seg_;
+    const SegHeader* hdr = reinterpret_cast<const SegHeader*>(pb);
+    SegmentRec* t = reinterpret_cast<SegmentRec*>(pb + sizeof(SegHeader));
+    const size_t n = out.n_segments;
+    if (profile_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&seg_ms_[k], ev_seg_[k], ev_seg_[k + 1]));
+    if (hdr->bad != SEG_NONE)
+        throw ParamError{"segments: segment " + std::to_string((size_t)hdr->bad + seg_index_base_) + " does not end in a newline (every non-empty segment in front of the last must)"};
+    if (out.has_lines) for (size_t s = 0; s < n; ++s) t[s].lines = (s + 1 < n ? t[s + 1].line_base : hdr->total_nl) - t[s].line_base;
 }
 
 size_t host_piece_bytes() {
@@ -1490,6 +1588,24 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     if (cand_bases) cand_bases->clear();
     if (fin) { fin->clear(); fin_ids->clear(); fin_offs->clear(); }
     if (fin_lines) fin_lines->clear();
+    // segmented scan: every piece gets the starts that intersect it, clamped and shifted; a piece ends at a line end, so the per-segment
+    // figures of the pieces add up, and the indices go back into the caller's table
+    std::vector<uint32_t> seg_all;
+    if (lookup) {
+        arm_segments(len, host_stream_, false);   // the whole table; every piece uploads its own below
+        if (seg_active_) seg_all.swap(seg_starts_);
+        seg_active_ = false;
+    }
+    struct SegOff { Scanner& s; ~SegOff() { s.seg_active_ = false; s.seg_index_base_ = 0; } } seg_off{*this};
+    if (!seg_all.empty()) {
+        out.seg_own.resize(seg_all.size());
+        for (size_t s = 0; s < seg_all.size(); ++s) {
+            SegmentRec r{};
+            r.start = seg_all[s];
+            r.len = (s + 1 < seg_all.size() ? seg_all[s + 1] : (uint32_t)len) - seg_all[s];
+            out.seg_own[s] = r;
+        }
+    }
     do {
         const size_t n = newline_cut(data, pos, len, MAXC) - pos;
         if (n > ((size_t)1 << 30)) throw HipError{"scan_host: a single line exceeds 1 GiB"};
@@ -1525,6 +1641,19 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         } else if (n) MXY_HIP(hipMemcpyAsync(staging_.p, src, n, hipMemcpyHostToDevice, host_stream_));
         ScanRequest rq;
         rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = line_ctx_ && lookup;
+        size_t seg_first = 0;
+        if (!seg_all.empty()) {
+            // the last segment that starts at or in front of the piece .. the last that starts inside it (the last piece: the last of all)
+            // (a run of empty segments that starts exactly at the piece's start belongs to this piece: from the first start equal to pos)
+            const size_t at_pos = (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)pos) - seg_all.begin());
+            seg_first = at_pos < seg_all.size() && seg_all[at_pos] == pos ? at_pos : at_pos - 1;
+            const size_t seg_last = pos + n >= len ? seg_all.size() - 1 : (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)(pos + n)) - seg_all.begin()) - 1;
+            seg_starts_.resize(seg_last - seg_first + 1);
+            for (size_t k = 0; k < seg_starts_.size(); ++k) seg_starts_[k] = std::max(seg_all[seg_first + k], (uint32_t)pos) - (uint32_t)pos;
+            seg_active_ = true;
+            seg_index_base_ = (uint32_t)seg_first;
+            upload_segments(host_stream_);
+        }
         scan_device(rq, host_stream_);
         ScanOutput part;
         const double t_launch = ms_since(th0);
@@ -1539,6 +1668,16 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             out.has_lines = true; out.lines_with_matches += part.lines_with_matches;
             if (fin_lines && part.n_fin) append_shifted_lines(part.fin_lines, part.n_fin, (uint32_t)pos, (uint32_t)out.lines, *fin_lines);
         }
+        if (part.has_segments) {
+            out.has_segments = true;
+            for (size_t k = 0; k < part.n_segments; ++k) {
+                SegmentRec& g = out.seg_own[seg_first + k];
+                const SegmentRec& p = part.segments[k];
+                g.hits += p.hits; g.lines += p.lines; g.lines_with_matches += p.lines_with_matches;
+                if (part.has_lines && seg_all[seg_first + k] >= pos) g.line_base = (uint32_t)out.lines + p.line_base;   // the segment starts in this piece
+            }
+            if (part.seg_of_fin) for (size_t i = 0; i < part.n_fin; ++i) out.seg_of_own.push_back(part.seg_of_fin[i] + (uint32_t)seg_first);
+        }
         out.lines += part.lines; out.n_cand += part.n_cand; out.n_hits += part.n_hits;
         for (int t = 0; t < IT_COUNT; ++t) out.by_type[t] += part.by_type[t];
         if (fin && part.n_fin) append_shifted(part.fin, part.n_fin, part.fin_ids, part.fin_offs, part.n_fin_ids, (uint32_t)pos, *fin, *fin_ids, *fin_offs);
@@ -1546,6 +1685,10 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         pos += n;
     } while (pos < len);
     out.cands.swap(all_cands);
+    if (out.has_segments) {
+        out.segments = out.seg_own.data(); out.n_segments = out.seg_own.size();
+        out.seg_of_fin = out.seg_of_own.empty() ? nullptr : out.seg_of_own.data();
+    }
 }
 
 namespace pins {

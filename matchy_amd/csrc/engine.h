@@ -10,6 +10,7 @@
 #include "db_image.h"
 #include "line_index.h"
 #include "scan_types.h"
+#include "segments.h"
 
 namespace mxy {
 
@@ -35,6 +36,8 @@ class HitTally;      // tally.h
 struct TallyEntry;
 
 struct HipError { std::string what; };
+// what the caller handed in cannot be scanned (a segment table that breaks its rules): nothing is wrong with the device or the scanner
+struct ParamError { std::string what; };
 #define MXY_HIP(expr)                                                                                   \
     do {                                                                                                \
         hipError_t _e = (expr);                                                                         \
@@ -121,6 +124,16 @@ struct ScanOutput {
     const LineRec* fin_lines = nullptr;
     const LineRec* c4_lines = nullptr;
     uint64_t lines_with_matches = 0;
+    // segmented scan (Scanner::set_segments): the table, and one segment index per entry of fin / c4. A scan_device fetch BORROWS them
+    // like fin (the indices stay on the device unless HITS_FINAL: Scanner::device_segment_of); scan_host owns them in seg_own / seg_of_own,
+    // with indices and line_base in the caller's table and buffer
+    bool has_segments = false;
+    const SegmentRec* segments = nullptr;
+    size_t n_segments = 0;
+    const uint32_t* seg_of_fin = nullptr;
+    const uint32_t* seg_of_c4 = nullptr;
+    std::vector<SegmentRec> seg_own;
+    std::vector<uint32_t> seg_of_own;
 };
 
 // Process-wide registry of the host ranges this library pinned (hipHostRegister): the caller's (matchy_amd_host_register, kept until
@@ -211,6 +224,18 @@ public:
     const LineRec* device_c4_lines() const { return line_c4_.p; }
     // with set_profile: milliseconds of the streaming count kernel, of the prefix sum, and of resolve + distinct set of the last fetch
     void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = line_ms_[k]; }
+    // Segmented scans (segments.hip): `starts` (copied) describes the buffer of the NEXT lookup scan as n segments — starts[0] == 0,
+    // non-decreasing, every start <= the scan's length, every non-empty segment in front of the last ends in '\n'. n == 0 or null
+    // clears a pending table. arm_segments(len) is what the entries of a lookup scan call before scan_device: it consumes the pending
+    // table (none: the scan has no segments), checks it against `len`, throws ParamError for a bad one and queues its copy to the device
+    // on `stream` in front of the scan. scan_host arms itself.
+    // fetch() then attributes the records on the device and throws ParamError when a segment breaks the newline rule.
+    void set_segments(const uint32_t* starts, size_t n);
+    void arm_segments(size_t len, hipStream_t stream, bool upload = true);   // upload false: scan_host, which uploads piece by piece
+    const uint32_t* device_segment_of() const { return seg_of_fin_.p; }
+    const uint32_t* device_segment_of_c4() const { return seg_of_c4_.p; }
+    // with set_profile: milliseconds of the segment pass, the record passes and the lines-with-matches pass of the last fetch
+    void segment_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = seg_ms_[k]; }
     // Distinct candidate texts (distinct.hip), for extractor handles: while on, a fetch with want_cands returns only the candidates whose
     // text this scanner has not returned since it was created or reset — the set lives in device memory across scans and pieces, and only
     // the survivors are copied back. Off (the default), nothing of it is allocated, launched or copied.
@@ -339,6 +364,22 @@ private:
     hipEvent_t ev_line_[4] = {nullptr, nullptr, nullptr, nullptr};
     float line_ms_[3] = {0, 0, 0};
     void resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
+    size_t line_set_slots_ = 0;                // slots of line_set_ the last resolve_lines used (0: it had no records)
+    // segmented scans (segments.hip), grown on demand and reused between scans like the line buffers: the pending table and the one of
+    // the scan in flight, its copy on the device, header + table in one block, line_base per segment, the sample table, one segment
+    // index per final / compact record, and the pinned block header, table and (HITS_FINAL) the indices come back in
+    std::vector<uint32_t> seg_pending_, seg_starts_;
+    bool seg_active_ = false;
+    uint32_t seg_index_base_ = 0;              // scan_host: the caller's index of the first segment of the piece in flight
+    DevBuf<uint32_t> seg_starts_dev_, seg_line_base_, seg_sample_, seg_of_fin_, seg_of_c4_;
+    DevBuf<uint8_t> seg_table_;
+    void* pinned_seg_ = nullptr;
+    size_t pinned_seg_bytes_ = 0;
+    hipEvent_t ev_seg_[4] = {nullptr, nullptr, nullptr, nullptr};
+    float seg_ms_[3] = {0, 0, 0};
+    void upload_segments(hipStream_t stream);   // seg_starts_ to the device, queued in front of the scan
+    void resolve_segments(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
+    void finish_segments(ScanOutput& out);
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
     bool tally_on_ = false;

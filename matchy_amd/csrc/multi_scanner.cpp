@@ -28,7 +28,7 @@ using namespace mxy;
 using namespace mxy::capi;
 
 namespace {
-struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; };   // node: NUMA node the bytes live on, -1 = anywhere
+struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments)
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
     const matchy_t* db = nullptr;
@@ -75,7 +75,7 @@ struct MultiScanner {
                 // with nothing of its own takes the oldest batch of another node rather than idling
                 auto it = q.begin();
                 for (auto k = q.begin(); k != q.end(); ++k) if (k->node < 0 || k->node == worker_node[w]) { it = k; break; }
-                j = *it;
+                j = std::move(*it);
                 q.erase(it);
                 cv_space.notify_one();
                 want_lines = line_ctx;
@@ -86,10 +86,11 @@ struct MultiScanner {
             if (!scanners[w]) scanners[w] = matchy_scanner_create(db, flags, devices[w]);
             std::string err;
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
-            else if (j.len) {
+            else if (j.len || !j.starts.empty()) {   // an empty batch with a table is scanned too: its result carries the table
                 matchy_scanner_set_line_context(scanners[w], want_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
-                d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
+                if (!j.starts.empty()) d.status = matchy_scanner_set_segments(scanners[w], j.starts.data(), j.starts.size());
+                if (d.status == MATCHY_SUCCESS) d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
             if (d.status == MATCHY_SUCCESS && hook) d.payload = hook(hook_user, w, scanners[w], &d.res, j.data, j.len, j.tag);
@@ -231,7 +232,18 @@ int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t* h, const uint8_
     // blocks while the job queue is full OR max_inflight batches are out (someone has to call matchy_multi_scanner_next: a caller that
     // submits and gathers on ONE thread interleaves the two — matchy_multi_scanner_pending() tells it when a next() is due)
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node});
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}});
+    ms->cv_work.notify_one();
+    return MATCHY_SUCCESS;
+}
+int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, const uint32_t* starts, size_t n, void* tag,
+                                             const void* pinned_range) {
+    if (!h || (!data && len) || len > 0xFFFFFFFFull || (!starts && n)) return MATCHY_ERROR_INVALID_PARAM;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::vector<uint32_t> table(starts, starts + n);   // copied in front of the lock
+    std::unique_lock<std::mutex> lk(ms->mu);
+    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table)});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }

@@ -1,0 +1,209 @@
+// Segmented scans, on the GPU: the caller describes a batch as a sequence of newline-terminated segments (the files of a pack), the scan
+// runs once as for any batch, and the passes here attribute its records to the segments where they lie:
+//   k_seg_build     one lane per segment: the newline rule (the byte in front of the next start of a non-empty segment that is not the
+//                   last must be '\n'; the lowest offending index goes into an error word with atomicMin), the segment's entry of the
+//                   table, with line context its line_base (prefix of the tile of its start + the '\n' bytes of that tile in front of
+//                   it, the SWAR test of line_index.hip), and every stride-th start into the sample table
+//   k_seg_records   one lane per record: the last segment whose start is <= the record's start, by an upper bound in two levels — the
+//                   sample table in LDS, then the <= stride starts behind the sample in global memory — and the segment's hit count
+//   k_seg_lines     line context: one lane per slot of the distinct-line set; an occupied slot counts for the last segment whose
+//                   line_base is <= its line number
+// The two counting passes use the scheme of k_tally_claim (tally.hip), restated here: lanes of a wave with the same segment add once
+// (a bounded number of leader rounds), the adds go to a small per-workgroup aggregator in LDS, and one global add per occupied entry
+// flushes it — a batch whose hits sit in one large segment would otherwise put every wave on one counter line. No lane waits for
+// another, every loop has a fixed bound, nothing is stored without a bound test, and no load of log bytes reaches `len`.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "line_index.h"
+#include "segments.h"
+
+namespace mxy {
+
+namespace {
+
+constexpr uint32_t SEG_THREADS = 256;
+constexpr uint32_t SEG_ITEMS = 1024;          // records (slots) per workgroup at least, while the grid allows: what one flush of the aggregator covers
+constexpr uint32_t SEG_MAX_GRID = 2048;
+constexpr uint32_t SEG_AGG_BITS = 7, SEG_AGG_SLOTS = 1u << SEG_AGG_BITS, SEG_AGG_PROBES = 4;
+constexpr uint32_t SEG_LEADER_ROUNDS = 4;
+constexpr uint32_t SEG_WORDS = sizeof(SegmentRec) / 4;   // the counters of neighbouring segments lie this many words apart
+// LDS is handed out in 1280-byte granules: sample table + aggregator are four of them, the aggregator alone is padded to one
+constexpr uint32_t SEG_LDS_RECORDS = SEG_SAMPLES + 2 * SEG_AGG_SLOTS, SEG_LDS_LINES = 320;
+static_assert(SEG_LDS_RECORDS * 4 % 1280 == 0 && SEG_LDS_LINES * 4 % 1280 == 0 && SEG_LDS_LINES >= 2 * SEG_AGG_SLOTS, "whole LDS granules");
+
+// 0x80 in every byte of x that is '\n' (exact: no carry crosses a byte) — the test of line_index.hip
+__device__ __forceinline__ uint32_t nl_bytes(uint32_t x) {
+    const uint32_t v = x ^ 0x0A0A0A0Au;
+    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
+}
+
+// the last index i of [lo, hi) with a[i] <= x, given a[lo] <= x (a is non-decreasing): at most 32 turns
+template <class A>
+__device__ __forceinline__ uint32_t last_le(A a, uint32_t lo, uint32_t hi, uint32_t x) {
+    for (uint32_t turn = 0; turn < 32u && hi - lo > 1u; ++turn) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (a[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void k_seg_build(const uint8_t* __restrict__ data, uint32_t len, const uint32_t* __restrict__ starts, uint32_t n,
+                                                           const uint32_t* __restrict__ prefix, uint32_t n_tiles, SegHeader* __restrict__ hdr,
+                                                           SegmentRec* __restrict__ table, uint32_t* __restrict__ line_base, uint32_t* __restrict__ sample,
+                                                           uint32_t stride) {
+    const uint32_t s = blockIdx.x * SEG_THREADS + threadIdx.x;
+    if (s == 0) hdr->total_nl = prefix ? prefix[n_tiles] : 0u;
+    if (s >= n) return;
+    // the host has checked the table; the clamps keep every offset inside the batch whatever it holds
+    const uint32_t start = min(starts[s], len);
+    const uint32_t end = max(s + 1 < n ? min(starts[s + 1], len) : len, start);
+    if (s + 1 < n && end > start && data[end - 1] != (uint8_t)'\n') atomicMin(&hdr->bad, s);
+    uint32_t lb = 0;
+    if (prefix) {
+        const uint32_t tile = start / LINE_TILE;   // <= n_tiles: the prefix array has n_tiles + 1 entries
+        uint32_t off = tile * LINE_TILE, cnt = 0;  // `data` is 16-byte aligned and every byte in front of start lies inside the batch
+        for (; off + 16u <= start; off += 16u) {   // < LINE_TILE / 16 turns
+            const uint4 v = *reinterpret_cast<const uint4*>(data + off);
+            cnt += __popc(nl_bytes(v.x)) + __popc(nl_bytes(v.y)) + __popc(nl_bytes(v.z)) + __popc(nl_bytes(v.w));
+        }
+        for (; off + 4u <= start; off += 4u) cnt += __popc(nl_bytes(*reinterpret_cast<const uint32_t*>(data + off)));
+        for (; off < start; ++off) cnt += data[off] == (uint8_t)'\n' ? 1u : 0u;
+        lb = prefix[tile] + cnt;
+    }
+    uint4* row = reinterpret_cast<uint4*>(table + s);
+    row[0] = make_uint4(start, end - start, 0u, lb);
+    row[1] = make_uint4(0u, 0u, 0u, 0u);
+    line_base[s] = lb;
+    if (s % stride == 0 && s / stride < SEG_SAMPLES) sample[s / stride] = start;
+}
+
+// `add` for segment `seg` into the workgroup's aggregator; a key that finds no room within SEG_AGG_PROBES probes adds to the global word
+__device__ __forceinline__ void d_seg_add(uint32_t* keys, uint32_t* counts, uint32_t seg, uint32_t add, uint32_t* __restrict__ field) {
+    uint32_t h = (seg * 2654435761u) >> (32 - SEG_AGG_BITS);
+#pragma unroll
+    for (uint32_t t = 0; t < SEG_AGG_PROBES; ++t, h = (h + 1u) & (SEG_AGG_SLOTS - 1u)) {
+        uint32_t k = keys[h];
+        if (k == SEG_NONE) k = atomicCAS(&keys[h], SEG_NONE, seg);
+        if (k == SEG_NONE || k == seg) { atomicAdd(&counts[h], add); return; }
+    }
+    atomicAdd(&field[(size_t)seg * SEG_WORDS], add);
+}
+
+// One count per lane with `valid` for its segment. Every lane of the wave calls this: the leader rounds are wave-wide. In each round
+// the lanes that share the segment of the first lane still uncounted add once through that lane; what is left after the rounds adds
+// one by one.
+__device__ __forceinline__ void d_seg_count(uint32_t* keys, uint32_t* counts, bool valid, uint32_t seg, uint32_t lane, uint32_t* __restrict__ field) {
+    unsigned long long left = __ballot(valid);
+    for (uint32_t r = 0; r < SEG_LEADER_ROUNDS && left; ++r) {
+        const uint32_t first = (uint32_t)__ffsll((long long)left) - 1u;
+        const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)seg, (int)first);
+        const unsigned long long same = __ballot(valid && seg == lead) & left;
+        if (lane == first) d_seg_add(keys, counts, lead, (uint32_t)__popcll(same), field);
+        left &= ~same;
+    }
+    if ((left >> lane) & 1ull) d_seg_add(keys, counts, seg, 1u, field);
+}
+
+__device__ __forceinline__ void d_agg_clear(uint32_t* keys, uint32_t* counts) {
+    for (uint32_t e = threadIdx.x; e < SEG_AGG_SLOTS; e += SEG_THREADS) { keys[e] = SEG_NONE; counts[e] = 0; }
+}
+__device__ __forceinline__ void d_agg_flush(const uint32_t* keys, const uint32_t* counts, uint32_t n, uint32_t* __restrict__ field) {
+    for (uint32_t e = threadIdx.x; e < SEG_AGG_SLOTS; e += SEG_THREADS) {
+        const uint32_t k = keys[e], c = counts[e];
+        if (k < n && c) atomicAdd(&field[(size_t)k * SEG_WORDS], c);
+    }
+}
+
+// STRIDE: bytes of a record (16: FinalHit, 8: compact IPv4 record); both begin with the start offset. n_samples = seg_sample_count(n) and
+// stride = seg_sample_stride(n) as k_seg_build wrote the sample table; hits = &table[0].hits.
+template <uint32_t STRIDE>
+__global__ __launch_bounds__(SEG_THREADS) void k_seg_records(const uint8_t* __restrict__ recs, uint32_t n_recs, uint32_t len, const uint32_t* __restrict__ starts,
+                                                             uint32_t n, const uint32_t* __restrict__ sample, uint32_t n_samples, uint32_t stride,
+                                                             uint32_t* __restrict__ seg_of, uint32_t* __restrict__ hits) {
+    __shared__ uint32_t lds[SEG_LDS_RECORDS];
+    uint32_t* smp = lds;
+    uint32_t* keys = lds + SEG_SAMPLES;
+    uint32_t* counts = keys + SEG_AGG_SLOTS;
+    for (uint32_t e = threadIdx.x; e < n_samples && e < SEG_SAMPLES; e += SEG_THREADS) smp[e] = sample[e];
+    d_agg_clear(keys, counts);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * SEG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * SEG_THREADS) >> 6;
+    // every lane of a wave takes every turn of this loop: the counting is wave-wide
+    for (uint32_t base = wave * 64u; base < n_recs; base += n_waves * 64u) {
+        const uint32_t idx = base + lane;
+        const bool valid = idx < n_recs;
+        uint32_t seg = 0;
+        if (valid) {
+            const uint32_t x = min(*reinterpret_cast<const uint32_t*>(recs + (size_t)idx * STRIDE), len);   // a record never starts behind the batch
+            const uint32_t j = last_le(smp, 0u, n_samples, x);        // smp[0] = starts[0] = 0 <= x
+            const uint32_t lo = j * stride;                           // starts[lo] = smp[j] <= x < smp[j + 1] = starts[lo + stride]
+            seg = last_le(starts, lo, min(lo + stride, n), x);        // ties: the last equal start, so an empty segment owns nothing
+            seg_of[idx] = seg;
+        }
+        d_seg_count(keys, counts, valid, seg, lane, hits);
+    }
+    __syncthreads();
+    d_agg_flush(keys, counts, n, hits);
+}
+
+// set: the distinct-line set of line_index_resolve; lwm = &table[0].lines_with_matches
+__global__ __launch_bounds__(SEG_THREADS) void k_seg_lines(const uint32_t* __restrict__ set, uint32_t set_slots, const uint32_t* __restrict__ line_base, uint32_t n,
+                                                           uint32_t* __restrict__ lwm) {
+    __shared__ uint32_t lds[SEG_LDS_LINES];
+    uint32_t* keys = lds;
+    uint32_t* counts = lds + SEG_AGG_SLOTS;
+    d_agg_clear(keys, counts);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * SEG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * SEG_THREADS) >> 6;
+    for (uint32_t base = wave * 64u; base < set_slots; base += n_waves * 64u) {
+        const uint32_t idx = base + lane;
+        const uint32_t line = idx < set_slots ? set[idx] : LINE_SET_EMPTY;
+        const bool valid = line != LINE_SET_EMPTY;
+        // line_base[0] = 0 <= line. A non-empty segment in front of the last ends in '\n', so equal neighbours are empty segments and
+        // an unterminated line can only belong to the last one: the last segment with line_base <= line is the line's segment
+        const uint32_t seg = valid ? last_le(line_base, 0u, n, line) : 0u;
+        d_seg_count(keys, counts, valid, seg, lane, lwm);
+    }
+    __syncthreads();
+    d_agg_flush(keys, counts, n, lwm);
+}
+
+uint32_t grid_for(uint32_t items) { return std::max<uint32_t>(1u, std::min<uint32_t>((items + SEG_ITEMS - 1) / SEG_ITEMS, SEG_MAX_GRID)); }
+
+}  // namespace
+
+hipError_t segments_build(const uint8_t* data, uint32_t len, const uint32_t* starts, uint32_t n, const uint32_t* prefix, SegHeader* hdr, SegmentRec* table,
+                          uint32_t* line_base, uint32_t* sample, hipStream_t stream) {
+    if (n == 0) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(hdr, 0xFF, sizeof(SegHeader), stream);   // bad = SEG_NONE
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_seg_build, dim3((n + SEG_THREADS - 1) / SEG_THREADS), dim3(SEG_THREADS), 0, stream, data, len, starts, n, prefix, line_tiles(len), hdr, table,
+                       line_base, sample, seg_sample_stride(n));
+    return hipGetLastError();
+}
+
+hipError_t segments_attribute(const void* recs, uint32_t stride, uint32_t n_recs, uint32_t len, const uint32_t* starts, uint32_t n, const uint32_t* sample,
+                              uint32_t* seg_of, SegmentRec* table, hipStream_t stream) {
+    if (n_recs == 0) return hipSuccess;
+    if (n == 0 || (stride != 16 && stride != 8)) return hipErrorInvalidValue;
+    if (stride == 16)
+        hipLaunchKernelGGL(k_seg_records<16>, dim3(grid_for(n_recs)), dim3(SEG_THREADS), 0, stream, (const uint8_t*)recs, n_recs, len, starts, n, sample,
+                           seg_sample_count(n), seg_sample_stride(n), seg_of, &table->hits);
+    else
+        hipLaunchKernelGGL(k_seg_records<8>, dim3(grid_for(n_recs)), dim3(SEG_THREADS), 0, stream, (const uint8_t*)recs, n_recs, len, starts, n, sample,
+                           seg_sample_count(n), seg_sample_stride(n), seg_of, &table->hits);
+    return hipGetLastError();
+}
+
+hipError_t segments_count_lines(const uint32_t* set, uint32_t set_slots, const uint32_t* line_base, uint32_t n, SegmentRec* table, hipStream_t stream) {
+    if (set_slots == 0) return hipSuccess;
+    if (n == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_seg_lines, dim3(grid_for(set_slots)), dim3(SEG_THREADS), 0, stream, set, set_slots, line_base, n, &table->lines_with_matches);
+    return hipGetLastError();
+}
+
+}  // namespace mxy
