@@ -14,6 +14,14 @@ constexpr uint32_t LINE_TILE = 1024;
 constexpr uint32_t LINE_SCAN_CHUNK = 2048;
 constexpr uint32_t LINE_SET_EMPTY = 0xFFFFFFFFu;   // free slot of the distinct-line set (line numbers stay below 2^31)
 
+// 0x80 in every byte of x that is '\n' (exact: no carry crosses a byte): the SWAR test of the '\n' counts, here and in segments.hip
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t nl_bytes(uint32_t x) {
+    const uint32_t v = x ^ 0x0A0A0A0Au;
+    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
+}
+#endif
+
 // One record per hit, bit-identical to matchy_scan_line_t (include/matchy_amd.h).
 struct LineRec { uint32_t line, line_start, line_end, reserved; };
 

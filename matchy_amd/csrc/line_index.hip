@@ -37,11 +37,6 @@ __device__ __forceinline__ uint4 load16(const uint8_t* __restrict__ data, uint32
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// 0x80 in every byte of x that is '\n' (exact: no carry crosses a byte)
-__device__ __forceinline__ uint32_t nl_bytes(uint32_t x) {
-    const uint32_t v = x ^ 0x0A0A0A0Au;
-    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
-}
 __device__ __forceinline__ uint32_t nl_count16(uint4 v) {
     return __popc(nl_bytes(v.x)) + __popc(nl_bytes(v.y)) + __popc(nl_bytes(v.z)) + __popc(nl_bytes(v.w));
 }

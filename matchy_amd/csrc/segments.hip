@@ -8,14 +8,14 @@
 //                   sample table in LDS, then the <= stride starts behind the sample in global memory — and the segment's hit count
 //   k_seg_lines     line context: one lane per slot of the distinct-line set; an occupied slot counts for the last segment whose
 //                   line_base is <= its line number
-// The two counting passes use the scheme of k_tally_claim (tally.hip), restated here: lanes of a wave with the same segment add once
-// (a bounded number of leader rounds), the adds go to a small per-workgroup aggregator in LDS, and one global add per occupied entry
-// flushes it — a batch whose hits sit in one large segment would otherwise put every wave on one counter line. No lane waits for
-// another, every loop has a fixed bound, nothing is stored without a bound test, and no load of log bytes reaches `len`.
+// The two counting passes count through the workgroup's LDS aggregator (lds_aggregator.h: segment -> count, four leader rounds) — a
+// batch whose hits sit in one large segment would otherwise put every wave on one counter line. No lane waits for another, every loop
+// has a fixed bound, nothing is stored without a bound test, and no load of log bytes reaches `len`.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "lds_aggregator.h"
 #include "line_index.h"
 #include "segments.h"
 
@@ -26,18 +26,13 @@ namespace {
 constexpr uint32_t SEG_THREADS = 256;
 constexpr uint32_t SEG_ITEMS = 1024;          // records (slots) per workgroup at least, while the grid allows: what one flush of the aggregator covers
 constexpr uint32_t SEG_MAX_GRID = 2048;
-constexpr uint32_t SEG_AGG_BITS = 7, SEG_AGG_SLOTS = 1u << SEG_AGG_BITS, SEG_AGG_PROBES = 4;
-constexpr uint32_t SEG_LEADER_ROUNDS = 4;
+using SegAgg = LdsAggregator<7, 4, 4>;
+constexpr uint32_t SEG_AGG_SLOTS = SegAgg::SLOTS;
+static_assert(SegAgg::NO_KEY == SEG_NONE, "no segment has the aggregator's free key");
 constexpr uint32_t SEG_WORDS = sizeof(SegmentRec) / 4;   // the counters of neighbouring segments lie this many words apart
 // LDS is handed out in 1280-byte granules: sample table + aggregator are four of them, the aggregator alone is padded to one
 constexpr uint32_t SEG_LDS_RECORDS = SEG_SAMPLES + 2 * SEG_AGG_SLOTS, SEG_LDS_LINES = 320;
 static_assert(SEG_LDS_RECORDS * 4 % 1280 == 0 && SEG_LDS_LINES * 4 % 1280 == 0 && SEG_LDS_LINES >= 2 * SEG_AGG_SLOTS, "whole LDS granules");
-
-// 0x80 in every byte of x that is '\n' (exact: no carry crosses a byte) — the test of line_index.hip
-__device__ __forceinline__ uint32_t nl_bytes(uint32_t x) {
-    const uint32_t v = x ^ 0x0A0A0A0Au;
-    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
-}
 
 // the last index i of [lo, hi) with a[i] <= x, given a[lo] <= x (a is non-decreasing): at most 32 turns
 template <class A>
@@ -79,41 +74,16 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_build(const uint8_t* __rest
     if (s % stride == 0 && s / stride < SEG_SAMPLES) sample[s / stride] = start;
 }
 
-// `add` for segment `seg` into the workgroup's aggregator; a key that finds no room within SEG_AGG_PROBES probes adds to the global word
-__device__ __forceinline__ void d_seg_add(uint32_t* keys, uint32_t* counts, uint32_t seg, uint32_t add, uint32_t* __restrict__ field) {
-    uint32_t h = (seg * 2654435761u) >> (32 - SEG_AGG_BITS);
-#pragma unroll
-    for (uint32_t t = 0; t < SEG_AGG_PROBES; ++t, h = (h + 1u) & (SEG_AGG_SLOTS - 1u)) {
-        uint32_t k = keys[h];
-        if (k == SEG_NONE) k = atomicCAS(&keys[h], SEG_NONE, seg);
-        if (k == SEG_NONE || k == seg) { atomicAdd(&counts[h], add); return; }
-    }
-    atomicAdd(&field[(size_t)seg * SEG_WORDS], add);
-}
-
-// One count per lane with `valid` for its segment. Every lane of the wave calls this: the leader rounds are wave-wide. In each round
-// the lanes that share the segment of the first lane still uncounted add once through that lane; what is left after the rounds adds
-// one by one.
+// One count per lane of `counting` for its segment into `field` of the table (&table[0].hits or .lines_with_matches). Every lane of
+// the wave calls this: the leader rounds are wave-wide. An add the aggregator has no room for goes to the global word.
 __device__ __forceinline__ void d_seg_count(uint32_t* keys, uint32_t* counts, bool valid, uint32_t seg, uint32_t lane, uint32_t* __restrict__ field) {
-    unsigned long long left = __ballot(valid);
-    for (uint32_t r = 0; r < SEG_LEADER_ROUNDS && left; ++r) {
-        const uint32_t first = (uint32_t)__ffsll((long long)left) - 1u;
-        const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)seg, (int)first);
-        const unsigned long long same = __ballot(valid && seg == lead) & left;
-        if (lane == first) d_seg_add(keys, counts, lead, (uint32_t)__popcll(same), field);
-        left &= ~same;
-    }
-    if ((left >> lane) & 1ull) d_seg_add(keys, counts, seg, 1u, field);
+    const uint32_t direct = SegAgg::count(keys, counts, __ballot(valid), seg, lane);
+    if (direct) atomicAdd(&field[(size_t)seg * SEG_WORDS], direct);
 }
-
-__device__ __forceinline__ void d_agg_clear(uint32_t* keys, uint32_t* counts) {
-    for (uint32_t e = threadIdx.x; e < SEG_AGG_SLOTS; e += SEG_THREADS) { keys[e] = SEG_NONE; counts[e] = 0; }
-}
-__device__ __forceinline__ void d_agg_flush(const uint32_t* keys, const uint32_t* counts, uint32_t n, uint32_t* __restrict__ field) {
-    for (uint32_t e = threadIdx.x; e < SEG_AGG_SLOTS; e += SEG_THREADS) {
-        const uint32_t k = keys[e], c = counts[e];
-        if (k < n && c) atomicAdd(&field[(size_t)k * SEG_WORDS], c);
-    }
+__device__ __forceinline__ void d_seg_flush(const uint32_t* keys, const uint32_t* counts, uint32_t n, uint32_t* __restrict__ field) {
+    SegAgg::flush(keys, counts, SEG_THREADS, [=](uint32_t k, uint32_t c) {
+        if (k < n) atomicAdd(&field[(size_t)k * SEG_WORDS], c);
+    });
 }
 
 // STRIDE: bytes of a record (16: FinalHit, 8: compact IPv4 record); both begin with the start offset. n_samples = seg_sample_count(n) and
@@ -127,7 +97,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_records(const uint8_t* __re
     uint32_t* keys = lds + SEG_SAMPLES;
     uint32_t* counts = keys + SEG_AGG_SLOTS;
     for (uint32_t e = threadIdx.x; e < n_samples && e < SEG_SAMPLES; e += SEG_THREADS) smp[e] = sample[e];
-    d_agg_clear(keys, counts);
+    SegAgg::clear(keys, counts, SEG_THREADS);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * SEG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * SEG_THREADS) >> 6;
@@ -146,7 +116,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_records(const uint8_t* __re
         d_seg_count(keys, counts, valid, seg, lane, hits);
     }
     __syncthreads();
-    d_agg_flush(keys, counts, n, hits);
+    d_seg_flush(keys, counts, n, hits);
 }
 
 // set: the distinct-line set of line_index_resolve; lwm = &table[0].lines_with_matches
@@ -155,7 +125,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_lines(const uint32_t* __res
     __shared__ uint32_t lds[SEG_LDS_LINES];
     uint32_t* keys = lds;
     uint32_t* counts = lds + SEG_AGG_SLOTS;
-    d_agg_clear(keys, counts);
+    SegAgg::clear(keys, counts, SEG_THREADS);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * SEG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * SEG_THREADS) >> 6;
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_lines(const uint32_t* __res
         d_seg_count(keys, counts, valid, seg, lane, lwm);
     }
     __syncthreads();
-    d_agg_flush(keys, counts, n, lwm);
+    d_seg_flush(keys, counts, n, lwm);
 }
 
 uint32_t grid_for(uint32_t items) { return std::max<uint32_t>(1u, std::min<uint32_t>((items + SEG_ITEMS - 1) / SEG_ITEMS, SEG_MAX_GRID)); }

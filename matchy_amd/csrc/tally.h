@@ -3,8 +3,7 @@
 // The key of an entry is (item type, matched text): the bytes log[start, start + len) of a final record and the type the extractor gave
 // them. The first part of this header is what the host and the kernels share (slot words, record decoding, the type-seeded hash) and the
 // host-only ordering / merge logic of the read-out: plain functions that tests/cpp/test_tally_layout.cpp runs on the host. The HitTally
-// class behind it drives the kernels. The helpers of the distinct-text set (distinct.h: hash mask, home slot, text word, table size,
-// pool alignment) are reused as they are.
+// class behind it drives the kernels. The table itself is a TextTable (text_table.h); distinct.h is here for the type rank of the order.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -19,23 +18,14 @@
 
 namespace mxy {
 
-// One slot of the open-addressing table, 32 bytes (one sector). `state` is the only word more than one lane writes with a
-// compare-and-swap inside a launch; `count` is only ever added to:
+// The `state` word of a slot (text_table.h), the only word more than one lane writes with a compare-and-swap inside a launch; the
+// slot's `aux` word is the count, which is only ever added to:
 //   TALLY_EMPTY (0)                 free: a table is cleared with zero bytes, which also makes every count 0
 //   index + 1 (bits 32.. clear)     claimed in the batch that is running by the record with that index; every record that joins has
 //                                   the same type and bytes, so it does not matter which one holds the slot
-//   TALLY_PUBLISHED | item type     the text is in the pool: `hash` and `text` are valid and never change again (until a reset)
-struct TallySlot {
-    unsigned long long state;
-    unsigned long long hash;    // masked, type-seeded hash the slot was placed with (rehash; filter in front of the byte compare)
-    unsigned long long text;    // distinct_text_word(): pool offset and length
-    unsigned long long count;   // hits of this value since creation or the last reset
-};
-static_assert(sizeof(TallySlot) == 32, "one slot per 32-byte sector");
-
+//   TALLY_PUBLISHED | item type     the text is in the pool
 constexpr unsigned long long TALLY_EMPTY = 0;
-constexpr unsigned long long TALLY_PUBLISHED = 1ull << 63;
-constexpr uint32_t TALLY_NO_SLOT = 0xFFFFFFFFu;
+constexpr unsigned long long TALLY_PUBLISHED = TEXT_PUBLISHED;
 constexpr uint64_t TALLY_MAX_RECORDS = 0xFFFFFFF0ull;   // records of one batch: index + 1 stays below 2^32
 
 MXY_HD bool tally_is_published(unsigned long long state) { return (state >> 63) != 0; }
@@ -49,25 +39,8 @@ MXY_HD uint32_t tally_c4_len(uint32_t packed) { return ((packed >> C4_DATA_BITS)
 // a record is used only when its text lies inside the batch
 MXY_HD bool tally_usable(uint32_t start, uint32_t n, uint32_t len) { return start < len && n <= len - start; }
 // The item type is part of the key: it seeds the hash (and is compared before the bytes). MATCHY_AMD_TALLY_HASH_BITS masks the result
-// like MATCHY_AMD_DISTINCT_HASH_BITS does (distinct_hash_mask): 0 bits make every (type, text) collide.
+// (text_hash_mask): 0 bits make every (type, text) collide.
 MXY_HD unsigned long long tally_hash(const uint8_t* text, uint32_t n, uint32_t item_type, unsigned long long mask) { return xxh64(text, n, item_type) & mask; }
-
-// The LDS aggregator of k_tally_claim: per workgroup a small open-addressing table slot index -> count. 256 entries of a key word and a
-// count word are 2 KiB, two of the 1280-byte granules LDS is handed out in: eight workgroups of 256 threads (all the wave slots of a CU
-// hold) take 20 KiB of its LDS. A key that finds no room within TALLY_AGG_PROBES probes adds straight to the global count.
-constexpr uint32_t TALLY_AGG_BITS = 8, TALLY_AGG_SLOTS = 1u << TALLY_AGG_BITS, TALLY_AGG_PROBES = 4;
-MXY_HD uint32_t tally_agg_home(uint32_t slot) { return (slot * 2654435761u) >> (32 - TALLY_AGG_BITS); }
-
-// The counters of the tally, each group in a 128-byte line of its own: the first lives as long as the set, the second is cleared per batch.
-struct TallyCounters {
-    alignas(128) unsigned long long pool_used;   // bytes of the pool handed out (may pass the capacity: demand of the publish pass)
-    alignas(128) unsigned long long n_counted;   // records of the running batch that found a slot (one add per wave)
-    uint32_t n_new;                              // slots published in the running batch
-    uint32_t n_pending;                          // winners the publish pass could not store (pool full)
-    uint32_t error;                              // bit 0: no free slot on a probe run, bit 1: the same in the rehash (the host keeps the table half empty)
-    uint32_t n_direct;                           // counts that went past the LDS aggregator straight to the global word
-    uint32_t n_export;                           // entries k_tally_export appended
-};
 
 // One published entry as k_tally_export writes it; `text` is the slot's text word, `slot` leads back to the table.
 struct TallyExport {
@@ -145,7 +118,7 @@ public:
     // (compact IPv4 records; null / 0 when compact records are not in effect), both in device memory like `log`. Synchronises `stream`.
     void add(const uint8_t* log, uint32_t len, const FinalHit* final, uint32_t n_final, const uint2* c4, uint32_t n_c4, hipStream_t stream);
     void reset();                                      // empties the tally, keeps the allocations
-    uint64_t distinct() const { return distinct_; }    // entries since creation or the last reset
+    uint64_t distinct() const { return table_.count(); }   // entries since creation or the last reset
     uint64_t matches() const { return matches_; }      // records counted (the sum of all counts)
     // The first `limit` entries in read-out order (0 = all): the counts of all entries come back, the texts of the chosen ones only.
     void top(size_t limit, std::vector<TallyEntry>& out, hipStream_t stream);
@@ -160,22 +133,9 @@ public:
     const Events& last_events() const { return events_; }
 
 private:
-    void ensure_counters();
-    void ensure_table(uint64_t entries, hipStream_t stream);
-    void grow_pool(unsigned long long want, hipStream_t stream);
-    TallySlot* slots_ = nullptr;
-    uint64_t n_slots_ = 0;
-    uint8_t* pool_ = nullptr;
-    unsigned long long pool_cap_ = 0;
-    TallyCounters* ctr_ = nullptr;        // device
-    TallyCounters* ctr_host_ = nullptr;   // pinned
-    uint32_t* slot_of_ = nullptr;         // per record of the running batch: its slot, or TALLY_NO_SLOT
-    size_t slot_of_n_ = 0;
-    uint64_t distinct_ = 0, matches_ = 0;
-    unsigned long long pool_used_ = 0;    // TallyCounters::pool_used behind the last batch
-    uint64_t init_slots_, init_pool_;
-    uint32_t hash_bits_;
-    bool poisoned_ = false, profile_ = false;
+    TextTable table_;
+    uint64_t matches_ = 0;
+    bool profile_ = false;
     hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};
     float last_ms_ = 0, claim_ms_ = 0, publish_ms_ = 0;
     Events events_;

@@ -1,4 +1,5 @@
-// distinct.h alone: the layout logic the host and the kernels of the distinct-text set share, on the host.
+// distinct.h alone: what is the distinct-text set's own of the layout the host and its kernels share (order key, type rank), on the
+// host. The table's layout is in test_text_table_layout.cpp.
 // Build: g++ -O1 -g -std=c++17 -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I matchy_amd/csrc
 //        tests/cpp/test_distinct_layout.cpp -o /tmp/test_distinct_layout      (no library: only the inline functions are used)
 #include <cstdio>
@@ -40,34 +41,6 @@ int main() {
         CHECK((a < b) == (ka < kb) && (a == b) == (ka == kb));
         CHECK(distinct_key_index(ka) == i1);
     }
-    // hash masking: n bits keep n bits; 0 bits make every hash equal; 64 and more keep all
-    CHECK(distinct_hash_mask(0) == 0 && distinct_hash_mask(4) == 15 && distinct_hash_mask(63) == (~0ull >> 1));
-    CHECK(distinct_hash_mask(64) == ~0ull && distinct_hash_mask(65) == ~0ull && distinct_hash_mask(1000) == ~0ull);
-    // home slot: inside the table, and the high half of the hash counts
-    for (uint32_t bits = 4; bits <= 31; ++bits) {
-        const uint32_t mask = (1u << bits) - 1;
-        for (int it = 0; it < 1000; ++it) CHECK(distinct_home(rng(), mask) <= mask);
-    }
-    CHECK(distinct_home(0x0000000100000000ull, 0xFFFF) != distinct_home(0, 0xFFFF));
-    // text word and pool padding
-    for (unsigned long long off : {0ull, 8ull, (1ull << 32) + 8, (1ull << 40) - 8})
-        for (uint32_t len : {0u, 1u, 7u, 8u, 253u, 0xFFFFFFu}) {
-            const unsigned long long w = distinct_text_word(off, len);
-            CHECK(distinct_text_off(w) == off && distinct_text_len(w) == len);
-        }
-    for (uint32_t len = 0; len < 100; ++len) {
-        const unsigned long long b = distinct_pool_bytes(len);
-        CHECK(b >= len && b < (unsigned long long)len + DISTINCT_POOL_ALIGN && b % DISTINCT_POOL_ALIGN == 0);
-    }
-    CHECK(distinct_pool_bytes(0xFFFFFFu) == 0x1000000ull);
-    // table size: a power of two, at least the floor, at most half full
-    for (unsigned long long entries : {0ull, 1ull, 7ull, 8ull, 9ull, 32768ull, 32769ull, 1ull << 29, (1ull << 30)})
-        for (unsigned long long floor_slots : {0ull, 1ull, 64ull, 65ull, 1ull << 16}) {
-            const unsigned long long s = distinct_slots_for(entries, floor_slots);
-            CHECK((s & (s - 1)) == 0 && s >= 16 && s >= floor_slots && s >= 2 * entries);
-            CHECK(s == 16 || s / 2 < floor_slots || s / 2 < 2 * entries);
-        }
-    static_assert(sizeof(DistinctCounters) == 256 && offsetof(DistinctCounters, n_out) == 128, "two 128-byte counter lines");
     printf("distinct layout: ok\n");
     return 0;
 }

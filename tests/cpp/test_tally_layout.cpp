@@ -30,9 +30,6 @@ int main() {
         const unsigned long long w = tally_published(t);
         CHECK(tally_is_published(w) && tally_state_type(w) == t && w != TALLY_EMPTY);
     }
-    static_assert(sizeof(TallyCounters) == 256 && offsetof(TallyCounters, n_counted) == 128, "two 128-byte counter lines");
-    static_assert(offsetof(TallySlot, count) == 24, "count is the last word of the slot");
-    static_assert(2 * sizeof(uint32_t) * TALLY_AGG_SLOTS <= 2 * 1280, "the aggregator fits two LDS granules");
 
     // compact-record length: c4_pack stores length - 7 in four bits; every length an IPv4 text can have comes back
     for (uint32_t len = 7; len <= 15; ++len)
@@ -47,14 +44,13 @@ int main() {
 
     // the hash is seeded with the type: same bytes, other type, other hash; masking keeps the low bits; 0 bits collide everything
     const uint8_t text[] = "9e107d9d372bb6826bd81d3542a419d6";
-    const unsigned long long all = distinct_hash_mask(64);
+    const unsigned long long all = text_hash_mask(64);
     CHECK(tally_hash(text, 32, IT_MD5, all) == xxh64(text, 32, IT_MD5));
     CHECK(tally_hash(text, 32, IT_MD5, all) != tally_hash(text, 32, IT_DOMAIN, all));
     CHECK(tally_hash(text, 32, IT_DOMAIN, all) == xxh64(text, 32, 0));
     CHECK(tally_hash(text, 31, IT_MD5, all) != tally_hash(text, 32, IT_MD5, all));
-    CHECK(tally_hash(text, 32, IT_MD5, distinct_hash_mask(4)) == (xxh64(text, 32, IT_MD5) & 15));
-    for (uint32_t t = 0; t < IT_COUNT; ++t) CHECK(tally_hash(text, 32, t, distinct_hash_mask(0)) == 0);
-    for (uint32_t s : {0u, 1u, 255u, 256u, 0x7FFFFFFFu, 0xFFFFFFFEu}) CHECK(tally_agg_home(s) < TALLY_AGG_SLOTS);
+    CHECK(tally_hash(text, 32, IT_MD5, text_hash_mask(4)) == (xxh64(text, 32, IT_MD5) & 15));
+    for (uint32_t t = 0; t < IT_COUNT; ++t) CHECK(tally_hash(text, 32, t, text_hash_mask(0)) == 0);
 
     // read-out order: count descending, extractor order of the type, text bytewise ascending (a prefix first, bytes unsigned)
     {
@@ -89,7 +85,7 @@ int main() {
     // selection for a top-N from the export alone: everything in front of the cut by (count, rank) and the whole group tied with it
     {
         std::vector<TallyExport> ex;
-        auto add = [&](uint64_t count, uint32_t type) { TallyExport x{}; x.count = count; x.item_type = type; x.slot = (uint32_t)ex.size(); x.text = distinct_text_word(8 * ex.size(), 5); ex.push_back(x); };
+        auto add = [&](uint64_t count, uint32_t type) { TallyExport x{}; x.count = count; x.item_type = type; x.slot = (uint32_t)ex.size(); x.text = text_word(8 * ex.size(), 5); ex.push_back(x); };
         add(1, IT_IPV4); add(7, IT_DOMAIN); add(1, IT_IPV4); add(3, IT_IPV4); add(1, IT_DOMAIN); add(3, IT_IPV6); add(1, IT_IPV4); add(7, IT_IPV4);
         auto sel = [&](size_t limit) { std::vector<uint32_t> s = tally_select(ex, limit); return std::set<uint32_t>(s.begin(), s.end()); };
         CHECK(sel(0).size() == 8 && sel(8).size() == 8 && sel(100).size() == 8);

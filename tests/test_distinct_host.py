@@ -1,5 +1,6 @@
 """CPU: the host side of the distinct-text set — the C ABI surface (header, export list, library) and the layout logic the host shares
-with the kernels (csrc/distinct.h: order key, slot states, hash masking, pool words), run alone under AddressSanitizer + UBSan."""
+with the kernels (csrc/distinct.h: order key, slot states; the table's own layout is in test_text_table_host.py), run alone under
+AddressSanitizer + UBSan."""
 import re
 import subprocess
 from pathlib import Path

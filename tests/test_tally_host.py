@@ -53,8 +53,10 @@ def test_sources_build_list_and_command_line():
     src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
     assert "--tally" in src and "matchy_multi_scanner_tally_top" in src
     hip = (ROOT / "matchy_amd" / "csrc" / "tally.hip").read_text()
-    for k in ("k_tally_claim", "k_tally_publish", "k_tally_rehash", "k_tally_export", "k_tally_gather"):
+    for k in ("k_tally_claim", "k_tally_publish", "k_tally_export", "k_tally_gather"):
         assert re.search(r"__global__[^;{]*\b%s\b" % k, hip), k
+    # the rehash kernel is the text table's, shared with the distinct-text set
+    assert "text_table.hip" in B.SOURCES and re.search(r"__global__[^;{]*\bk_text_rehash\b", (ROOT / "matchy_amd" / "csrc" / "text_table.hip").read_text())
     for env in ("MATCHY_AMD_TALLY_SLOTS", "MATCHY_AMD_TALLY_POOL_BYTES", "MATCHY_AMD_TALLY_HASH_BITS"):
         assert env in hip
 
