@@ -20,15 +20,16 @@
 //     k_validate_dom. Anchors whose look-ahead lies in the block that is not staged yet go back into the ring.
 //     Lists are written through wave-private chunks (one atomic per chunk, coalesced stores).
 // Tokens long enough to be hashes / crypto addresses (>= 26 bytes) are found without per-byte work: every accepted form is
-// made of ASCII letters and digits, so one bit per dword ("all four bytes alphanumeric") travels down the wave (DPP rotate);
-// only when three such dwords stand in a row somewhere (rare in logs) is the chain taken to five, and a dword with a
-// boundary byte behind five of them closes a candidate whose exact length is then computed from ballots.
+// made of ASCII letters and digits, so one bit per dword ("all four bytes alphanumeric") is all the block loop looks at: a cheap
+// necessary test for five such dwords in a row (anchor_planes.h: tok_trigger), only then the exact five-step chain (DPP rotate),
+// and a dword with a boundary byte behind five of them closes a candidate whose exact length is then computed from ballots.
+// The boundary plane is evaluated only in blocks that get that far, or all the time while a wave is in text full of such tokens.
 //
 // Anchor rules (exact-coverage arguments in DESIGN.md §Anchors; differential-tested against oracle/). The streaming
 // pass may list MORE positions than these rules (the look-ahead of the last bytes of a block is taken as "anything", the
 // first byte of a public-suffix label is a superset class): the drains and the validation kernels decide exactly.
 //   IPv4    '.' at j preceded by 1-3 digits preceded by a boundary / buffer start, followed by 1-3 digits and '.'
-//                                                                                    (ext:1120-1179, 813-869)
+//           (ext:1120-1179, 813-869; streamed as: digit at j-1, neither digit nor '.' at j-2..4, '.' at j+2..4)
 //   domain  byte that can start a PSL last label at j, '.' at j-1 (ext:537-628)
 //   IPv6    "::" ending at j, no third ':' before it                                (ext:1044-1116)
 //   e-mail  '@' at j                                                                 (ext:1182-1196)
@@ -539,9 +540,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan_add(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2 and 3
     return v;
 }
-// class of the byte k positions earlier / later (k = 1..4), aligned to this position
-template <int K> __device__ __forceinline__ uint32_t back(uint32_t P, uint32_t PV) { return K == 4 ? PV : __builtin_amdgcn_alignbyte(P, PV, 4 - K); }
-template <int K> __device__ __forceinline__ uint32_t ahead(uint32_t P, uint32_t NV) { return K == 4 ? NV : __builtin_amdgcn_alignbyte(NV, P, K); }
+// (class of the byte k positions earlier / later: plane_back / plane_ahead in anchor_planes.h)
+
+// Long tokens, sparse or dense (see the token block of the loop). A wave in dense mode goes back to sparse mode after this many blocks
+// in a row without a candidate: a sparse block that gets as far as the exact chain pays for the boundary plane a second time (window
+// read, transpose, class function: ~110 instructions), a dense block without need ~35, so dense mode is held over gaps of a few blocks.
+// Measured with 2, 4 and 8 on the shapes that live in dense mode and on the headline shape (profiles/r08_anchor_trigger_ab.txt): no value
+// stands out of the run-to-run spread on any of them (a wave there is either always dense or meets a token every ~80 blocks), so the
+// value from the cost estimate stays.
+constexpr uint32_t TOK_DENSE_HOLD = 4;
 
 // ALL: every extractor is enabled and the public-suffix first-byte class is the narrow one (the command line's and the
 // bulk scan's configuration): no run-time flag tests in the block loop.
@@ -586,6 +593,16 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
     PendingV4 pend;
     const uint32_t lane_off = lane << 2;
     const uint32_t lane0_one = lane == 0 ? 1u : 0u;   // shift count: the value that wraps from lane 63 into lane 0 moves one row up (x << 1 there, x elsewhere)
+    // classes (ctab) of the four bytes of a dword
+    auto dword_classes = [&](uint32_t x) {
+        return (uint32_t)ctab[x & 0xFF] | ((uint32_t)ctab[(x >> 8) & 0xFF] << 8) | ((uint32_t)ctab[(x >> 16) & 0xFF] << 16) | ((uint32_t)ctab[x >> 24] << 24);
+    };
+    // Long-token mode of this wave (wave-uniform). Dense: the boundary plane is evaluated in every block (the wave is in text full of long
+    // tokens). Both live outside the segment loop on purpose: a wave that takes another segment starts it in the mode it left the last one
+    // in — the same log goes on — instead of paying for the plane a second time at every segment start. Any mode is correct at a segment
+    // start: in dense mode Bcur is evaluated in the front end, and Bprev / Aprev come from the segment prologue either way.
+    bool tok_dense = false;
+    uint32_t tok_quiet = 0;    // dense mode: blocks in a row without a candidate
 
     // dword `lane` of the 8 rows of block `b`; positions >= len read as ' ' (a boundary, like the end of the buffer)
     auto load_block = [&](uint32_t b, uint32_t (&w)[8]) {
@@ -622,26 +639,26 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
         const uint32_t seg_end = min(seg_start + ks->seg_bytes, ks->scan_end);
         // Plane carries = the word a lane 63 of a block in front of the segment would hold; only its row-7 bits (8 b + 7 =
         // class of byte seg_start - 4 + b) are ever used. In front of the buffer: boundary.
-        uint32_t cB = 0x80808080u, cX = 0;   // cX: carry of the packed word X = [C.b2, C.b3, D.b3, T.b3] (see the block loop)
+        uint32_t cN = 0x80808080u, cX = 0;   // cN: "neither digit nor '.'"; cX: carry of the packed word X = [C.b2, C.b3, D.b3, T.b3] (see the block loop)
         if (seg_start) {
             uint32_t c4 = 0;
             for (uint32_t k = 0; k < 4; ++k) c4 |= (uint32_t)ctab[p.log[seg_start - 4 + k]] << (8 * k);
             c4 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c4);
             static_assert(C_B == 1 && C_DIG == 2 && C_DOT == 4 && C_COLON == 8 && C_LD == 32, "carry shifts");
-            cB = (c4 << 7) & 0x80808080u;
+            cN = (~((c4 << 6) | (c4 << 5))) & 0x80808080u;   // neither C_DIG nor C_DOT
             const uint32_t c2 = (c4 >> 16) & 0xFFu, c3 = c4 >> 24;   // classes of the bytes at seg_start - 2 and seg_start - 1
             cX = ((c2 << 4) & 0x80u) | (((c3 << 4) & 0x80u) << 8) | (((c3 << 6) & 0x80u) << 16) | (((c3 << 5) & 0x80u) << 24);
         }
-        // Token state: the boundary plane of the previous block (row 7 = the 256 bytes in front of this block) and its
-        // "dword holds no boundary byte" bits. In front of the buffer: a boundary at position -1.
+        // Token state: the boundary plane of the previous block (only its row 7 = the 256 bytes in front of this block is read; kept from
+        // block to block in dense mode, taken from the window where a sparse block needs it) and, in bit 0, whether that block's dword
+        // of row 7 was all-alphanumeric (tok_rows). In front of the buffer: a boundary at position -1.
         uint32_t Bprev = lane == 63 ? 0x80000000u : 0u, Aprev = 0;
         if (en_tok && seg_start) {
             const uint32_t x = *reinterpret_cast<const uint32_t*>(p.log + seg_start - AB_ROW_BYTES + lane_off);
-            const uint32_t c = (uint32_t)ctab[x & 0xFF] | ((uint32_t)ctab[(x >> 8) & 0xFF] << 8) | ((uint32_t)ctab[(x >> 16) & 0xFF] << 16) |
-                               ((uint32_t)ctab[x >> 24] << 24);
+            const uint32_t c = dword_classes(x);
             Bprev = (c << 7) & 0x80808080u;
-            // all four bytes ASCII alphanumerics (label bytes below 0x80): row 7 of the previous block for the token chain
-            Aprev = ((c & (C_LD * 0x01010101u)) == C_LD * 0x01010101u && (x & 0x80808080u) == 0) ? 0x80u : 0u;
+            // all four bytes ASCII alphanumerics (label bytes below 0x80)
+            Aprev = ((c & (C_LD * 0x01010101u)) == C_LD * 0x01010101u && (x & 0x80808080u) == 0) ? 1u : 0u;
         }
 
         uint32_t nx[8];
@@ -683,29 +700,57 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
             // ---- bit planes and byte classes of the lane's 32 positions: bit t <-> position blk + 256 (t & 7) + 4 lane + (t >> 3)
             bit_transpose8_rest(w);
             const ClassPlanes cl = classify_planes(w, tl_wide);
+            // cl.B is read nowhere: the boundary plane is evaluated here only while the wave is in dense mode (token block below)
+            uint32_t Bcur = 0;
+            if (en_tok && tok_dense) Bcur = boundary_plane(w);
             nl_count += __popc(cl.NL);
             __builtin_amdgcn_s_setprio(PRIO_CHAIN);  // from here on cross-lane steps, LDS and memory: see PRIO_CHAIN
             const uint32_t pos_base = blk + lane_off;
             const uint32_t ent_base = blk | (lane << 5);   // ring entries: anchor_pos()
 
+            // Long tokens, first steps: run in the token block below. (Kept as a function defined here: with the same statements written out
+            // in the token block the compiler lays the loop out differently and the kernel takes 0.605 instead of 0.590 ms on the headline
+            // batch; called here, side by side with the ring scan, 0.606.)
+            // a4: bit q set when all four bytes of this lane's dword of row q are ASCII alphanumerics.
+            // x: bit q + 1 = row q of this lane, bit 0 = row 7 of the previous block. The value travels down the wave (rotate by one lane
+            // per step); when it wraps from lane 63 to lane 0 it moves one row up, which is one bit to the left. After k steps it is the
+            // state of the dword k places earlier in the byte stream (tok_y: one place).
+            // SPARSE MODE (a): is the exact chain worth running? Five all-alphanumeric dwords in a row contain the four-dword windows that
+            // end at their last two dwords, in neighbouring lanes (tok_trigger in anchor_planes.h, checked there against the exact chain):
+            // two-dword windows from the first step, four-dword windows (tok_w4) with one ds_bpermute (two lanes down), then scalar work
+            // on one ballot. Per 2 KiB block of the synthetic shapes (tools/synth.py, 40 000 lines): three such dwords in a row stand in
+            // 74.9 % of the nginx blocks and four in 44.9 % (url-heavy: 30.9 % and none), five in 1.2 %; the trigger fires in 1.8 %.
+            // Application and endpoint logs (jsonl-app, hash-dense) have five in every block: dense mode, no trigger.
+            uint32_t tok_y = 0, tok_w4 = 0;
+            auto tok_first_steps = [&]() {
+                const uint32_t a4 = tok_a4(cl.LD, w[7]);
+                const uint32_t x = tok_rows(a4, Aprev);
+                Aprev = a4 >> 7;
+                tok_y = tok_up((uint32_t)__builtin_amdgcn_mov_dpp((int)x, DPP_WAVE_ROR1, 0xF, 0xF, false), lane0_one);   // every lane has a source: no `old` value to set up
+                if (!tok_dense) {
+                    const uint32_t t = x & tok_y;
+                    const uint32_t t2 = tok_up((uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane + 62u) & 63u) << 2), (int)t), lane < 2 ? 1u : 0u);
+                    tok_w4 = t & t2;
+                }
+            };
             uint32_t Fd = 0, F4 = 0, F6 = 0;
             // The patterns need one byte of the previous dword's '.' and digit planes and two of its ':' plane: they travel
             // together as X = [C.b2, C.b3, D.b3, T.b3] (one cross-lane step instead of three; `v_perm` puts the bytes in place)
             const uint32_t X = __builtin_amdgcn_perm(cl.T, __builtin_amdgcn_perm(cl.D, cl.C, 0x07070302u), 0x07020100u);
             const uint32_t PV_X = plane_prev_dword(X, cX);
             if (en_v4) {
-                // '.' at j, digit at j-1, a boundary 2..4 positions back ...
-                const uint32_t PV_B = plane_prev_dword(cl.B, cB);
-                const uint32_t lookback = __builtin_amdgcn_perm(cl.D, PV_X, 0x06050402u) & (back<2>(cl.B, PV_B) | back<3>(cl.B, PV_B) | back<4>(cl.B, PV_B));
-                // ... and a digit at j+1 and a second dot 2..4 positions ahead (necessary for a dotted quad whose first dot this is;
-                // drops "HTTP/1.1", "Mozilla/5.0", "Safari/537.36" style anchors). The drain checks the digits in between.
-                const uint32_t NV_D = plane_next_dword(cl.D, 0x80808080u), NV_T = plane_next_dword(cl.T, 0x80808080u);
-                const uint32_t lookahead = ahead<1>(cl.D, NV_D) & (ahead<2>(cl.T, NV_T) | ahead<3>(cl.T, NV_T) | ahead<4>(cl.T, NV_T));
-                F4 = cl.T & lookback & lookahead;
+                // '.' at j, digit at j-1, a byte that is neither digit nor '.' 2..4 positions back (a superset of "boundary" from planes that
+                // are there anyway; the drain checks the byte in front of the first octet exactly) and a second dot 2..4 positions ahead
+                // (necessary for a dotted quad whose first dot this is; drops "HTTP/1.1", "Mozilla/5.0", "Safari/537.36" style anchors).
+                // The drain checks the digits in between.
+                const uint32_t N = nondigit_nondot_plane(cl.D, cl.T);
+                const uint32_t PV_N = plane_prev_dword(N, cN);
+                const uint32_t NV_T = plane_next_dword(cl.T, 0x80808080u);
+                F4 = ipv4_anchor_plane(cl.T, __builtin_amdgcn_perm(cl.D, PV_X, 0x06050402u), N, PV_N, NV_T);
             }
             if (en_dom) {
                 // byte that can start a public suffix's last label at j, '.' at j-1 (what stands at j-2 is the validators' business)
-                Fd = cl.TL & back<1>(cl.T, PV_X);
+                Fd = cl.TL & plane_back<1>(cl.T, PV_X);
             }
             if (en_v6) {
                 // "::" ending at j without a third ':'
@@ -798,29 +843,36 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
             if (en_tok) {
                 // Every token the validators accept (hex hashes, Base58 / Bech32 / 0x-hex addresses) consists of ASCII letters
                 // and digits only, and a token of >= 26 such bytes that ends in dword i makes dwords i-1 .. i-5 all-alphanumeric.
-                // a4: bit q set when all four bytes of this lane's dword of row q are ASCII alphanumerics.
-                const uint32_t an = cl.LD & ~w[7];
-                const uint32_t a4 = an & (an >> 8) & (an >> 16) & (an >> 24) & 0xFFu;
-                // x: bit q + 1 = row q of this lane, bit 0 = row 7 of the previous block. The value travels down the wave (rotate
-                // by one lane per step); when it wraps from lane 63 to lane 0 it moves one row up, which is one bit to the left.
-                // After k steps x is the state of the dword k places earlier in the byte stream.
-                uint32_t x = (a4 << 1) | (Aprev >> 7), r = 0xFFFFFFFFu;
-                Aprev = a4;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    x = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, DPP_WAVE_ROR1, 0xF, 0xF, false) << lane0_one;   // every lane has a source: no `old` value to set up
-                    r &= x;
-                }
-                // three all-alphanumeric dwords in a row (12+ such bytes) are rare in logs: the rest only then
+                tok_first_steps();
+                uint32_t y = tok_y;
+                bool chain = tok_dense;
+                if (!tok_dense) chain = tok_trigger_from_lanes(__ballot(tok_w4 != 0));
                 uint32_t cand = 0;
-                if (__ballot(r != 0)) {
+                if (chain) {
+                    // (b) the exact chain: five steps
+                    uint32_t r = y;
 #pragma unroll
-                    for (int k = 3; k < 5; ++k) {
-                        x = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, DPP_WAVE_ROR1, 0xF, 0xF, false) << lane0_one;
-                        r &= x;
+                    for (int k = 1; k < 5; ++k) {
+                        y = tok_up((uint32_t)__builtin_amdgcn_mov_dpp((int)y, DPP_WAVE_ROR1, 0xF, 0xF, false), lane0_one);
+                        r &= y;
+                    }
+                    if (!tok_dense && __ballot(tok_chain_rows(r) != 0)) {
+                        // some dword has five all-alphanumeric ones below it: from here on the boundary plane is needed. This block's
+                        // comes from its bytes in the window (each lane reads back the eight dwords it wrote), the previous block's
+                        // row 7 from the window through the class table, as at the start of a segment (whose value still stands when
+                        // this is the segment's first block). The wave is in dense mode from the next block on.
+                        uint32_t rb[8];
+                        const uint32_t* src = &raw32[((blk & (RAW_BYTES - 1)) >> 2) + lane];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) rb[q] = src[64 * q];
+                        bit_transpose8(rb);
+                        Bcur = boundary_plane(rb);
+                        if (blk != seg_start) Bprev = (dword_classes(raw32[(((blk - AB_ROW_BYTES) & (RAW_BYTES - 1)) >> 2) + lane]) << 7) & 0x80808080u;
+                        tok_dense = true;
+                        tok_quiet = 0;
                     }
                     // only the lowest boundary byte of a dword can close a long token
-                    cand = (cl.B | (cl.B >> 8) | (cl.B >> 16) | (cl.B >> 24)) & (r >> 1) & 0xFFu;
+                    cand = (Bcur | (Bcur >> 8) | (Bcur >> 16) | (Bcur >> 24)) & tok_chain_rows(r);
                 }
                 if (__ballot(cand != 0)) {
                     // Exact length from the boundary-free dwords (G) around the candidate. One candidate per lane and round, whatever row it
@@ -828,7 +880,7 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
                     // of an endpoint or JSON log, where each line carries hashes or ids). The rows' free-dword masks — eight ballots and the
                     // previous block's last row — are parked in the lanes of one register (lane r: low word of row r - 1, lane 16 + r: high
                     // word; r = 0: the previous block's row 7) and every lane fetches the two rows it needs with ds_bpermute.
-                    const uint32_t G = ~(cl.B | (cl.B >> 8) | (cl.B >> 16) | (cl.B >> 24)) & 0xFFu;
+                    const uint32_t G = ~(Bcur | (Bcur >> 8) | (Bcur >> 16) | (Bcur >> 24)) & 0xFFu;
                     const uint32_t Gprev = (Bprev & 0x80808080u) ? 0u : 0x80u;   // row 7 of the previous block
                     // (v_writelane through inline assembly: the compiler offers no builtin for it here and does not see the hazard between the
                     // v_cmp that has just written VCC and a v_writelane that reads it — without the wait states in front of each one the lanes
@@ -867,12 +919,12 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
                         // the dword below the run holds the last boundary byte before the token
                         const int32_t it = (int32_t)(64 * q + lane) - (int32_t)run - 1;    // dword index in the block (negative: previous block)
                         const uint32_t src_lane = (uint32_t)it & 63u;
-                        const uint32_t wb_cur = (uint32_t)__shfl((int)cl.B, (int)src_lane);
+                        const uint32_t wb_cur = (uint32_t)__shfl((int)Bcur, (int)src_lane);
                         const uint32_t wb_prev = (uint32_t)__shfl((int)Bprev, (int)src_lane);
                         const uint32_t rowbits = it >= 0 ? ((wb_cur >> (it >> 6)) & 0x01010101u) : ((wb_prev >> 7) & 0x01010101u);
                         const uint32_t hb = rowbits ? (31u - (uint32_t)__clz((int)rowbits)) >> 3 : 0u;
                         const int32_t s = (int32_t)blk + 4 * it + (int32_t)hb + 1;         // token start
-                        const uint32_t mybits = (cl.B >> q) & 0x01010101u;
+                        const uint32_t mybits = (Bcur >> q) & 0x01010101u;
                         const uint32_t b0 = mybits ? ((uint32_t)__ffs((int)mybits) - 1u) >> 3 : 0u;
                         const uint32_t e = blk + AB_ROW_BYTES * q + lane_off + b0;          // closing boundary
                         const uint32_t tl = e - (uint32_t)s;
@@ -880,8 +932,11 @@ __global__ __launch_bounds__(AW * 64) void k_anchor(TokParams p, DevDb db) {
                                          ((tl >= 26 && tl <= 62) || tl == 64 || (tl >= 90 && tl <= 110) || tl == 128);
                         cw_tok.append(tok, make_uint2((uint32_t)s, (uint32_t)RARE_TOK | (tl << 8)));
                     }
+                    tok_quiet = 0;
+                } else if (tok_dense && ++tok_quiet >= TOK_DENSE_HOLD) {
+                    tok_dense = false;
                 }
-                Bprev = cl.B;
+                Bprev = Bcur;   // dense mode: the next block's previous plane (sparse mode: not read before it is set again)
             }
         }
         // the next segment of this wave is not contiguous: finish the rings while their bytes are still in the window
