@@ -48,9 +48,6 @@ MXY_HD bool distinct_is_key(unsigned long long order) { return (order >> 63) == 
 class DistinctSet {
 public:
     DistinctSet();
-    ~DistinctSet();
-    DistinctSet(const DistinctSet&) = delete;
-    DistinctSet& operator=(const DistinctSet&) = delete;
     // Keeps, of the candidates of one batch (two lists, padding entries have len_type 0xFFFFFFFF; `cand_true` real ones), those whose
     // text log[start, start + len) is not in the set yet — per text the one with the least (start, type rank) — adds their texts, and
     // copies exactly them to `out`. Synchronises `stream`.
@@ -64,10 +61,9 @@ public:
 
 private:
     TextTable table_;
-    Candidate* out_dev_ = nullptr;
-    size_t out_n_ = 0;
+    DevBuf<Candidate> out_dev_;
     bool profile_ = false;
-    hipEvent_t ev_[2] = {nullptr, nullptr};
+    Event ev_[2];   // created by the first profiled filter()
     float last_ms_ = 0;
 };
 

@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <string>
 
-#include "engine.h"
 
 namespace mxy {
 
@@ -109,11 +108,6 @@ constexpr TextTableOwner DISTINCT_OWNER = {"distinct set", "texts", "matchy_amd_
 
 DistinctSet::DistinctSet() : table_(DISTINCT_OWNER) {}
 
-DistinctSet::~DistinctSet() {
-    if (out_dev_) (void)hipFree(out_dev_);
-    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-}
-
 void DistinctSet::reset() { table_.reset(); }
 
 void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
@@ -128,19 +122,14 @@ void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list
     table_.start_batch(stream);
     // everything that can fail for lack of memory comes first: up to here and through these the set is untouched
     table_.reserve(table_.count() + cand_true, n, stream);
-    if (out_n_ < cand_true) {
-        if (out_dev_) (void)hipFree(out_dev_);
-        out_dev_ = nullptr; out_n_ = 0;
-        MXY_HIP(hipMalloc((void**)&out_dev_, ((size_t)cand_true + cand_true / 4 + 1024) * sizeof(Candidate)));
-        out_n_ = (size_t)cand_true + cand_true / 4 + 1024;
-    }
-    if (profile_) for (auto& e : ev_) if (!e) MXY_HIP(hipEventCreate(&e));
+    if (out_dev_.n < cand_true) out_dev_.alloc((size_t)cand_true + cand_true / 4 + 1024);
+    if (profile_) for (Event& e : ev_) e.create();
 
     DistinctParams p{};
     p.log = log; p.len = len;
     p.list_a = list_a; p.n_a = n_a; p.list_b = list_b; p.n_b = n_b;
     p.t = table_.open();
-    p.out = out_dev_; p.out_cap = (uint32_t)std::min<size_t>(out_n_, 0xFFFFFFFFu);
+    p.out = out_dev_.p; p.out_cap = (uint32_t)std::min<size_t>(out_dev_.n, 0xFFFFFFFFu);
     const int grid = grid_for_items(n);
     if (profile_) MXY_HIP(hipEventRecord(ev_[0], stream));
     hipLaunchKernelGGL(k_distinct_claim, dim3(grid), dim3(DISTINCT_THREADS), 0, stream, p);
@@ -153,7 +142,7 @@ void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list
     const uint32_t n_out = table_.host_counters().n_new;
     if (n_out > p.out_cap) throw HipError{"distinct set: more survivors than candidates"};
     out.resize(n_out);
-    if (n_out) MXY_HIP(hipMemcpyAsync(out.data(), out_dev_, (size_t)n_out * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
+    if (n_out) MXY_HIP(hipMemcpyAsync(out.data(), out_dev_.p, (size_t)n_out * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     MXY_HIP(hipStreamSynchronize(stream));
     if (profile_) MXY_HIP(hipEventElapsedTime(&last_ms_, ev_[0], ev_[1]));
     table_.close();

@@ -488,39 +488,16 @@ Scanner::Scanner(std::shared_ptr<const DbImage> img, std::shared_ptr<DeviceDb> d
     counters_.alloc(MAX_SLICES);
     MXY_HIP(hipMemset(counters_.p, 0, sizeof(ScanCounters) * MAX_SLICES));
     counters_clean_ = true;
-    MXY_HIP(hipHostMalloc((void**)&host_slices_, sizeof(ScanCounters) * MAX_SLICES, hipHostMallocDefault));
-    for (auto& e : ev_) MXY_HIP(hipEventCreate(&e));
-    MXY_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-    MXY_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-    MXY_HIP(hipStreamCreateWithFlags(&aux_stream_, hipStreamNonBlocking));
-    MXY_HIP(hipEventCreateWithFlags(&ev_join2_, hipEventDisableTiming));
-    MXY_HIP(hipStreamCreateWithFlags(&aux2_stream_, hipStreamNonBlocking));
+    host_slices_.alloc(MAX_SLICES);
+    for (Event& e : ev_) e.create();
+    ev_fork_.create(hipEventDisableTiming);
+    ev_join_.create(hipEventDisableTiming);
+    aux_stream_.create(hipStreamNonBlocking);
+    ev_join2_.create(hipEventDisableTiming);
+    aux2_stream_.create(hipStreamNonBlocking);
 }
 
-Scanner::~Scanner() {
-    if (pinned_) (void)hipHostFree(pinned_);
-    if (mirror_) (void)hipHostFree(mirror_);
-    if (mirror_c4_) (void)hipHostFree(mirror_c4_);
-    if (pinned_c4_) (void)hipHostFree(pinned_c4_);
-    if (host_slices_) (void)hipHostFree(host_slices_);
-    if (pinned_lines_) (void)hipHostFree(pinned_lines_);
-    for (auto& e : ev_line_) if (e) (void)hipEventDestroy(e);
-    if (pinned_seg_) (void)hipHostFree(pinned_seg_);
-    for (auto& e : ev_seg_) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_anchor_) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_misc_) if (e) (void)hipEventDestroy(e);
-    if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-    if (ev_join_) (void)hipEventDestroy(ev_join_);
-    if (aux_stream_) (void)hipStreamDestroy(aux_stream_);
-    if (ev_join2_) (void)hipEventDestroy(ev_join2_);
-    if (ev_join3_) (void)hipEventDestroy(ev_join3_);
-    if (ev_dom_) (void)hipEventDestroy(ev_dom_);
-    if (ev_v1_) (void)hipEventDestroy(ev_v1_);
-    if (aux2_stream_) (void)hipStreamDestroy(aux2_stream_);
-    if (dom_stream_) (void)hipStreamDestroy(dom_stream_);
-    if (host_stream_) (void)hipStreamDestroy(host_stream_);
-}
+Scanner::~Scanner() = default;   // here: DistinctSet and HitTally are incomplete in the header
 
 void Scanner::set_unique(bool on) {
     if (on && !distinct_) {
@@ -584,20 +561,23 @@ void Scanner::ensure_capacity(uint32_t len) {
     ensure_final(work_[0].hits.n, work_[0].ids.n);
 }
 
-void Scanner::ensure_mirror(uint32_t recs, uint32_t ids) {
-    if (mirror_ && mirror_cap_ >= recs && mirror_ids_cap_ >= ids) return;
-    if (mirror_) (void)hipHostFree(mirror_);
-    mirror_cap_ = std::max(recs, mirror_cap_); mirror_ids_cap_ = std::max(ids, mirror_ids_cap_);
-    const size_t bytes = (size_t)mirror_cap_ * sizeof(FinalHit) + (size_t)mirror_ids_cap_ * 12 + 64;
-    MXY_HIP(hipHostMalloc(&mirror_, bytes, hipHostMallocDefault));
-}
+static_assert(sizeof(FinalHit) == ResultLayout::REC_BYTES, "result_layout.h lays out FinalHit records");
 
-void Scanner::ensure_mirror_c4(uint32_t recs) {
-    if (mirror_c4_ && mirror_c4_cap_ >= recs) return;
-    if (mirror_c4_) (void)hipHostFree(mirror_c4_);
-    mirror_c4_ = nullptr;
-    mirror_c4_cap_ = std::max(recs, mirror_c4_cap_);
-    MXY_HIP(hipHostMalloc((void**)&mirror_c4_, (size_t)mirror_c4_cap_ * sizeof(uint2), hipHostMallocDefault));
+namespace {
+// the three arrays of a result block (result_layout.h) that begins at `block`
+struct ResultArrays { FinalHit* recs; uint32_t* ids; long long* offs; };
+ResultArrays arrays_of(uint8_t* block, const ResultLayout& l) {
+    return {(FinalHit*)block, (uint32_t*)(block + l.ids_offset()), (long long*)(block + l.offs_offset())};
+}
+}  // namespace
+
+// Neither capacity shrinks. The layout is recorded when the block exists: a failed allocation leaves an empty mirror of no capacity.
+void Scanner::ensure_mirror(uint32_t recs, uint32_t ids) {
+    if (mirror_.p && mirror_layout_.recs_cap >= recs && mirror_layout_.ids_cap >= ids) return;
+    const ResultLayout want{std::max<size_t>(recs, mirror_layout_.recs_cap), std::max<size_t>(ids, mirror_layout_.ids_cap)};
+    mirror_layout_ = ResultLayout{};
+    mirror_.alloc(want.bytes());
+    mirror_layout_ = want;
 }
 
 namespace {
@@ -708,15 +688,14 @@ void Scanner::slice_params(int sl, const ScanRequest& rq, uint32_t lo, uint32_t 
         pp.out = final_.p; pp.out_cap = (uint32_t)final_.n;
         pp.out_ids = final_ids_.p; pp.out_offs = final_offs_.p; pp.out_ids_cap = (uint32_t)final_ids_.n;
         if (rq.host_mirror) {
-            uint8_t* mb = (uint8_t*)mirror_;
-            pp.host_out = (FinalHit*)mb; pp.host_cap = mirror_cap_;
-            pp.host_ids = (uint32_t*)(mb + (size_t)mirror_cap_ * sizeof(FinalHit));
-            pp.host_offs = (long long*)(mb + (size_t)mirror_cap_ * sizeof(FinalHit) + (((size_t)mirror_ids_cap_ * 4 + 7) & ~(size_t)7));
-            pp.host_ids_cap = mirror_ids_cap_;
+            const ResultArrays m = arrays_of(mirror_.p, mirror_layout_);
+            pp.host_out = m.recs; pp.host_cap = (uint32_t)mirror_layout_.recs_cap;
+            pp.host_ids = m.ids; pp.host_offs = m.offs;
+            pp.host_ids_cap = (uint32_t)mirror_layout_.ids_cap;
         }
         if (compact_) {
             pp.c4_out = c4_.p; pp.c4_cap = (uint32_t)c4_.n;
-            if (rq.host_mirror) { pp.host_c4 = mirror_c4_; pp.host_c4_cap = mirror_c4_cap_; }
+            if (rq.host_mirror) { pp.host_c4 = mirror_c4_.p; pp.host_c4_cap = (uint32_t)mirror_c4_.n; }
         }
         pp.counters = counters_.p;   // n_final / n_final_ids of slice 0 hand out the slots of the shared record arrays
         // k_lookup writes the final records itself (the PCIe writes of the mirror overlap the lookups); only the
@@ -813,7 +792,7 @@ void Scanner::scan_device(const ScanRequest& rq, hipStream_t stream) {
     if (rq.lookup && rq.host_mirror) {
         static const uint32_t mirror0 = getenv("MATCHY_AMD_MIRROR_RECS") ? (uint32_t)atoi(getenv("MATCHY_AMD_MIRROR_RECS")) : (1u << 20);
         ensure_mirror(std::max(mirror0, 16u), std::max(mirror0 / 16, 16u));
-        if (compact_) ensure_mirror_c4(std::max(mirror0, 16u));
+        if (compact_) mirror_c4_.ensure(std::max(mirror0, 16u));
         mirror_used_ = true;
     }
     if (compact_ && c4_.n < final_.n) c4_.alloc(final_.n);
@@ -852,9 +831,9 @@ void Scanner::scan_device(const ScanRequest& rq, hipStream_t stream) {
 
 void Scanner::ensure_dom_stream() {
     if (dom_stream_) return;
-    MXY_HIP(hipStreamCreateWithFlags(&dom_stream_, hipStreamNonBlocking));
-    MXY_HIP(hipEventCreateWithFlags(&ev_join3_, hipEventDisableTiming));
-    MXY_HIP(hipEventCreateWithFlags(&ev_dom_, hipEventDisableTiming));
+    dom_stream_.create(hipStreamNonBlocking);
+    ev_join3_.create(hipEventDisableTiming);
+    ev_dom_.create(hipEventDisableTiming);
 }
 
 // Sliced scan. The scan's stream carries the k_anchor launches, slice after slice. Behind k_anchor of slice i three side streams
@@ -866,10 +845,8 @@ void Scanner::launch_sliced(int ns, hipStream_t stream) {
     const DevDb& view = ddb_->view;
     last_forked_ = true;
     ensure_dom_stream();
-    if (!ev_anchor_[0]) {
-        for (auto& e : ev_anchor_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto& e : ev_misc_) MXY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    for (Event& e : ev_anchor_) e.create(hipEventDisableTiming);
+    for (Event& e : ev_misc_) e.create(hipEventDisableTiming);
     for (int k = 0; k < ns; ++k) {
         SliceLaunch& L = launch_[k];
         ScanCounters* ctr = counters_.p + k;
@@ -973,7 +950,7 @@ void Scanner::launch_forked(hipStream_t stream) {
         TokParams tt = t1;
         tt.vmode = 4u;
         launch_validate_misc(tt, view, tok_grid, aux2_stream_);
-        if (!ev_v1_) MXY_HIP(hipEventCreateWithFlags(&ev_v1_, hipEventDisableTiming));
+        ev_v1_.create(hipEventDisableTiming);
         MXY_HIP(hipEventRecord(ev_v1_, aux2_stream_));
         t1.vmode = 1u;
     }
@@ -1077,13 +1054,6 @@ void Scanner::launch_one_stream(hipStream_t stream) {
     }
 }
 
-void Scanner::ensure_pinned(size_t bytes) {
-    if (pinned_bytes_ >= bytes) return;
-    if (pinned_) (void)hipHostFree(pinned_);
-    pinned_bytes_ = bytes + bytes / 4 + (1 << 16);
-    MXY_HIP(hipHostMalloc(&pinned_, pinned_bytes_, hipHostMallocDefault));
-}
-
 size_t sort_hits_temp_bytes(uint32_t n);
 hipError_t sort_hits(const FinalHit* fin, uint32_t n, unsigned long long* keys, uint32_t* vals, void* temp, size_t temp_bytes, FinalHit* out,
                      hipStream_t stream);
@@ -1128,11 +1098,10 @@ static void wait_stream(hipStream_t stream, bool poll) {
     MXY_HIP(hipStreamSynchronize(stream));
 }
 
-void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMode hit_mode, bool sorted) {
-    const bool trace = !single_ && getenv("MATCHY_AMD_TRACE");
-    MXY_HIP(hipSetDevice(ddb_->device));   // regrown buffers must land on this scanner's device whatever thread calls
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+// The counters of the last scan_device, settled: k_finish copies the counter blocks out, a list that was over is regrown and the scan runs
+// again, candidates the glob pass could not hold go through the spill pass. Leaves host_counters_ (and the slices' blocks) final and
+// the device counters clean.
+void Scanner::settle_counters(bool trace, hipStream_t stream) {
     const int ns = n_slices_;
     // `attempt` counts the regrows of this fetch. While a list is over, its consumers see min(counter, capacity) entries and everything
     // downstream of it under-counts; the most upstream list that is over has an exact count (nothing in front of it was cut), so every
@@ -1143,12 +1112,12 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     constexpr int MAX_REGROWS = 8;
     for (int attempt = 0;;) {
         // k_finish: the counter blocks go to pinned host memory and are cleared on the device for the next scan
-        launch_finish(counters_.p, host_slices_, ns, expect_chains_, dom_want_, stream);
+        launch_finish(counters_.p, host_slices_.p, ns, expect_chains_, dom_want_, stream);
         // side chains that report to k_finish end behind the last event scan_device recorded: the interval ends behind k_finish then
         if (profile_ && expect_chains_) MXY_HIP(hipEventRecord(ev_[4], stream));
         expect_chains_ = 0;   // a rescan sets it again; the spill pass below runs on this stream
         wait_stream(stream, last_.fork);
-        if (host_slices_[0].error & 8u) {
+        if (host_slices_.p[0].error & 8u) {
             // k_finish gave up polling for the side chains (they are slow, not lost): the counters it copied are a snapshot and the
             // device copies were left alone. Join the side streams here, then take the counters again without a poll.
             counters_clean_ = false;
@@ -1156,15 +1125,15 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             if (aux_stream_) MXY_HIP(hipStreamSynchronize(aux_stream_));
             if (aux2_stream_) MXY_HIP(hipStreamSynchronize(aux2_stream_));
             if (dom_stream_) MXY_HIP(hipStreamSynchronize(dom_stream_));
-            launch_finish(counters_.p, host_slices_, ns, 0u, dom_want_, stream);
+            launch_finish(counters_.p, host_slices_.p, ns, 0u, dom_want_, stream);
             wait_stream(stream, false);
         }
         counters_clean_ = true;
         // slice 0 holds n_final / n_final_ids of all slices; statistics are summed
         ScanCounters& c = host_counters_;
-        c = host_slices_[0];
+        c = host_slices_.p[0];
         for (int k = 1; k < ns; ++k) {
-            const ScanCounters& s = host_slices_[k];
+            const ScanCounters& s = host_slices_.p[k];
             c.lines += s.lines; c.cand_true += s.cand_true; c.hits_true += s.hits_true; c.error |= s.error;
         }
         bool over = false;
@@ -1179,7 +1148,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             over_names += b;
         };
         for (int k = 0; k < ns; ++k)
-            each_list(work_[k], host_slices_[k], [&](const char* name, size_t cap, size_t need, auto&&) { test(name, k, cap, need); });
+            each_list(work_[k], host_slices_.p[k], [&](const char* name, size_t cap, size_t need, auto&&) { test(name, k, cap, need); });
         test("final_", 0, final_.n, c.n_final);
         test("final_ids_", 0, final_ids_.n, c.n_final_ids);
         if (compact_) test("c4_", 0, c4_.n, c.n_c4);
@@ -1188,16 +1157,16 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             // If there are, the spill pass runs now — its scratch (one bit per pattern id per thread) is allocated only here — and
             // appends their records to the same arrays; the counters are read again afterwards.
             uint32_t n_spill = 0;
-            for (int k = 0; k < ns; ++k) n_spill += work_[k].spill.n ? host_slices_[k].n_spill : 0u;
+            for (int k = 0; k < ns; ++k) n_spill += work_[k].spill.n ? host_slices_.p[k].n_spill : 0u;
             if (n_spill == 0 || spill_done_ || !last_.lookup) break;
             const uint32_t threads = spill_threads();
             const size_t words = launch_[0].lp.spill_words;
             if (spill_scratch_.n < words * SPILL_BLOCKS * threads) spill_scratch_.alloc(words * SPILL_BLOCKS * threads);
             // the spill pass appends to the lists the counters describe: put them back (k_finish cleared them)
-            MXY_HIP(hipMemcpyAsync(counters_.p, host_slices_, sizeof(ScanCounters) * ns, hipMemcpyHostToDevice, stream));
+            MXY_HIP(hipMemcpyAsync(counters_.p, host_slices_.p, sizeof(ScanCounters) * ns, hipMemcpyHostToDevice, stream));
             counters_clean_ = false;
             for (int k = 0; k < ns; ++k) {
-                if (!work_[k].spill.n || !host_slices_[k].n_spill) continue;
+                if (!work_[k].spill.n || !host_slices_.p[k].n_spill) continue;
                 LookupParams lp = launch_[k].lp;
                 lp.spill_scratch = spill_scratch_.p;
                 launch_lookup_spill(lp, ddb_->view, stream);
@@ -1213,7 +1182,7 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         // grow and run again: the kernels count past the capacity without writing, so the counts are exact demands
         size_t recs = 0, ids = 0;
         for (int k = 0; k < ns; ++k) {
-            each_list(work_[k], host_slices_[k], [](const char*, size_t cap, size_t need, auto&& grow) { if (need > cap) grow(); });
+            each_list(work_[k], host_slices_.p[k], [](const char*, size_t cap, size_t need, auto&& grow) { if (need > cap) grow(); });
             recs += work_[k].hits.n; ids += work_[k].ids.n;
         }
         if (final_.n < recs || c.n_final > final_.n) final_.alloc(std::max<size_t>(recs, grown(c.n_final)));
@@ -1224,10 +1193,15 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         if (compact_ && c.n_c4 > c4_.n) c4_.alloc(grown(c.n_c4));
         scan_device(last_, stream);
     }
+}
+
+// What the settled counters say: the grid hints of the next scan, the error words, the trace line, `out`'s counters, the timings.
+void Scanner::report_counters(ScanOutput& out, bool trace) {
+    const int ns = n_slices_;
     {
         ListHint hh;
         for (int k = 0; k < ns; ++k) {
-            const ScanCounters& q = host_slices_[k];
+            const ScanCounters& q = host_slices_.p[k];
             hh.n_tok = std::max(hh.n_tok, q.n_tok); hh.n_rare = std::max(hh.n_rare, q.n_rare); hh.n_rare_dom = std::max(hh.n_rare_dom, q.n_rare_dom);
             hh.n_heavy = std::max(hh.n_heavy, q.n_heavy); hh.n_cand = std::max(hh.n_cand, q.n_cand); hh.n_cand_m = std::max(hh.n_cand_m, q.n_cand_m);
             hh.n_cand_r = std::max(hh.n_cand_r, q.n_cand_r); hh.n_cand_d = std::max(hh.n_cand_d, q.n_cand_d);
@@ -1238,11 +1212,10 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     const ScanCounters& c = host_counters_;
     if (c.error & 1) throw HipError{"scan: a candidate matches more than 65535 glob patterns (the hit record counts pattern ids in 16 bits)"};
     if (c.error & 4) throw HipError{"scan: a candidate is longer than 16 MiB (24-bit length field)"};
-    const double t_counters = since();
     if (trace) {
-        ScanCounters t = host_slices_[0];
+        ScanCounters t = host_slices_.p[0];
         for (int k = 1; k < ns; ++k) {
-            const ScanCounters& s = host_slices_[k];
+            const ScanCounters& s = host_slices_.p[k];
             t.n_dom += s.n_dom; t.n_rare += s.n_rare; t.n_rare_dom += s.n_rare_dom; t.n_tok += s.n_tok; t.n_heavy += s.n_heavy; t.n_cand_a += s.n_cand_a;
             t.n_cand += s.n_cand; t.n_hits += s.n_hits; t.n_ids += s.n_ids; t.n_glob_work += s.n_glob_work;
         }
@@ -1264,6 +1237,14 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
         MXY_HIP(hipEventElapsedTime(&timing_.total_ms, ev_[0], ev_[4]));
         timing_.slices = ns;
     }
+}
+
+// Queues the copies of what the caller asked for on `stream` (raw hits; final records from the mirror, or through the copy path with
+// the optional sort; compact records; candidates) and points `out` at the pinned blocks. Returns the final records in the caller's
+// order where they lie in device memory.
+const FinalHit* Scanner::queue_record_copies(ScanOutput& out, bool want_cands, HitMode hit_mode, bool sorted, hipStream_t stream) {
+    const ScanCounters& c = host_counters_;
+    const int ns = n_slices_;
     out.hits.clear(); out.ids.clear(); out.cands.clear();
     out.fin = nullptr; out.fin_ids = nullptr; out.fin_offs = nullptr; out.n_fin = 0; out.n_fin_ids = 0;
     out.c4 = nullptr; out.n_c4 = 0;
@@ -1276,28 +1257,26 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     // D2H into pinned memory (pageable destinations run at a fraction of the PCIe rate)
     if (get_raw) {
         ensure_pinned((size_t)c.n_hits * sizeof(Hit));
-        MXY_HIP(hipMemcpyAsync(pinned_, w0.hits.p, (size_t)c.n_hits * sizeof(Hit), hipMemcpyDeviceToHost, stream));
+        MXY_HIP(hipMemcpyAsync(pinned_.p, w0.hits.p, (size_t)c.n_hits * sizeof(Hit), hipMemcpyDeviceToHost, stream));
         if (c.n_ids) {
             out.ids.resize(c.n_ids);
             MXY_HIP(hipMemcpyAsync(out.ids.data(), w0.ids.p, (size_t)c.n_ids * 4, hipMemcpyDeviceToHost, stream));
         }
     }
-    if (get_fin && !sorted && mirror_used_ && c.n_final <= mirror_cap_ && c.n_final_ids <= mirror_ids_cap_) {
+    if (get_fin && !sorted && mirror_used_ && c.n_final <= mirror_layout_.recs_cap && c.n_final_ids <= mirror_layout_.ids_cap) {
         // k_lookup (pack_record) has already written the records into pinned host memory
-        uint8_t* mb = (uint8_t*)mirror_;
-        out.fin = (const FinalHit*)mb; out.n_fin = c.n_final;
-        out.fin_ids = (const uint32_t*)(mb + (size_t)mirror_cap_ * sizeof(FinalHit));
-        out.fin_offs = (const long long*)(mb + (size_t)mirror_cap_ * sizeof(FinalHit) + (((size_t)mirror_ids_cap_ * 4 + 7) & ~(size_t)7));
-        out.n_fin_ids = c.n_final_ids;
+        const ResultArrays m = arrays_of(mirror_.p, mirror_layout_);
+        out.fin = m.recs; out.n_fin = c.n_final;
+        out.fin_ids = m.ids; out.fin_offs = m.offs; out.n_fin_ids = c.n_final_ids;
     } else if (get_fin) {
         if (mirror_used_ && !sorted) {  // did not fit: take the copy path now, have a larger mirror next time
-            const uint32_t want_r = std::max(mirror_cap_, c.n_final + c.n_final / 2), want_i = std::max(mirror_ids_cap_, c.n_final_ids + c.n_final_ids / 2);
+            const uint32_t want_r = std::max((uint32_t)mirror_layout_.recs_cap, c.n_final + c.n_final / 2), want_i = std::max((uint32_t)mirror_layout_.ids_cap, c.n_final_ids + c.n_final_ids / 2);
             mirror_used_ = false;
             ensure_mirror(want_r, want_i);
         }
-        const size_t hb = (size_t)c.n_final * sizeof(FinalHit), ib = (((size_t)c.n_final_ids * 4) + 7) & ~(size_t)7, ob = (size_t)c.n_final_ids * 8;
-        ensure_pinned(hb + ib + ob);
-        uint8_t* base = (uint8_t*)pinned_;
+        const ResultLayout lay{c.n_final, c.n_final_ids};   // exactly the records of this scan
+        ensure_pinned(lay.end());
+        const ResultArrays h = arrays_of(pinned_.p, lay);
         const FinalHit* src = final_.p;
         if (sorted) {
             const uint32_t n = c.n_final;
@@ -1308,37 +1287,45 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
             src = final_sorted_.p;
             dev_recs = src;
         }
-        MXY_HIP(hipMemcpyAsync(base, src, hb, hipMemcpyDeviceToHost, stream));
+        MXY_HIP(hipMemcpyAsync(h.recs, src, (size_t)c.n_final * sizeof(FinalHit), hipMemcpyDeviceToHost, stream));
         if (c.n_final_ids) {
-            MXY_HIP(hipMemcpyAsync(base + hb, final_ids_.p, (size_t)c.n_final_ids * 4, hipMemcpyDeviceToHost, stream));
-            MXY_HIP(hipMemcpyAsync(base + hb + ib, final_offs_.p, ob, hipMemcpyDeviceToHost, stream));
+            MXY_HIP(hipMemcpyAsync(h.ids, final_ids_.p, (size_t)c.n_final_ids * 4, hipMemcpyDeviceToHost, stream));
+            MXY_HIP(hipMemcpyAsync(h.offs, final_offs_.p, (size_t)c.n_final_ids * 8, hipMemcpyDeviceToHost, stream));
         }
-        out.fin = (const FinalHit*)base; out.n_fin = c.n_final;
-        out.fin_ids = (const uint32_t*)(base + hb); out.fin_offs = (const long long*)(base + hb + ib); out.n_fin_ids = c.n_final_ids;
+        out.fin = h.recs; out.n_fin = c.n_final;
+        out.fin_ids = h.ids; out.fin_offs = h.offs; out.n_fin_ids = c.n_final_ids;
     }
     if (last_.lookup && hit_mode == HITS_FINAL && compact_ && c.n_c4) {
-        if (had_mirror && !sorted && c.n_c4 <= mirror_c4_cap_) out.c4 = mirror_c4_;   // written by the kernels
+        if (had_mirror && !sorted && c.n_c4 <= mirror_c4_.n) out.c4 = mirror_c4_.p;   // written by the kernels
         else {
-            if (had_mirror) { mirror_used_ = false; ensure_mirror_c4(c.n_c4 + c.n_c4 / 2); }   // a larger mirror next time
-            if (pinned_c4_n_ < c.n_c4) {
-                if (pinned_c4_) (void)hipHostFree(pinned_c4_);
-                pinned_c4_ = nullptr;
-                pinned_c4_n_ = (size_t)c.n_c4 + c.n_c4 / 4 + 1024;
-                MXY_HIP(hipHostMalloc((void**)&pinned_c4_, pinned_c4_n_ * sizeof(uint2), hipHostMallocDefault));
-            }
-            MXY_HIP(hipMemcpyAsync(pinned_c4_, c4_.p, (size_t)c.n_c4 * sizeof(uint2), hipMemcpyDeviceToHost, stream));
-            out.c4 = pinned_c4_;
+            if (had_mirror) { mirror_used_ = false; mirror_c4_.ensure(c.n_c4 + c.n_c4 / 2); }   // a larger mirror next time
+            pinned_c4_.ensure(c.n_c4, c.n_c4 / 4 + 1024);
+            MXY_HIP(hipMemcpyAsync(pinned_c4_.p, c4_.p, (size_t)c.n_c4 * sizeof(uint2), hipMemcpyDeviceToHost, stream));
+            out.c4 = pinned_c4_.p;
         }
         out.n_c4 = c.n_c4;
     }
-    const bool dedup = want_cands && unique_;
-    if (want_cands && !dedup && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
+    if (want_cands && !unique_ && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
         out.cands.resize((size_t)c.n_cand_a + c.n_cand);
         if (c.n_cand_a) MXY_HIP(hipMemcpyAsync(out.cands.data(), w0.cands_a.p, (size_t)c.n_cand_a * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
         if (c.n_cand) MXY_HIP(hipMemcpyAsync(out.cands.data() + c.n_cand_a, w0.cands.p, (size_t)c.n_cand * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     }
+    return dev_recs;
+}
+
+// The passes behind the scan, each over the records where they lie: line context, hit tally, segments (which reads the line context of
+// this fetch), distinct texts.
+void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool want_cands, HitMode hit_mode, bool trace, hipStream_t stream) {
+    const ScanCounters& c = host_counters_;
+    Work& w0 = work_[0];
+    const HitBatch batch{last_.ptr, last_.len, dev_recs, c.n_final, c4_.p, compact_ ? c.n_c4 : 0u};
+    const bool to_host = hit_mode == HITS_FINAL;
     out.has_lines = false; out.fin_lines = nullptr; out.c4_lines = nullptr; out.lines_with_matches = 0;
-    if (last_.lines && last_.lookup && !single_) resolve_lines(out, dev_recs, hit_mode == HITS_FINAL, stream);
+    if (last_.lines && last_.lookup && !single_) {
+        if (!lines_) lines_ = std::make_unique<LineContext>();
+        lines_->resolve(batch, to_host, n_cu_, profile_, stream);
+        out.has_lines = true;
+    }
     // hit tally: the records of the batch are counted where they lie, once per fetch — behind the regrow loop and the spill pass. With
     // set_profile or MATCHY_AMD_TRACE the pass times its kernels (one more host wait between them)
     if (tally_on_ && last_.lookup && !single_) {
@@ -1353,23 +1340,35 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     }
     // segmented scan: the records are attributed to the caller's segments where they lie, behind the line context it builds on
     out.has_segments = false; out.segments = nullptr; out.n_segments = 0; out.seg_of_fin = nullptr; out.seg_of_c4 = nullptr;
-    if (seg_active_ && last_.lookup && !single_) resolve_segments(out, dev_recs, hit_mode == HITS_FINAL, stream);
+    if (segments_ && segments_->active() && last_.lookup && !single_) {
+        const SegLines with_lines = out.has_lines ? SegLines{lines_->prefix(), lines_->set(), lines_->set_slots()} : SegLines{};
+        segments_->resolve(batch, with_lines, to_host, profile_, stream);
+        out.has_segments = true;
+    }
     // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
-    if (dedup) {
+    if (want_cands && unique_) {
         distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);
         if (trace) fprintf(stderr, "[matchy_amd] distinct: %zu of %u candidates are new, dedup %.3f ms behind %.3f ms of extraction kernels\n", out.cands.size(), c.cand_true,
                            distinct_->last_ms(), timing_.total_ms);
     }
+}
+
+// The wait for everything queued, what the passes read behind it, and the padding slots of partially filled chunks dropped.
+void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, hipStream_t stream) {
+    const ScanCounters& c = host_counters_;
+    const bool get_raw = last_.lookup && hit_mode == HITS_RAW && c.n_hits;
     wait_stream(stream, last_.fork);
     if (out.has_lines) {
-        out.lines_with_matches = *reinterpret_cast<const uint32_t*>(pinned_lines_);
-        if (profile_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&line_ms_[k], ev_line_[k], ev_line_[k + 1]));
+        const LineContext::Result r = lines_->finish();
+        out.lines_with_matches = r.lines_with_matches; out.fin_lines = r.fin_lines; out.c4_lines = r.c4_lines;
     }
-    if (out.has_segments) finish_segments(out);
-    if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
+    if (out.has_segments) {
+        const SegmentPass::Result r = segments_->finish();
+        out.segments = r.segments; out.n_segments = r.n_segments; out.seg_of_fin = r.seg_of_fin; out.seg_of_c4 = r.seg_of_c4;
+    }
     // drop the padding slots of partially filled chunks
     if (get_raw) {
-        const Hit* ph = (const Hit*)pinned_;
+        const Hit* ph = (const Hit*)pinned_.p;
         out.hits.reserve(c.hits_true);
         for (size_t r = 0; r < c.n_hits; ++r) if (ph[r].kind != 0xFF) out.hits.push_back(ph[r]);
     }
@@ -1382,142 +1381,32 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     if (want_cands) for (const Candidate& cd : out.cands) { uint32_t ty = cd.len_type >> 24; if (ty < IT_COUNT) out.by_type[ty]++; }
 }
 
-// Line context of the last scan (line_index.hip): runs once per fetch, behind the regrow loop — a rescan never counts the batch twice —
-// and behind the sort, over the records in the order the caller gets them. Every array is written again for exactly the records of
-// this scan. to_host: the line records come back into pinned memory like the hit records; otherwise they stay on the device and only
-// the distinct-line count crosses the bus.
-void Scanner::resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream) {
-    const ScanCounters& c = host_counters_;
-    const uint32_t n_fin = c.n_final, n_c4 = compact_ ? c.n_c4 : 0u;
-    const size_t n = (size_t)n_fin + n_c4;
-    const uint32_t tiles = line_tiles(last_.len), chunks = line_chunks(tiles);
-    if (line_counts_.n < tiles || !line_prefix_.p) { line_counts_.alloc(grown(tiles)); line_prefix_.alloc(line_counts_.n + 1); }
-    if (line_chunks_.n < chunks) line_chunks_.alloc((size_t)chunks + 64);
-    if (!line_ctr_.p) line_ctr_.alloc(1);
-    if (line_recs_.n < n_fin) line_recs_.alloc(grown(n_fin));
-    if (line_c4_.n < n_c4) line_c4_.alloc(grown(n_c4));
-    size_t slots = 1024;
-    while (slots < 2 * n) slots <<= 1;
-    if (line_set_.n < slots) line_set_.alloc(slots);
-    line_set_slots_ = n ? slots : 0;
-    const size_t head = sizeof(LineCounters), want = head + (to_host ? n * sizeof(LineRec) : 0);
-    if (pinned_lines_bytes_ < want) {
-        if (pinned_lines_) (void)hipHostFree(pinned_lines_);
-        pinned_lines_ = nullptr;
-        pinned_lines_bytes_ = want + want / 4 + (1 << 16);
-        MXY_HIP(hipHostMalloc(&pinned_lines_, pinned_lines_bytes_, hipHostMallocDefault));
-    }
-    if (profile_) {
-        for (auto& e : ev_line_) if (!e) MXY_HIP(hipEventCreate(&e));
-        MXY_HIP(hipEventRecord(ev_line_[0], stream));
-    }
-    MXY_HIP(hipMemsetAsync(line_ctr_.p, 0, sizeof(LineCounters), stream));
-    if (n) MXY_HIP(hipMemsetAsync(line_set_.p, 0xFF, slots * 4, stream));
-    MXY_HIP(line_index_build(last_.ptr, last_.len, line_counts_.p, line_chunks_.p, line_prefix_.p, n_cu_, stream, profile_ ? ev_line_[1] : nullptr));
-    if (profile_) { if (!tiles) MXY_HIP(hipEventRecord(ev_line_[1], stream)); MXY_HIP(hipEventRecord(ev_line_[2], stream)); }
-    MXY_HIP(line_index_resolve(last_.ptr, last_.len, line_prefix_.p, recs, sizeof(FinalHit), n_fin, line_recs_.p, line_set_.p, (uint32_t)slots, &line_ctr_.p->distinct, stream));
-    MXY_HIP(line_index_resolve(last_.ptr, last_.len, line_prefix_.p, c4_.p, sizeof(uint2), n_c4, line_c4_.p, line_set_.p, (uint32_t)slots, &line_ctr_.p->distinct, stream));
-    if (profile_) MXY_HIP(hipEventRecord(ev_line_[3], stream));
-    uint8_t* pb = (uint8_t*)pinned_lines_;
-    MXY_HIP(hipMemcpyAsync(pb, line_ctr_.p, sizeof(LineCounters), hipMemcpyDeviceToHost, stream));
-    if (to_host) {
-        if (n_fin) MXY_HIP(hipMemcpyAsync(pb + head, line_recs_.p, (size_t)n_fin * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
-        if (n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)n_fin * sizeof(LineRec), line_c4_.p, (size_t)n_c4 * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
-        out.fin_lines = n_fin ? (const LineRec*)(pb + head) : nullptr;
-        out.c4_lines = n_c4 ? (const LineRec*)(pb + head) + n_fin : nullptr;
-    }
-    out.has_lines = true;
+void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMode hit_mode, bool sorted) {
+    const bool trace = !single_ && getenv("MATCHY_AMD_TRACE");
+    MXY_HIP(hipSetDevice(ddb_->device));   // regrown buffers must land on this scanner's device whatever thread calls
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+    settle_counters(trace, stream);
+    const double t_counters = since();
+    report_counters(out, trace);
+    const FinalHit* dev_recs = queue_record_copies(out, want_cands, hit_mode, sorted, stream);
+    queue_post_passes(out, dev_recs, want_cands, hit_mode, trace, stream);
+    finish_fetch(out, want_cands, hit_mode, stream);
+    if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
 }
 
-// Segmented scans (segments.hip). The table is the caller's until arm_segments() takes it for one scan.
+// Segmented scans (segments.h). The table is the caller's until arm_segments() takes it for one scan.
 void Scanner::set_segments(const uint32_t* starts, size_t n) {
-    if (!starts || !n) { seg_pending_.clear(); return; }
-    seg_pending_.assign(starts, starts + n);
+    if (!segments_ && starts && n) segments_ = std::make_unique<SegmentPass>();
+    if (segments_) segments_->set(starts, n);
 }
 
 void Scanner::arm_segments(size_t len, hipStream_t stream, bool upload) {
-    seg_active_ = false;
-    seg_index_base_ = 0;
-    seg_starts_.clear();
-    seg_starts_.swap(seg_pending_);   // consumed whether the scan succeeds or not
-    if (seg_starts_.empty()) return;
-    std::string bad;
-    if (seg_starts_.size() > 0x7FFFFFFFull) bad = "segments: too many segments";
-    else if (seg_starts_[0] != 0) bad = "segments: starts[0] must be 0";
-    for (size_t s = 0; bad.empty() && s < seg_starts_.size(); ++s) {
-        if (seg_starts_[s] > len) bad = "segments: start of segment " + std::to_string(s) + " lies behind the end of the buffer";
-        else if (s && seg_starts_[s] < seg_starts_[s - 1]) bad = "segments: start of segment " + std::to_string(s) + " lies in front of its predecessor's";
-    }
-    if (!bad.empty()) { seg_starts_.clear(); throw ParamError{bad}; }
-    seg_active_ = true;
-    if (upload) upload_segments(stream);
-}
-
-// The table of the scan about to be launched goes to the device at submit, in front of the scan's kernels: the copy of a pageable
-// vector is staged by the runtime, and behind the scan it would sit on the critical path of fetch().
-void Scanner::upload_segments(hipStream_t stream) {
+    if (!segments_) return;
+    segments_->arm(len);
+    if (!segments_->active() || !upload) return;
     MXY_HIP(hipSetDevice(ddb_->device));
-    const size_t n = seg_starts_.size();
-    if (seg_starts_dev_.n < n) {
-        seg_starts_dev_.alloc(grown((uint32_t)n)); seg_line_base_.alloc(seg_starts_dev_.n);
-        seg_table_.alloc(sizeof(SegHeader) + seg_starts_dev_.n * sizeof(SegmentRec));
-    }
-    MXY_HIP(hipMemcpyAsync(seg_starts_dev_.p, seg_starts_.data(), n * 4, hipMemcpyHostToDevice, stream));
-}
-
-// Segments of the last scan: runs once per fetch behind the regrow loop, the spill pass, the sort and resolve_lines (whose prefix array
-// and distinct-line set it reads), over the records in the order the caller gets them. to_host: the segment indices come back into
-// pinned memory like the hit records; otherwise they stay on the device and only header + table cross the bus, in one copy.
-void Scanner::resolve_segments(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream) {
-    const ScanCounters& c = host_counters_;
-    const uint32_t n_fin = c.n_final, n_c4 = compact_ ? c.n_c4 : 0u, n = (uint32_t)seg_starts_.size();
-    const size_t n_recs = (size_t)n_fin + n_c4;
-    if (!seg_sample_.p) seg_sample_.alloc(SEG_SAMPLES);
-    if (seg_of_fin_.n < n_fin) seg_of_fin_.alloc(grown(n_fin));
-    if (seg_of_c4_.n < n_c4) seg_of_c4_.alloc(grown(n_c4));
-    const size_t head = sizeof(SegHeader) + (size_t)n * sizeof(SegmentRec), want = head + (to_host ? n_recs * 4 : 0);
-    if (pinned_seg_bytes_ < want) {
-        if (pinned_seg_) (void)hipHostFree(pinned_seg_);
-        pinned_seg_ = nullptr;
-        pinned_seg_bytes_ = want + want / 4 + (1 << 16);
-        MXY_HIP(hipHostMalloc(&pinned_seg_, pinned_seg_bytes_, hipHostMallocDefault));
-    }
-    if (profile_) {
-        for (auto& e : ev_seg_) if (!e) MXY_HIP(hipEventCreate(&e));
-        MXY_HIP(hipEventRecord(ev_seg_[0], stream));
-    }
-    SegHeader* hdr = reinterpret_cast<SegHeader*>(seg_table_.p);
-    SegmentRec* table = reinterpret_cast<SegmentRec*>(seg_table_.p + sizeof(SegHeader));
-    MXY_HIP(segments_build(last_.ptr, last_.len, seg_starts_dev_.p, n, out.has_lines ? line_prefix_.p : nullptr, hdr, table, seg_line_base_.p, seg_sample_.p, stream));
-    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[1], stream));
-    MXY_HIP(segments_attribute(recs, sizeof(FinalHit), n_fin, last_.len, seg_starts_dev_.p, n, seg_sample_.p, seg_of_fin_.p, table, stream));
-    MXY_HIP(segments_attribute(c4_.p, sizeof(uint2), n_c4, last_.len, seg_starts_dev_.p, n, seg_sample_.p, seg_of_c4_.p, table, stream));
-    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[2], stream));
-    if (out.has_lines && line_set_slots_) MXY_HIP(segments_count_lines(line_set_.p, (uint32_t)line_set_slots_, seg_line_base_.p, n, table, stream));
-    if (profile_) MXY_HIP(hipEventRecord(ev_seg_[3], stream));
-    uint8_t* pb = (uint8_t*)pinned_seg_;
-    MXY_HIP(hipMemcpyAsync(pb, seg_table_.p, head, hipMemcpyDeviceToHost, stream));
-    if (to_host) {
-        if (n_fin) MXY_HIP(hipMemcpyAsync(pb + head, seg_of_fin_.p, (size_t)n_fin * 4, hipMemcpyDeviceToHost, stream));
-        if (n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)n_fin * 4, seg_of_c4_.p, (size_t)n_c4 * 4, hipMemcpyDeviceToHost, stream));
-        out.seg_of_fin = n_fin ? (const uint32_t*)(pb + head) : nullptr;
-        out.seg_of_c4 = n_c4 ? (const uint32_t*)(pb + head) + n_fin : nullptr;
-    }
-    out.segments = reinterpret_cast<const SegmentRec*>(pb + sizeof(SegHeader));
-    out.n_segments = n;
-    out.has_segments = true;
-}
-
-// behind the wait of fetch(): the error word, and the lines of every segment from neighbouring line_base values and the batch's total
-void Scanner::finish_segments(ScanOutput& out) {
-    uint8_t* pb = (uint8_t*)pinned_seg_;
-    const SegHeader* hdr = reinterpret_cast<const SegHeader*>(pb);
-    SegmentRec* t = reinterpret_cast<SegmentRec*>(pb + sizeof(SegHeader));
-    const size_t n = out.n_segments;
-    if (profile_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&seg_ms_[k], ev_seg_[k], ev_seg_[k + 1]));
-    if (hdr->bad != SEG_NONE)
-        throw ParamError{"segments: segment " + std::to_string((size_t)hdr->bad + seg_index_base_) + " does not end in a newline (every non-empty segment in front of the last must)"};
-    if (out.has_lines) for (size_t s = 0; s < n; ++s) t[s].lines = (s + 1 < n ? t[s + 1].line_base : hdr->total_nl) - t[s].line_base;
+    segments_->upload(stream);
 }
 
 size_t host_piece_bytes() {
@@ -1564,12 +1453,13 @@ void Scanner::lookup_one(const std::string& text, Candidate c, ScanOutput& out) 
     launch_[0].lp = lp;   // fetch() launches the spill pass from here if the candidate spilled
     n_slices_ = 1; spill_done_ = false;
     last_.lookup = true; last_.ptr = staging_.p; last_.len = (uint32_t)text.size();
-    bool prof = profile_;
-    profile_ = false;
-    single_ = true;
-    try { fetch(out, false, nullptr, HITS_RAW); } catch (...) { single_ = false; profile_ = prof; throw; }
-    single_ = false;
-    profile_ = prof;
+    // a single query is fetched untimed and as raw hits; both switches go back however fetch() ends
+    struct Single {
+        Scanner& s; const bool prof;
+        explicit Single(Scanner& sc) : s(sc), prof(sc.profile_) { s.profile_ = false; s.single_ = true; }
+        ~Single() { s.single_ = false; s.profile_ = prof; }
+    } single(*this);
+    fetch(out, false, nullptr, HITS_RAW);
 }
 
 void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_cands, ScanOutput& out, std::vector<uint64_t>* cand_bases,
@@ -1581,7 +1471,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     MXY_HIP(hipSetDevice(ddb_->device));
     // copies and kernels of a host-buffer scan go to a stream of this scanner's own, so that several scanners on one
     // device (one per host thread, `matchy match --devices 0,0`) overlap one batch's transfer with another's kernels
-    if (!host_stream_) MXY_HIP(hipStreamCreateWithFlags(&host_stream_, hipStreamNonBlocking));
+    host_stream_.create(hipStreamNonBlocking);
     out = ScanOutput();
     size_t pos = 0;
     std::vector<Candidate> all_cands;
@@ -1591,12 +1481,11 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     // segmented scan: every piece gets the starts that intersect it, clamped and shifted; a piece ends at a line end, so the per-segment
     // figures of the pieces add up, and the indices go back into the caller's table
     std::vector<uint32_t> seg_all;
-    if (lookup) {
+    if (lookup && segments_) {
         arm_segments(len, host_stream_, false);   // the whole table; every piece uploads its own below
-        if (seg_active_) seg_all.swap(seg_starts_);
-        seg_active_ = false;
+        seg_all = segments_->take();
     }
-    struct SegOff { Scanner& s; ~SegOff() { s.seg_active_ = false; s.seg_index_base_ = 0; } } seg_off{*this};
+    const SegmentPass::OffAtExit seg_off{segments_.get()};
     if (!seg_all.empty()) {
         out.seg_own.resize(seg_all.size());
         for (size_t s = 0; s < seg_all.size(); ++s) {
@@ -1648,11 +1537,8 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             const size_t at_pos = (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)pos) - seg_all.begin());
             seg_first = at_pos < seg_all.size() && seg_all[at_pos] == pos ? at_pos : at_pos - 1;
             const size_t seg_last = pos + n >= len ? seg_all.size() - 1 : (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)(pos + n)) - seg_all.begin()) - 1;
-            seg_starts_.resize(seg_last - seg_first + 1);
-            for (size_t k = 0; k < seg_starts_.size(); ++k) seg_starts_[k] = std::max(seg_all[seg_first + k], (uint32_t)pos) - (uint32_t)pos;
-            seg_active_ = true;
-            seg_index_base_ = (uint32_t)seg_first;
-            upload_segments(host_stream_);
+            segments_->arm_piece(seg_all, seg_first, seg_last, (uint32_t)pos);
+            segments_->upload(host_stream_);
         }
         scan_device(rq, host_stream_);
         ScanOutput part;

@@ -8,7 +8,9 @@
 #include <vector>
 
 #include "db_image.h"
+#include "hip_owners.h"
 #include "line_index.h"
+#include "result_layout.h"
 #include "scan_types.h"
 #include "segments.h"
 
@@ -35,15 +37,6 @@ class DistinctSet;   // distinct.h
 class HitTally;      // tally.h
 struct TallyEntry;
 
-struct HipError { std::string what; };
-// what the caller handed in cannot be scanned (a segment table that breaks its rules): nothing is wrong with the device or the scanner
-struct ParamError { std::string what; };
-#define MXY_HIP(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) throw ::mxy::HipError{std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-    } while (0)
-
 // Public-suffix set loaded from the PSLB container (tools/gen_psl.py), shared by all handles.
 struct PslHost {
     std::vector<std::string> suffixes;
@@ -54,23 +47,6 @@ struct PslHost {
     uint32_t mask = 0, max_tld_len = 0, max_suffix_len = 0;
     uint32_t tld_first[8] = {0};
     static const PslHost& get();  // throws std::runtime_error if the container cannot be found
-};
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void alloc(size_t count) {
-        free();
-        if (count) MXY_HIP(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-    }
-    void upload(const std::vector<T>& v) { alloc(v.size()); if (!v.empty()) MXY_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)); }
-    void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    ~DevBuf() { free(); }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
 };
 
 // Device-resident image of one database on one GPU (uploaded once, at first use).
@@ -220,10 +196,10 @@ public:
     void set_line_context(bool on) { line_ctx_ = on; }
     bool line_context() const { return line_ctx_; }
     // the line records of the last scan with line context as the kernel left them in device memory, parallel to device_final() / the compact array
-    const LineRec* device_lines() const { return line_recs_.p; }
-    const LineRec* device_c4_lines() const { return line_c4_.p; }
+    const LineRec* device_lines() const { return lines_ ? lines_->device_lines() : nullptr; }
+    const LineRec* device_c4_lines() const { return lines_ ? lines_->device_c4_lines() : nullptr; }
     // with set_profile: milliseconds of the streaming count kernel, of the prefix sum, and of resolve + distinct set of the last fetch
-    void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = line_ms_[k]; }
+    void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (lines_) lines_->timing(out_ms); }
     // Segmented scans (segments.hip): `starts` (copied) describes the buffer of the NEXT lookup scan as n segments — starts[0] == 0,
     // non-decreasing, every start <= the scan's length, every non-empty segment in front of the last ends in '\n'. n == 0 or null
     // clears a pending table. arm_segments(len) is what the entries of a lookup scan call before scan_device: it consumes the pending
@@ -232,10 +208,10 @@ public:
     // fetch() then attributes the records on the device and throws ParamError when a segment breaks the newline rule.
     void set_segments(const uint32_t* starts, size_t n);
     void arm_segments(size_t len, hipStream_t stream, bool upload = true);   // upload false: scan_host, which uploads piece by piece
-    const uint32_t* device_segment_of() const { return seg_of_fin_.p; }
-    const uint32_t* device_segment_of_c4() const { return seg_of_c4_.p; }
+    const uint32_t* device_segment_of() const { return segments_ ? segments_->device_of_fin() : nullptr; }
+    const uint32_t* device_segment_of_c4() const { return segments_ ? segments_->device_of_c4() : nullptr; }
     // with set_profile: milliseconds of the segment pass, the record passes and the lines-with-matches pass of the last fetch
-    void segment_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = seg_ms_[k]; }
+    void segment_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (segments_) segments_->timing(out_ms); }
     // Distinct candidate texts (distinct.hip), for extractor handles: while on, a fetch with want_cands returns only the candidates whose
     // text this scanner has not returned since it was created or reset — the set lives in device memory across scans and pieces, and only
     // the survivors are copied back. Off (the default), nothing of it is allocated, launched or copied.
@@ -312,6 +288,12 @@ private:
     void launch_one_stream(hipStream_t stream);
     void ensure_dom_stream();       // the fourth stream and its events, created at first use
     bool rare_possible() const { return (flags_ & (EX_HASHES | EX_BITCOIN | EX_ETHEREUM | EX_MONERO)) != 0; }
+    // the steps of fetch(), in its order
+    void settle_counters(bool trace, hipStream_t stream);
+    void report_counters(ScanOutput& out, bool trace);
+    const FinalHit* queue_record_copies(ScanOutput& out, bool want_cands, HitMode hit_mode, bool sorted, hipStream_t stream);
+    void queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool want_cands, HitMode hit_mode, bool trace, hipStream_t stream);
+    void finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, hipStream_t stream);
     // visits every (work list, counter) pair of a slice for fetch's overflow test and regrow
     template <class F> void each_list(Work& w, const ScanCounters& s, F&& f);
     bool spill_done_ = false;
@@ -329,21 +311,21 @@ private:
     ScanRequest last_;              // of the last scan_device (fetch runs it again after regrowing the work lists)
     std::shared_ptr<const DbImage> img_;
     std::shared_ptr<DeviceDb> ddb_;
-    hipStream_t host_stream_ = nullptr;   // scan_host: this scanner's own non-blocking stream
+    Stream host_stream_;            // scan_host: this scanner's own non-blocking stream, created by the first scan_host
     uint32_t flags_, min_labels_;
     // the lookups of k_anchor's IPv4 candidates run on this stream beside the validation kernels (fork after k_anchor, join
     // before the counters are read back)
-    hipStream_t aux_stream_ = nullptr;
-    hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
+    Stream aux_stream_;
+    Event ev_fork_, ev_join_;
     // a third stream: k_validate's part that does not depend on k_validate_dom (tokens, IPv6 / e-mail anchors) and k_rare behind it
-    hipStream_t aux2_stream_ = nullptr;
-    hipEvent_t ev_join2_ = nullptr;
+    Stream aux2_stream_;
+    Event ev_join2_;
     // sliced scans: the k_validate_dom -> k_validate -> k_lookup chain of every slice runs on a stream of its own too (the scan's
     // stream only carries the k_anchor launches), one "k_anchor of slice i is done" and one "misc stream of slice i is done" event
-    // per slice
-    hipStream_t dom_stream_ = nullptr;
-    hipEvent_t ev_anchor_[MAX_SLICES] = {}, ev_misc_[MAX_SLICES] = {};
-    hipEvent_t ev_join3_ = nullptr, ev_dom_ = nullptr, ev_v1_ = nullptr;
+    // per slice (all created at first use)
+    Stream dom_stream_;
+    Event ev_anchor_[MAX_SLICES], ev_misc_[MAX_SLICES];
+    Event ev_join3_, ev_dom_, ev_v1_;
     DevBuf<FinalHit> final_;
     DevBuf<uint32_t> final_ids_;
     DevBuf<long long> final_offs_;
@@ -352,62 +334,34 @@ private:
     DevBuf<uint8_t> sort_tmp_;
     DevBuf<FinalHit> final_sorted_;
     DevBuf<ScanCounters> counters_;            // MAX_SLICES entries
-    // line context (line_index.hip), grown on demand and reused between scans like the sort buffers: '\n' counts per tile, sums per
-    // chunk of tiles, exclusive prefix; one line record per final / compact record; the distinct-line set and its counter; the pinned
-    // block the line records (and the counter, in front of them) come back in
+    // the passes behind the scan, each created at first use: line context (line_index.h; line_ctx_ is what scan_host asks for),
+    // segmented scans (segments.h), distinct texts (distinct.h), hit tally (tally.h)
     bool line_ctx_ = false;
-    DevBuf<uint32_t> line_counts_, line_chunks_, line_prefix_, line_set_;
-    DevBuf<LineRec> line_recs_, line_c4_;
-    DevBuf<LineCounters> line_ctr_;
-    void* pinned_lines_ = nullptr;
-    size_t pinned_lines_bytes_ = 0;
-    hipEvent_t ev_line_[4] = {nullptr, nullptr, nullptr, nullptr};
-    float line_ms_[3] = {0, 0, 0};
-    void resolve_lines(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
-    size_t line_set_slots_ = 0;                // slots of line_set_ the last resolve_lines used (0: it had no records)
-    // segmented scans (segments.hip), grown on demand and reused between scans like the line buffers: the pending table and the one of
-    // the scan in flight, its copy on the device, header + table in one block, line_base per segment, the sample table, one segment
-    // index per final / compact record, and the pinned block header, table and (HITS_FINAL) the indices come back in
-    std::vector<uint32_t> seg_pending_, seg_starts_;
-    bool seg_active_ = false;
-    uint32_t seg_index_base_ = 0;              // scan_host: the caller's index of the first segment of the piece in flight
-    DevBuf<uint32_t> seg_starts_dev_, seg_line_base_, seg_sample_, seg_of_fin_, seg_of_c4_;
-    DevBuf<uint8_t> seg_table_;
-    void* pinned_seg_ = nullptr;
-    size_t pinned_seg_bytes_ = 0;
-    hipEvent_t ev_seg_[4] = {nullptr, nullptr, nullptr, nullptr};
-    float seg_ms_[3] = {0, 0, 0};
-    void upload_segments(hipStream_t stream);   // seg_starts_ to the device, queued in front of the scan
-    void resolve_segments(ScanOutput& out, const FinalHit* recs, bool to_host, hipStream_t stream);
-    void finish_segments(ScanOutput& out);
+    std::unique_ptr<LineContext> lines_;       // created by the first fetch of a scan with line context
+    std::unique_ptr<SegmentPass> segments_;    // created by the first set_segments with a table
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
     bool tally_on_ = false;
     std::unique_ptr<HitTally> tally_;          // created by the first set_tally(true), kept (with its counts) while the feature is switched off
     DevBuf<uint32_t> spill_scratch_;           // per-thread scratch of k_lookup_spill (allocated when a scan first spills)
     DevBuf<uint8_t> staging_;  // scan_host only
-    // pinned mirror of the final records written by the lookup kernels themselves: FinalHit[mirror_cap_] | u32 ids[mirror_ids_cap_] | i64 offs[..]
-    void* mirror_ = nullptr;
-    uint32_t mirror_cap_ = 0, mirror_ids_cap_ = 0;
+    // pinned mirror of the final records written by the lookup kernels themselves, laid out by mirror_layout_ (result_layout.h)
+    PinnedBuf<uint8_t> mirror_;
+    ResultLayout mirror_layout_;
     bool mirror_used_ = false;
     void ensure_mirror(uint32_t recs, uint32_t ids);
     // compact IPv4 records (scan_device `compact`): device array, pinned mirror written by the kernels, pinned block of the copy path
     DevBuf<uint2> c4_;
-    uint2* mirror_c4_ = nullptr;
-    uint32_t mirror_c4_cap_ = 0;
-    void ensure_mirror_c4(uint32_t recs);
-    uint2* pinned_c4_ = nullptr;
-    size_t pinned_c4_n_ = 0;
+    PinnedBuf<uint2> mirror_c4_, pinned_c4_;
     bool compact_ = false;   // of the last scan_device: in effect
-    void* pinned_ = nullptr;   // one pinned block: FinalHit[n] | u32 ids[m] | i64 offs[m]  (or Hit[n] for HITS_RAW)
-    size_t pinned_bytes_ = 0;
-    void ensure_pinned(size_t bytes);
+    PinnedBuf<uint8_t> pinned_;   // one pinned block: a ResultLayout for the counts of the fetch (or Hit[n] for HITS_RAW)
+    void ensure_pinned(size_t bytes) { pinned_.ensure(bytes, bytes / 4 + (1 << 16)); }
     ScanCounters host_counters_{};             // the slices' counters summed (list counters: of slice 0 for one-slice scans)
-    ScanCounters* host_slices_ = nullptr;      // pinned: MAX_SLICES counter blocks as read back
+    PinnedBuf<ScanCounters> host_slices_;      // MAX_SLICES counter blocks as read back
     bool last_forked_ = false;
     bool single_ = false;
     bool profile_ = false;
-    hipEvent_t ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    Event ev_[5];
     ScanTiming timing_;
     int n_cu_ = 256;
 };

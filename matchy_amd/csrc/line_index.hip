@@ -238,4 +238,49 @@ hipError_t line_index_resolve(const uint8_t* data, uint32_t len, const uint32_t*
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ host driver
+void LineContext::resolve(const HitBatch& b, bool to_host, int n_cu, bool profile, hipStream_t stream) {
+    auto grown = [](uint32_t n) { return (size_t)n + n / 4 + 1024; };
+    const size_t n = (size_t)b.n_fin + b.n_c4;
+    const uint32_t tiles = line_tiles(b.len), chunks = line_chunks(tiles);
+    if (counts_.n < tiles || !prefix_.p) { counts_.alloc(grown(tiles)); prefix_.alloc(counts_.n + 1); }
+    if (chunks_.n < chunks) chunks_.alloc((size_t)chunks + 64);
+    if (!ctr_.p) ctr_.alloc(1);
+    if (recs_.n < b.n_fin) recs_.alloc(grown(b.n_fin));
+    if (c4_.n < b.n_c4) c4_.alloc(grown(b.n_c4));
+    size_t slots = 1024;
+    while (slots < 2 * n) slots <<= 1;
+    if (set_.n < slots) set_.alloc(slots);
+    set_slots_ = n ? (uint32_t)slots : 0u;
+    const size_t head = sizeof(LineCounters), want = head + (to_host ? n * sizeof(LineRec) : 0);
+    pinned_.ensure(want, want / 4 + (1 << 16));
+    timed_ = profile;
+    if (profile) {
+        for (Event& e : ev_) e.create();
+        MXY_HIP(hipEventRecord(ev_[0], stream));
+    }
+    MXY_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(LineCounters), stream));
+    if (n) MXY_HIP(hipMemsetAsync(set_.p, 0xFF, slots * 4, stream));
+    MXY_HIP(line_index_build(b.data, b.len, counts_.p, chunks_.p, prefix_.p, n_cu, stream, profile ? (hipEvent_t)ev_[1] : nullptr));
+    if (profile) { if (!tiles) MXY_HIP(hipEventRecord(ev_[1], stream)); MXY_HIP(hipEventRecord(ev_[2], stream)); }
+    MXY_HIP(line_index_resolve(b.data, b.len, prefix_.p, b.fin, 16, b.n_fin, recs_.p, set_.p, (uint32_t)slots, &ctr_.p->distinct, stream));
+    MXY_HIP(line_index_resolve(b.data, b.len, prefix_.p, b.c4, 8, b.n_c4, c4_.p, set_.p, (uint32_t)slots, &ctr_.p->distinct, stream));
+    if (profile) MXY_HIP(hipEventRecord(ev_[3], stream));
+    uint8_t* pb = pinned_.p;
+    MXY_HIP(hipMemcpyAsync(pb, ctr_.p, sizeof(LineCounters), hipMemcpyDeviceToHost, stream));
+    pending_ = Result{};
+    if (to_host) {
+        if (b.n_fin) MXY_HIP(hipMemcpyAsync(pb + head, recs_.p, (size_t)b.n_fin * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
+        if (b.n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)b.n_fin * sizeof(LineRec), c4_.p, (size_t)b.n_c4 * sizeof(LineRec), hipMemcpyDeviceToHost, stream));
+        pending_.fin_lines = b.n_fin ? (const LineRec*)(pb + head) : nullptr;
+        pending_.c4_lines = b.n_c4 ? (const LineRec*)(pb + head) + b.n_fin : nullptr;
+    }
+}
+
+LineContext::Result LineContext::finish() {
+    pending_.lines_with_matches = reinterpret_cast<const LineCounters*>(pinned_.p)->distinct;
+    if (timed_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&ms_[k], ev_[k], ev_[k + 1]));
+    return pending_;
+}
+
 }  // namespace mxy

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 
 #include "lds_aggregator.h"
 #include "line_index.h"
@@ -174,6 +175,100 @@ hipError_t segments_count_lines(const uint32_t* set, uint32_t set_slots, const u
     if (n == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_seg_lines, dim3(grid_for(set_slots)), dim3(SEG_THREADS), 0, stream, set, set_slots, line_base, n, &table->lines_with_matches);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ host driver
+void SegmentPass::set(const uint32_t* starts, size_t n) {
+    if (!starts || !n) { pending_.clear(); return; }
+    pending_.assign(starts, starts + n);
+}
+
+void SegmentPass::arm(size_t len) {
+    off();
+    starts_.clear();
+    starts_.swap(pending_);
+    if (starts_.empty()) return;
+    std::string bad;
+    if (starts_.size() > 0x7FFFFFFFull) bad = "segments: too many segments";
+    else if (starts_[0] != 0) bad = "segments: starts[0] must be 0";
+    for (size_t s = 0; bad.empty() && s < starts_.size(); ++s) {
+        if (starts_[s] > len) bad = "segments: start of segment " + std::to_string(s) + " lies behind the end of the buffer";
+        else if (s && starts_[s] < starts_[s - 1]) bad = "segments: start of segment " + std::to_string(s) + " lies in front of its predecessor's";
+    }
+    if (!bad.empty()) { starts_.clear(); throw ParamError{bad}; }
+    active_ = true;
+}
+
+std::vector<uint32_t> SegmentPass::take() {
+    std::vector<uint32_t> all;
+    if (active_) all.swap(starts_);
+    off();
+    return all;
+}
+
+void SegmentPass::arm_piece(const std::vector<uint32_t>& all, size_t first, size_t last, uint32_t pos) {
+    starts_.resize(last - first + 1);
+    for (size_t k = 0; k < starts_.size(); ++k) starts_[k] = std::max(all[first + k], pos) - pos;
+    active_ = true;
+    index_base_ = (uint32_t)first;
+}
+
+void SegmentPass::upload(hipStream_t stream) {
+    const size_t n = starts_.size();
+    if (starts_dev_.n < n) {
+        starts_dev_.alloc(n + n / 4 + 1024); line_base_.alloc(starts_dev_.n);
+        table_.alloc(sizeof(SegHeader) + starts_dev_.n * sizeof(SegmentRec));
+    }
+    MXY_HIP(hipMemcpyAsync(starts_dev_.p, starts_.data(), n * 4, hipMemcpyHostToDevice, stream));
+}
+
+void SegmentPass::resolve(const HitBatch& b, const SegLines& lines, bool to_host, bool profile, hipStream_t stream) {
+    auto grown = [](uint32_t n) { return (size_t)n + n / 4 + 1024; };
+    const uint32_t n = (uint32_t)starts_.size();
+    const size_t n_recs = (size_t)b.n_fin + b.n_c4;
+    if (!sample_.p) sample_.alloc(SEG_SAMPLES);
+    if (of_fin_.n < b.n_fin) of_fin_.alloc(grown(b.n_fin));
+    if (of_c4_.n < b.n_c4) of_c4_.alloc(grown(b.n_c4));
+    const size_t head = sizeof(SegHeader) + (size_t)n * sizeof(SegmentRec), want = head + (to_host ? n_recs * 4 : 0);
+    pinned_.ensure(want, want / 4 + (1 << 16));
+    timed_ = profile;
+    with_lines_ = lines.prefix != nullptr;
+    if (profile) {
+        for (Event& e : ev_) e.create();
+        MXY_HIP(hipEventRecord(ev_[0], stream));
+    }
+    SegHeader* hdr = reinterpret_cast<SegHeader*>(table_.p);
+    SegmentRec* table = reinterpret_cast<SegmentRec*>(table_.p + sizeof(SegHeader));
+    MXY_HIP(segments_build(b.data, b.len, starts_dev_.p, n, lines.prefix, hdr, table, line_base_.p, sample_.p, stream));
+    if (profile) MXY_HIP(hipEventRecord(ev_[1], stream));
+    MXY_HIP(segments_attribute(b.fin, 16, b.n_fin, b.len, starts_dev_.p, n, sample_.p, of_fin_.p, table, stream));
+    MXY_HIP(segments_attribute(b.c4, 8, b.n_c4, b.len, starts_dev_.p, n, sample_.p, of_c4_.p, table, stream));
+    if (profile) MXY_HIP(hipEventRecord(ev_[2], stream));
+    if (with_lines_ && lines.set_slots) MXY_HIP(segments_count_lines(lines.set, lines.set_slots, line_base_.p, n, table, stream));
+    if (profile) MXY_HIP(hipEventRecord(ev_[3], stream));
+    uint8_t* pb = pinned_.p;
+    MXY_HIP(hipMemcpyAsync(pb, table_.p, head, hipMemcpyDeviceToHost, stream));
+    result_ = Result{};
+    if (to_host) {
+        if (b.n_fin) MXY_HIP(hipMemcpyAsync(pb + head, of_fin_.p, (size_t)b.n_fin * 4, hipMemcpyDeviceToHost, stream));
+        if (b.n_c4) MXY_HIP(hipMemcpyAsync(pb + head + (size_t)b.n_fin * 4, of_c4_.p, (size_t)b.n_c4 * 4, hipMemcpyDeviceToHost, stream));
+        result_.seg_of_fin = b.n_fin ? (const uint32_t*)(pb + head) : nullptr;
+        result_.seg_of_c4 = b.n_c4 ? (const uint32_t*)(pb + head) + b.n_fin : nullptr;
+    }
+    result_.segments = reinterpret_cast<const SegmentRec*>(pb + sizeof(SegHeader));
+    result_.n_segments = n;
+}
+
+// the error word, and the lines of every segment from neighbouring line_base values and the batch's total
+SegmentPass::Result SegmentPass::finish() {
+    const SegHeader* hdr = reinterpret_cast<const SegHeader*>(pinned_.p);
+    SegmentRec* t = reinterpret_cast<SegmentRec*>(pinned_.p + sizeof(SegHeader));
+    const size_t n = result_.n_segments;
+    if (timed_) for (int k = 0; k < 3; ++k) MXY_HIP(hipEventElapsedTime(&ms_[k], ev_[k], ev_[k + 1]));
+    if (hdr->bad != SEG_NONE)
+        throw ParamError{"segments: segment " + std::to_string((size_t)hdr->bad + index_base_) + " does not end in a newline (every non-empty segment in front of the last must)"};
+    if (with_lines_) for (size_t s = 0; s < n; ++s) t[s].lines = (s + 1 < n ? t[s + 1].line_base : hdr->total_nl) - t[s].line_base;
+    return result_;
 }
 
 }  // namespace mxy

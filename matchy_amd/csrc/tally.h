@@ -111,9 +111,6 @@ inline std::vector<TallyEntry> tally_merge(const std::vector<std::vector<TallyEn
 class HitTally {
 public:
     HitTally();
-    ~HitTally();
-    HitTally(const HitTally&) = delete;
-    HitTally& operator=(const HitTally&) = delete;
     // Counts the records of one batch whose text log[start, start + len) lies inside it: `final` (16-byte records, all kinds) and `c4`
     // (compact IPv4 records; null / 0 when compact records are not in effect), both in device memory like `log`. Synchronises `stream`.
     void add(const uint8_t* log, uint32_t len, const FinalHit* final, uint32_t n_final, const uint2* c4, uint32_t n_c4, hipStream_t stream);
@@ -136,7 +133,7 @@ private:
     TextTable table_;
     uint64_t matches_ = 0;
     bool profile_ = false;
-    hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};
+    Event ev_[3];   // created by the first profiled add()
     float last_ms_ = 0, claim_ms_ = 0, publish_ms_ = 0;
     Events events_;
 };

@@ -20,7 +20,6 @@
 #include <algorithm>
 #include <string>
 
-#include "engine.h"
 #include "lds_aggregator.h"
 
 namespace mxy {
@@ -172,15 +171,6 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_tally_gather(const uint8_t* p
 
 int grid_for_items(size_t n, size_t per_block) { return (int)std::max<size_t>(1, std::min<size_t>((n + per_block - 1) / per_block, 2048)); }
 
-template <class T>
-struct Scratch {   // a device allocation that lives as long as one call
-    T* p = nullptr;
-    explicit Scratch(size_t n) { if (n) MXY_HIP(hipMalloc((void**)&p, n * sizeof(T))); }
-    ~Scratch() { if (p) (void)hipFree(p); }
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-};
-
 }  // namespace
 
 // tests only: MATCHY_AMD_TALLY_SLOTS, MATCHY_AMD_TALLY_POOL_BYTES, MATCHY_AMD_TALLY_HASH_BITS
@@ -188,10 +178,6 @@ constexpr TextTableOwner TALLY_OWNER = {"hit tally", "values", "matchy_scanner_r
                                         "MATCHY_AMD_TALLY_", TALLY_EMPTY, 2048};
 
 HitTally::HitTally() : table_(TALLY_OWNER) {}
-
-HitTally::~HitTally() {
-    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-}
 
 void HitTally::reset() {
     table_.reset();
@@ -210,7 +196,7 @@ void HitTally::add(const uint8_t* log, uint32_t len, const FinalHit* final, uint
     if (n > TALLY_MAX_RECORDS) throw HipError{"hit tally: more than 2^32 records in one batch"};
     table_.start_batch(stream);
     if (profile_) {
-        for (auto& e : ev_) if (!e) MXY_HIP(hipEventCreate(&e));
+        for (Event& e : ev_) e.create();
         MXY_HIP(hipEventRecord(ev_[0], stream));
     }
     // everything that can fail for lack of memory comes first: up to here and through these the tally is untouched
@@ -256,7 +242,8 @@ void HitTally::top(size_t limit, std::vector<TallyEntry>& out, hipStream_t strea
     const TextTableView t = table_.view();
     // every published entry's count, text word and type: 24 bytes each
     const size_t cap = (size_t)distinct;
-    Scratch<TallyExport> ex_dev(cap);
+    DevBuf<TallyExport> ex_dev;   // the device allocations of a read-out live as long as the call
+    ex_dev.alloc(cap);
     MXY_HIP(hipMemsetAsync(&t.ctr->n_export, 0, sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_tally_export, dim3(grid_for_items((size_t)t.slot_mask + 1, TALLY_THREADS)), dim3(TALLY_THREADS), 0, stream, (const TextSlot*)t.slots, t.slot_mask + 1, ex_dev.p,
                        (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu), t.ctr);
@@ -277,8 +264,9 @@ void HitTally::top(size_t limit, std::vector<TallyEntry>& out, hipStream_t strea
     }
     std::vector<uint8_t> texts((size_t)bytes);
     if (bytes) {
-        Scratch<TallyGather> list_dev(list.size());
-        Scratch<uint8_t> dst_dev((size_t)bytes);
+        DevBuf<TallyGather> list_dev;
+        DevBuf<uint8_t> dst_dev;
+        list_dev.alloc(list.size()); dst_dev.alloc((size_t)bytes);
         MXY_HIP(hipMemcpyAsync(list_dev.p, list.data(), list.size() * sizeof(TallyGather), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(k_tally_gather, dim3(grid_for_items(list.size(), TALLY_THREADS / 64)), dim3(TALLY_THREADS), 0, stream, (const uint8_t*)t.pool, t.pool_cap,
                            (const TallyGather*)list_dev.p, (uint32_t)list.size(), dst_dev.p, bytes);

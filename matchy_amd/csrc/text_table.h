@@ -12,6 +12,7 @@
 #include <functional>
 
 #include "hashes.h"
+#include "hip_owners.h"
 #include "scan_types.h"
 
 namespace mxy {
@@ -93,9 +94,6 @@ struct TextTableOwner {
 class TextTable {
 public:
     explicit TextTable(const TextTableOwner& owner);
-    ~TextTable();
-    TextTable(const TextTable&) = delete;
-    TextTable& operator=(const TextTable&) = delete;
     void reset();                                   // empties the table, keeps the allocations
     void check() const;
     void start_batch(hipStream_t stream);           // the counters exist and their per-batch line is zero
@@ -109,21 +107,18 @@ public:
     uint32_t publish(const std::function<void()>& launch, TextTableView& view, hipStream_t stream);
     void close();                                   // the batch is in: takes pool_used and n_new from the counters
     void fetch_counters(hipStream_t stream);        // device -> host, synchronises
-    const TextCounters& host_counters() const { return *ctr_host_; }
+    const TextCounters& host_counters() const { return *ctr_host_.p; }
     uint64_t count() const { return count_; }       // entries since creation or the last reset
 
 private:
     void ensure_table(uint64_t entries, hipStream_t stream, uint32_t& rehashes);
     void grow_pool(unsigned long long want, hipStream_t stream);
     const TextTableOwner own_;
-    TextSlot* slots_ = nullptr;
-    uint64_t n_slots_ = 0;
-    uint8_t* pool_ = nullptr;
-    unsigned long long pool_cap_ = 0;
-    TextCounters* ctr_ = nullptr;        // device
-    TextCounters* ctr_host_ = nullptr;   // pinned
-    uint32_t* slot_of_ = nullptr;
-    size_t slot_of_n_ = 0;
+    DevBuf<TextSlot> slots_;
+    DevBuf<uint8_t> pool_;
+    DevBuf<TextCounters> ctr_;
+    PinnedBuf<TextCounters> ctr_host_;   // created with ctr_, behind it
+    DevBuf<uint32_t> slot_of_;
     uint64_t count_ = 0;
     unsigned long long pool_used_ = 0;   // TextCounters::pool_used behind the last batch
     uint64_t init_slots_, init_pool_;

@@ -6,7 +6,6 @@
 #include <cstdlib>
 #include <string>
 
-#include "engine.h"
 
 namespace mxy {
 
@@ -49,17 +48,9 @@ TextTable::TextTable(const TextTableOwner& owner) : own_(owner) {
     hash_bits_ = (uint32_t)std::min<unsigned long long>(env_u64(env + "HASH_BITS", 64), 64);
 }
 
-TextTable::~TextTable() {
-    if (slots_) (void)hipFree(slots_);
-    if (pool_) (void)hipFree(pool_);
-    if (ctr_) (void)hipFree(ctr_);
-    if (ctr_host_) (void)hipHostFree(ctr_host_);
-    if (slot_of_) (void)hipFree(slot_of_);
-}
-
 void TextTable::reset() {
-    if (slots_) MXY_HIP(hipMemset(slots_, (int)(own_.empty & 0xFF), n_slots_ * sizeof(TextSlot)));
-    if (ctr_) MXY_HIP(hipMemset(ctr_, 0, sizeof(TextCounters)));
+    if (slots_.p) MXY_HIP(hipMemset(slots_.p, (int)(own_.empty & 0xFF), slots_.n * sizeof(TextSlot)));
+    if (ctr_.p) MXY_HIP(hipMemset(ctr_.p, 0, sizeof(TextCounters)));
     count_ = 0; pool_used_ = 0;
     poisoned_ = false;
 }
@@ -69,35 +60,35 @@ void TextTable::check() const {
 }
 
 void TextTable::start_batch(hipStream_t stream) {
-    if (!ctr_) {
-        MXY_HIP(hipMalloc((void**)&ctr_, sizeof(TextCounters)));
-        MXY_HIP(hipMemset(ctr_, 0, sizeof(TextCounters)));
-        MXY_HIP(hipHostMalloc((void**)&ctr_host_, sizeof(TextCounters), hipHostMallocDefault));
+    if (!ctr_host_.p) {
+        ctr_.alloc(1);
+        MXY_HIP(hipMemset(ctr_.p, 0, sizeof(TextCounters)));
+        ctr_host_.alloc(1);
     }
     // the second counter line (pool_used, in the first, lives as long as the table)
-    MXY_HIP(hipMemsetAsync(&ctr_->n_counted, 0, 128, stream));
+    MXY_HIP(hipMemsetAsync(&ctr_.p->n_counted, 0, 128, stream));
 }
 
 // The new table is allocated before the old one is let go: a failed allocation leaves the table as it was.
 void TextTable::ensure_table(uint64_t entries, hipStream_t stream, uint32_t& rehashes) {
-    if (slots_ && 2 * entries <= n_slots_) return;
+    if (slots_.p && 2 * entries <= slots_.n) return;
     const std::string who = own_.who;
-    const unsigned long long want = text_slots_for(entries, slots_ ? 2 * n_slots_ : init_slots_);
+    const unsigned long long want = text_slots_for(entries, slots_.p ? 2 * slots_.n : init_slots_);
     if (want > (1ull << 31)) throw HipError{who + ": more than 2^30 distinct " + own_.entries};
-    TextSlot* fresh = nullptr;
-    hipError_t e = hipMalloc((void**)&fresh, want * sizeof(TextSlot));
+    DevBuf<TextSlot> fresh;   // released on every way out: the new table while it is incomplete, the old one behind the swap
+    hipError_t e = hipMalloc((void**)&fresh.p, want * sizeof(TextSlot));
     if (e != hipSuccess) throw HipError{who + ": cannot allocate a table of " + std::to_string(want) + " slots: " + hipGetErrorString(e)};
-    e = hipMemsetAsync(fresh, (int)(own_.empty & 0xFF), want * sizeof(TextSlot), stream);
-    if (e == hipSuccess && slots_ && count_) {
-        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((n_slots_ + TEXT_THREADS - 1) / TEXT_THREADS, own_.rehash_grid_cap));
-        hipLaunchKernelGGL(k_text_rehash, dim3(grid), dim3(TEXT_THREADS), 0, stream, (const TextSlot*)slots_, (uint32_t)n_slots_, fresh, (uint32_t)(want - 1), own_.empty, ctr_);
+    fresh.n = want;
+    e = hipMemsetAsync(fresh.p, (int)(own_.empty & 0xFF), want * sizeof(TextSlot), stream);
+    if (e == hipSuccess && slots_.p && count_) {
+        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((slots_.n + TEXT_THREADS - 1) / TEXT_THREADS, own_.rehash_grid_cap));
+        hipLaunchKernelGGL(k_text_rehash, dim3(grid), dim3(TEXT_THREADS), 0, stream, (const TextSlot*)slots_.p, (uint32_t)slots_.n, fresh.p, (uint32_t)(want - 1), own_.empty, ctr_.p);
         e = hipGetLastError();
         ++rehashes;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipFree(fresh); throw HipError{who + ": rehash: " + hipGetErrorString(e)}; }
-    if (slots_) (void)hipFree(slots_);
-    slots_ = fresh; n_slots_ = want;
+    if (e != hipSuccess) throw HipError{who + ": rehash: " + hipGetErrorString(e)};
+    slots_.swap(fresh);
 }
 
 // A pool of at least `want` bytes with the old pool's content: whole pages, except for the tiny pools of the tests
@@ -106,28 +97,23 @@ void TextTable::grow_pool(unsigned long long want, hipStream_t stream) {
     const std::string who = own_.who;
     want = want >= 4096 ? (want + 4095) & ~4095ull : text_pool_bytes((uint32_t)want);
     if (want > (1ull << 40)) throw HipError{who + ": text pool beyond 1 TiB"};
-    uint8_t* fresh = nullptr;
-    hipError_t e = hipMalloc((void**)&fresh, want);
+    DevBuf<uint8_t> fresh;   // as in ensure_table
+    hipError_t e = hipMalloc((void**)&fresh.p, want);
     if (e != hipSuccess) throw HipError{who + ": cannot allocate a text pool of " + std::to_string(want) + " bytes: " + hipGetErrorString(e)};
-    if (pool_) {
-        e = hipMemcpyAsync(fresh, pool_, pool_cap_, hipMemcpyDeviceToDevice, stream);
+    fresh.n = want;
+    if (pool_.p) {
+        e = hipMemcpyAsync(fresh.p, pool_.p, pool_.n, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { (void)hipFree(fresh); throw HipError{who + ": pool copy: " + hipGetErrorString(e)}; }
-        (void)hipFree(pool_);
+        if (e != hipSuccess) throw HipError{who + ": pool copy: " + hipGetErrorString(e)};
     }
-    pool_ = fresh; pool_cap_ = want;
+    pool_.swap(fresh);
 }
 
 uint32_t TextTable::reserve(uint64_t entries, size_t n_items, hipStream_t stream) {
     uint32_t rehashes = 0;
     ensure_table(entries, stream, rehashes);
-    if (!pool_) grow_pool(init_pool_, stream);
-    if (slot_of_n_ < n_items) {
-        if (slot_of_) (void)hipFree(slot_of_);
-        slot_of_ = nullptr; slot_of_n_ = 0;
-        MXY_HIP(hipMalloc((void**)&slot_of_, (n_items + n_items / 4 + 1024) * sizeof(uint32_t)));
-        slot_of_n_ = n_items + n_items / 4 + 1024;
-    }
+    if (!pool_.p) grow_pool(init_pool_, stream);
+    if (slot_of_.n < n_items) slot_of_.alloc(n_items + n_items / 4 + 1024);
     return rehashes;
 }
 
@@ -138,16 +124,16 @@ TextTableView TextTable::open() {
 
 TextTableView TextTable::view() const {
     TextTableView t{};
-    t.slots = slots_; t.slot_mask = (uint32_t)(n_slots_ - 1);
-    t.pool = pool_; t.pool_cap = pool_cap_;
+    t.slots = slots_.p; t.slot_mask = (uint32_t)(slots_.n - 1);
+    t.pool = pool_.p; t.pool_cap = pool_.n;
     t.hash_mask = text_hash_mask(hash_bits_);
-    t.slot_of = slot_of_; t.slot_of_cap = (uint32_t)std::min<size_t>(slot_of_n_, 0xFFFFFFFFu);
-    t.ctr = ctr_;
+    t.slot_of = slot_of_.p; t.slot_of_cap = (uint32_t)std::min<size_t>(slot_of_.n, 0xFFFFFFFFu);
+    t.ctr = ctr_.p;
     return t;
 }
 
 void TextTable::fetch_counters(hipStream_t stream) {
-    MXY_HIP(hipMemcpyAsync(ctr_host_, ctr_, sizeof(TextCounters), hipMemcpyDeviceToHost, stream));
+    MXY_HIP(hipMemcpyAsync(ctr_host_.p, ctr_.p, sizeof(TextCounters), hipMemcpyDeviceToHost, stream));
     MXY_HIP(hipStreamSynchronize(stream));
 }
 
@@ -159,19 +145,19 @@ uint32_t TextTable::publish(const std::function<void()>& launch, TextTableView& 
     for (uint32_t regrows = 0;; ++regrows) {
         launch();
         fetch_counters(stream);
-        if (ctr_host_->error) throw HipError{std::string(own_.who) + ": table full (" + own_.full_reason + ")"};
-        if (ctr_host_->n_pending == 0) return regrows;
+        if (ctr_host_.p->error) throw HipError{std::string(own_.who) + ": table full (" + own_.full_reason + ")"};
+        if (ctr_host_.p->n_pending == 0) return regrows;
         if (regrows >= MAX_REGROWS) throw HipError{std::string(own_.who) + ": text pool still full after regrowing"};
-        const unsigned long long demand = ctr_host_->pool_used;
-        grow_pool(std::max(2 * pool_cap_, demand + (demand - pool_used_)), stream);
-        view.pool = pool_; view.pool_cap = pool_cap_;
-        MXY_HIP(hipMemsetAsync(&ctr_->n_pending, 0, sizeof(uint32_t), stream));
+        const unsigned long long demand = ctr_host_.p->pool_used;
+        grow_pool(std::max<unsigned long long>(2 * pool_.n, demand + (demand - pool_used_)), stream);
+        view.pool = pool_.p; view.pool_cap = pool_.n;
+        MXY_HIP(hipMemsetAsync(&ctr_.p->n_pending, 0, sizeof(uint32_t), stream));
     }
 }
 
 void TextTable::close() {
-    pool_used_ = ctr_host_->pool_used;
-    count_ += ctr_host_->n_new;
+    pool_used_ = ctr_host_.p->pool_used;
+    count_ += ctr_host_.p->n_new;
     poisoned_ = false;
 }
 

@@ -350,6 +350,55 @@ def test_smaller_segmented_scan_after_a_larger_one(env):
         used.close()
 
 
+def _alternating_cases(T):
+    """a log of three tiles and a bit with hits in all three of its segments, and one of 100 bytes with two segments and two hits"""
+    L = 3 * T + 40
+    big = LC.make_log(L, [(5, LC.IP), (600, LC.DOM), (T + 3, LC.DOM), (2 * T + 9, LC.IP), (L - 9, LC.IP)], [500, T - 1, T + 500, 2 * T + 4, 2 * T + 600])
+    small = LC.make_log(100, [(3, LC.IP), (60, LC.DOM)], [49, 99])
+    return (big, [0, T, 2 * T + 5]), (small, [0, 50])
+
+
+@pytest.mark.parametrize("entry", ["scan_device", "scan"])
+def test_line_context_switched_between_segmented_scans(env, entry):
+    """One scanner, a table in front of every scan, line context on / off / on / off over a larger and a smaller log: the segment pass
+    reads the prefix array and the distinct-line set of the line context of ITS fetch, or none. Every scan equals the same scan on a
+    fresh scanner and the host model; without line context the three line figures are 0 (a stale prefix array or set would show)."""
+    M = env.M
+    (big, big_starts), (small, small_starts) = _alternating_cases(M.LINE_TILE)
+    assert len(big) == 3 * M.LINE_TILE + 40 and len(small) == 100
+    assert [t[2] for t in S.table_model(big, big_starts, [k[0] for k in env.expected(big, big_starts)], False)] == [2, 1, 2]
+    assert [t[2] for t in S.table_model(small, small_starts, [k[0] for k in env.expected(small, small_starts)], False)] == [1, 1]
+    used = M.Scanner(env.db)
+    dptrs = {id(b): on_device(b) for b in (big, small)}
+
+    def run(sc, buf, starts, lines):
+        sc.set_line_context(lines)
+        sc.set_segments(starts)
+        return sc.scan(buf.tobytes()) if entry == "scan" else sc.scan_device(dptrs[id(buf)].value, len(buf), fetch_mode=3)
+    try:
+        for step, (lines, (buf, starts)) in enumerate([(True, (big, big_starts)), (False, (small, small_starts)), (True, (small, small_starts)),
+                                                        (False, (big, big_starts))]):
+            what = (entry, step, lines)
+            fresh = M.Scanner(env.db)
+            try:
+                r, rf = run(used, buf, starts, lines), run(fresh, buf, starts, lines)
+                hit_starts, of, table = read(r)
+                f_starts, f_of, f_table = read(rf)
+                assert list(hit_starts) == list(f_starts) and list(of) == list(f_of) and table == f_table, what
+                assert r.has_lines == rf.has_lines == lines and r.lines_with_matches == rf.lines_with_matches, what
+                assert (r.lines_with_matches is None) if not lines else (r.lines_with_matches == sum(t[5] for t in table) > 0), what
+                check(r, buf, starts, lines, what, len(env.expected(buf, starts)))
+                if not lines:
+                    assert all(t[3:] == (0, 0, 0) for t in table), what
+                r.close(); rf.close()
+            finally:
+                fresh.close()
+    finally:
+        for d in dptrs.values():
+            hip().hipFree(d)
+        used.close()
+
+
 def _child(case, env_extra):
     e = dict(os.environ, **env_extra)
     p = subprocess.run([sys.executable, str(ROOT / "tests" / "segment_cases.py"), case], env=e, capture_output=True, text=True, timeout=300)
