@@ -20,6 +20,7 @@
 #include "scan_types.h"
 
 #include "device_shared.h"
+#include "domain_planes.h"
 
 namespace mxy {
 
@@ -289,83 +290,14 @@ __device__ bool val_domain_resume(const LogView& lg, const DevDb& db, uint32_t m
     return true;
 }
 
-// The same for an anchor that comes with its context record (k_anchor copies log[j-24, j+8) from its LDS window):
-// w = log[j, j+8), b0 = log[j-8, j), b1 = log[j-16, j-8), b2 = log[j-24, j-16). The common case — last label of <= 7
-// bytes that alone is a public suffix, name no longer than the context — is decided with mask arithmetic on these
-// registers, without a per-byte loop and without divergent control flow (k_validate is bound by scalar-ALU issue, i.e.
-// by control flow): the rules of is_valid_domain (ext:637-689) become tests on the dot / dash / domain-char masks.
-// Everything else is left to the general path (val_domain, in k_validate).
-// Returns 0 (no domain), 1 (domain: start / end set, the whole name lies in the context) or 2 (undecided: general path).
-__device__ __forceinline__ int val_domain_pre(const uint2* tldtab, uint32_t min_labels, uint32_t j, uint2 w, uint64_t b0, uint64_t b1,
-                                              uint64_t b2, uint32_t& start, uint32_t& end) {
-    constexpr uint64_t H = 0x8080808080808080ull;
-    const uint64_t w64 = (uint64_t)w.x | ((uint64_t)w.y << 32);
-    const ByteMasks mw = domain_masks(w64);
-    // last label = leading domain-char bytes of w; ll = its length (8: not terminated within the window)
-    const uint64_t ndc = ~mw.dc & H;
-    const uint32_t ll = ndc ? (uint32_t)(__ffsll((long long)ndc) - 1) >> 3 : 8u;
-    if (ll <= 7 && ll >= 1) {
-        const uint64_t below = (1ull << (8 * ll)) - 1ull;            // the label's bytes
-        if (mw.dot & below) return 0;                                // a later dot owns this run
-        const uint32_t stop_c = (uint32_t)(w64 >> (8 * ll)) & 0xFF;
-        if (!d_is_boundary(stop_c)) return 0;
-        const uint32_t lo = (uint32_t)(w64 & below), hi = (uint32_t)((w64 & below) >> 32);
-        uint32_t slot = tld_tab_slot(lo, hi);
-        bool alone = false;
-        for (;;) {
-            const uint2 t = tldtab[slot];
-            if ((t.y >> 24) == 0) return 0;
-            if (t.x == lo && (t.y & 0xFFFFFFu) == hi) { alone = (t.y >> 24) & 1; break; }
-            slot = (slot + 1) & ((1u << TLD_TAB_BITS) - 1);
-        }
-        if (alone) {
-            // the 24 bytes in front of the label, address order: b2 | b1 | b0; the run extends leftwards from the top
-            // byte of b0 (the dot at j-1) while bytes are domain chars
-            const ByteMasks m0 = domain_masks(b0), m1 = domain_masks(b1), m2 = domain_masks(b2);
-            const uint64_t n0m = ~m0.dc & H, n1m = ~m1.dc & H, n2m = ~m2.dc & H;
-            const uint32_t c0 = n0m ? (uint32_t)__clzll((long long)n0m) >> 3 : 8u;   // domain chars at the top of b0
-            const uint32_t c1 = n1m ? (uint32_t)__clzll((long long)n1m) >> 3 : 8u, c2 = n2m ? (uint32_t)__clzll((long long)n2m) >> 3 : 8u;
-            const uint32_t consumed = c0 < 8 ? c0 : (c1 < 8 ? 8 + c1 : 16 + c2);
-            if (consumed < 24 || j == 24) {   // the run starts inside the context (or at the start of the buffer)
-                // region masks: the top `k` bytes of each word that belong to the run
-                auto top = [](uint32_t k) -> uint64_t { return k == 0 ? 0ull : (~0ull << (64 - 8 * k)); };
-                const uint64_t r0 = top(min(consumed, 8u)), r1 = top(consumed > 8 ? min(consumed - 8, 8u) : 0u),
-                               r2 = top(consumed > 16 ? consumed - 16 : 0u);
-                // "byte to the right" (one position closer to the label) moved onto each byte: shift towards lower
-                // addresses; the byte right of b0's top byte is the label's first byte (neither dot nor dash)
-                const uint64_t d0 = m0.dot >> 8, d1 = (m1.dot >> 8) | (m0.dot << 56), d2 = (m2.dot >> 8) | (m1.dot << 56);
-                const uint64_t s0 = m0.dash >> 8, s1 = (m1.dash >> 8) | (m0.dash << 56), s2 = (m2.dash >> 8) | (m1.dash << 56);
-                // bad events: empty label (two dots in a row), label starting with '-' (dot, then dash to its right),
-                // label ending with '-' (dash, then dot to its right)
-                const uint64_t bad = ((m0.dot & (d0 | s0)) | (m0.dash & d0)) & r0;
-                const uint64_t bad1 = ((m1.dot & (d1 | s1)) | (m1.dash & d1)) & r1, bad2 = ((m2.dot & (d2 | s2)) | (m2.dash & d2)) & r2;
-                const uint32_t ndots = (uint32_t)(__popcll(m0.dot & r0) + __popcll(m1.dot & r1) + __popcll(m2.dot & r2));
-                // leftmost byte of the run: must not be a dot (empty leftmost label) or a dash
-                const uint32_t li = 24 - consumed;                       // its index in address order (consumed >= 1: the dot)
-                const uint64_t lw = li < 8 ? b2 : li < 16 ? b1 : b0;
-                const uint32_t left_c = (uint32_t)(lw >> (8 * (li & 7))) & 0xFF;
-                const uint32_t fi = 23 - consumed;                       // byte in front of the run (if inside the context)
-                const uint64_t fw = fi < 8 ? b2 : fi < 16 ? b1 : b0;
-                const uint32_t first_c = consumed < 24 ? (uint32_t)(fw >> (8 * (fi & 7))) & 0xFF : 0x100u;
-                const uint32_t lastc = (uint32_t)(w64 >> (8 * (ll - 1))) & 0xFF;
-                const bool any_bad = (bad | bad1 | bad2) != 0 || lastc == '-' || consumed == 0 || left_c == '.' || left_c == '-';
-                if (any_bad || ndots == 0 || 1 + ndots < min_labels) return 0;
-                if (first_c != 0x100 && !d_is_boundary(first_c)) return 0;
-                const uint32_t s_pos = j - consumed;
-                const bool high = ((m0.high & r0) | (m1.high & r1) | (m2.high & r2) | (mw.high & below)) != 0;
-                if (high) return 2;   // needs the UTF-8 check of the general path
-                start = s_pos; end = j + ll;
-                return 1;
-            }
-            // the name reaches further back than the context: general path below
-        }
-    }
-    return 2;
-}
-
-// val_domain_pre over NB context words instead of three, for the anchors k_validate_dom could not decide from its 24 context bytes (a proxy
+// An anchor that comes with its context record (k_anchor copies log[j-24, j+8) from its LDS window) is decided by domain_rules()
+// (domain_planes.h) in k_validate_dom: the common case — last label of <= 7 bytes that alone is a public suffix, name no longer than
+// the context — with bit-sliced class masks of the record, without a per-byte loop and without divergent control flow; everything else
+// is left to the general path (val_domain, in k_validate).
+//
+// The same rules over NB context words of 8 bytes, for the anchors k_validate_dom could not decide from its 24 context bytes (a proxy
 // log: 2 M host names of 25..48 bytes in front of their last label per batch, which otherwise all take the byte-and-word loops of the general
-// walk): w = log[j, j+8), b[k] = log[j-8(k+1), j-8k). The same rules on the same masks, written as loops over the words that unroll. A name
+// walk): w = log[j, j+8), b[k] = log[j-8(k+1), j-8k), on byte-lane SWAR masks (domain_masks), written as loops over the words that unroll. A name
 // decided here has at most 8 NB + 7 <= 63 bytes, so the 63-byte label and 253-byte name limits of is_valid_domain (ext:637-689) cannot bite
 // (NB <= 7). Returns 0 (no domain), 1 (domain: start / end set) or 2 (undecided: the general walk).
 template <int NB>
@@ -959,14 +891,12 @@ __global__ __launch_bounds__(256) void k_validate_dom(TokParams p, DevDb db) {
     const uint32_t nd = min(p.counters->n_dom, p.dom_cap);
     struct Rec { uint32_t j; uint32_t c[8]; };
     auto load_rec = [&](uint32_t i, Rec& r) {
-        r.j = 0xFFFFFFFFu;
+        // past the end of the list: slot 0 is loaded (the list always has slots) and discarded — no registers to zero, no branch around the loads
+        const uint32_t ic = i < nd ? i : 0u;
+        const uint32_t j = p.dom_list[dom_plane_index(ic, 0)];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) r.c[k] = 0;
-        if (i < nd) {
-            r.j = p.dom_list[dom_plane_index(i, 0)];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r.c[k] = p.dom_list[dom_plane_index(i, 1 + k)];
-        }
+        for (int k = 0; k < 8; ++k) r.c[k] = p.dom_list[dom_plane_index(ic, 1 + k)];
+        r.j = i < nd ? j : 0xFFFFFFFFu;
     };
     Rec cur, nxt;
     load_rec(blockIdx.x * blockDim.x + threadIdx.x, cur);
@@ -1026,11 +956,7 @@ __global__ __launch_bounds__(256) void k_validate_dom(TokParams p, DevDb db) {
         if (cur.j != 0xFFFFFFFFu) {
             uint32_t s = 0, e = 0;
             int r = 2;
-            if (!(cur.j & 0x80000000u)) {
-                const uint64_t b2 = (uint64_t)cur.c[0] | ((uint64_t)cur.c[1] << 32), b1 = (uint64_t)cur.c[2] | ((uint64_t)cur.c[3] << 32),
-                               b0 = (uint64_t)cur.c[4] | ((uint64_t)cur.c[5] << 32);
-                r = val_domain_pre(tldtab, p.min_labels, cur.j, make_uint2(cur.c[6], cur.c[7]), b0, b1, b2, s, e);
-            }
+            if (!(cur.j & 0x80000000u)) r = domain_rules(tldtab, p.min_labels, cur.j, cur.c, s, e);
             slow = r == 2;
             if (r == 1) {
                 pend_start = s; pend_lt = (e - s) | ((uint32_t)IT_DOMAIN << 24); pend = true;
