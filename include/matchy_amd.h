@@ -373,6 +373,48 @@ int32_t matchy_scan_result_to_ndjson_segments(matchy_scanner_t *scanner, const m
                                               char **out, size_t *out_len);
 /* With matchy_scanner_set_profile: milliseconds of the segment pass, the record passes and the lines-with-matches pass of the last scan. */
 void matchy_scanner_get_segment_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* ---- gz scans: many compressed files, one scan (opt-in: with these calls never made a scanner allocates, launches and copies nothing
+ * more, and every output stays as it is).
+ * The caller hands over one host buffer that holds whole gzip files (RFC 1952, one member each) and a table of them. The compressed
+ * bytes cross the bus, one wave per file inflates it on the GPU into its segment of one batch in device memory, CRC-32 and ISIZE are
+ * verified there, and the scan runs over that batch as a segmented scan: segment i is member i. DEFLATE is sequential within a
+ * stream: the parallelism is across the files, and a single large file gains nothing.
+ * Layout of the batch: the members' texts end to end in table order, one '\n' — the separator, which is not the input's — behind every
+ * non-empty member, whether or not its text ends in one: start[0] = 0, start[i + 1] = start[i] + out_len[i] + 1 for a non-empty
+ * member and start[i] for an empty one. Line numbers inside a member do not change: the extra empty line is its last.
+ * out_len: 0 = take the capacity from ISIZE, the member's last four bytes (what `matchy match --gz-on-gpu` does); any other value is
+ * the inflated length the caller vouches for. A member that inflates to more or fewer bytes fails.
+ * A member that fails does not fail the call: it gets a status, its whole region of the batch is overwritten with '\n' so that it can
+ * contribute no hit, and it keeps its index. One status per member; the FIRST error in stream order decides, and behind a stream that
+ * ended the trailer checks run in the order TRUNCATED, SIZE_MISMATCH, CRC_MISMATCH, TRAILING_DATA. */
+#define MATCHY_GZ_OK 0
+#define MATCHY_GZ_BAD_HEADER 1     /* host: the gzip header does not parse (magic, CM != 8, reserved FLG bit, a field past the end) */
+#define MATCHY_GZ_TRUNCATED 2      /* the input ends before the stream or its trailer does */
+#define MATCHY_GZ_BAD_BLOCK 3      /* block type 3, LEN / NLEN mismatch */
+#define MATCHY_GZ_BAD_CODES 4      /* bad code lengths or tables (what zlib's inflate_table refuses, and the rules of the code-length code) */
+#define MATCHY_GZ_BAD_SYMBOL 5     /* length symbol 286 / 287, distance symbol 30 / 31, bits that are no code of an incomplete code */
+#define MATCHY_GZ_BAD_DISTANCE 6   /* back-reference beyond the bytes produced */
+#define MATCHY_GZ_OVERFLOW 7       /* more output than out_len */
+#define MATCHY_GZ_SIZE_MISMATCH 8  /* fewer bytes than out_len, or the trailer's ISIZE differs */
+#define MATCHY_GZ_CRC_MISMATCH 9   /* the trailer's CRC-32 differs */
+#define MATCHY_GZ_TRAILING_DATA 10 /* bytes behind the trailer: a second member or garbage (gzread would go on; the caller falls back) */
+typedef struct matchy_gz_member_t { uint64_t offset; uint32_t len; uint32_t out_len; } matchy_gz_member_t;
+/* fetch_mode as matchy_scanner_scan_device (every mode; line context and the tally apply as for any scan). The result answers
+ * matchy_scan_result_segments (and _lines) like any segmented scan, and matchy_scan_result_gz. Its `lines` counts the '\n' bytes of the
+ * OK members' own text (separators and overwritten regions are not counted), its `bytes` is the sum of the OK members' inflated
+ * lengths; offsets of hits are offsets into the batch. want_text: the inflated batch is copied to pinned host memory once, behind the
+ * scan, for matchy_scan_hit_to_json and the NDJSON calls; without it only counters, records and tables cross the bus.
+ * MATCHY_ERROR_INVALID_PARAM with a message, and a scanner that stays usable: NULL handles, n == 0, a member outside packed[0, packed_len),
+ * a batch that reaches 2^31 bytes. */
+int32_t matchy_scanner_scan_gz(matchy_scanner_t *scanner, const uint8_t *packed, size_t packed_len, const matchy_gz_member_t *members,
+                               size_t n, uint32_t fetch_mode, bool want_text, matchy_scan_result_t *out);
+/* status: n_members values MATCHY_GZ_*, owned by the result. text / text_len: the inflated batch — NULL / its length without want_text;
+ * borrowed from the scanner until its next scan, or owned by the result for MATCHY_SCAN_FETCH_SORTED (like the hit arrays of that mode).
+ * MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_gz(const matchy_scan_result_t *result, const int32_t **status, size_t *n_members, const uint8_t **text,
+                              size_t *text_len);
+/* With matchy_scanner_set_profile: milliseconds of the inflate kernel (the CRC is computed inside it), 0, and the seal kernel of the last gz scan. */
+void matchy_scanner_get_gz_timing(const matchy_scanner_t *scanner, float out_ms[3]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -477,6 +519,12 @@ int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t *ms, const uint8
  * batch sets the table on its scanner before the scan, and the batch from _next answers matchy_scan_result_segments. */
 int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, const uint32_t *starts, size_t n,
                                              void *tag, const void *pinned_range);
+/* matchy_multi_scanner_submit of a pack of n gzip files (matchy_scanner_scan_gz: `members` is copied, the packed bytes stay the
+ * caller's until the batch has been taken): the worker that takes the batch inflates and scans it on its GPU. The batch from _next
+ * answers matchy_scan_result_segments and matchy_scan_result_gz; its data / len are the inflated text, owned by the result, and its
+ * length — NULL and the length without want_text. */
+int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_member_t *members,
+                                       size_t n, bool want_text, void *tag);
 /* NUMA node of a worker's GPU (-1 = unknown) and the number of CPUs its thread bound itself to (0 = not bound); valid once the
  * worker thread has started (after the first _next at the latest). */
 int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t *ms, size_t worker, int32_t *node, int32_t *cpus_bound);

@@ -56,7 +56,14 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_set_tally", "matchy_multi_scanner_tally_top", "matchy_multi_scanner_reset_tally", "matchy_tally_free",
     "matchy_scanner_set_segments", "matchy_scan_result_segments", "matchy_scan_result_to_ndjson_segments",
     "matchy_multi_scanner_submit_segments", "matchy_scanner_get_segment_timing",
+    "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
 ]
+
+# MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
+GZ_OK, GZ_BAD_HEADER, GZ_TRUNCATED, GZ_BAD_BLOCK, GZ_BAD_CODES, GZ_BAD_SYMBOL, GZ_BAD_DISTANCE = 0, 1, 2, 3, 4, 5, 6
+GZ_OVERFLOW, GZ_SIZE_MISMATCH, GZ_CRC_MISMATCH, GZ_TRAILING_DATA = 7, 8, 9, 10
+GZ_STATUS_NAMES = ["OK", "BAD_HEADER", "TRUNCATED", "BAD_BLOCK", "BAD_CODES", "BAD_SYMBOL", "BAD_DISTANCE", "OVERFLOW", "SIZE_MISMATCH",
+                   "CRC_MISMATCH", "TRAILING_DATA"]
 
 # bytes per tile of the '\n' count array and tiles per workgroup of its prefix sum (csrc/line_index.h): the sizes at which the line
 # kernels take another path
@@ -124,6 +131,11 @@ class _ScanSegment(C.Structure):
     # matchy_scan_segment_t (32 bytes)
     _fields_ = [("start", C.c_uint32), ("len", C.c_uint32), ("hits", C.c_uint32), ("line_base", C.c_uint32), ("lines", C.c_uint32),
                 ("lines_with_matches", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class _GzMember(C.Structure):
+    # matchy_gz_member_t (16 bytes)
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint32), ("out_len", C.c_uint32)]
 
 
 class _TallyEntry(C.Structure):
@@ -258,6 +270,10 @@ def lib():
                                                               C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_multi_scanner_submit_segments": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, vp, vp]),
         "matchy_scanner_get_segment_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_scan_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_gz": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_scanner_get_gz_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_multi_scanner_submit_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_bool, vp]),
         "matchy_scanner_set_tally": (None, [vp, C.c_bool]),
         "matchy_scanner_tally": (C.c_bool, [vp]),
         "matchy_scanner_reset_tally": (None, [vp]),
@@ -620,6 +636,35 @@ class ScanResult:
         finally:
             L.matchy_free_string(out)
 
+    def _gz_arrays(self):
+        """(status pointer, n_members, text pointer, text_len) of a gz scan, else None"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        st, n, t, tn = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        if lib().matchy_scan_result_gz(C.byref(self._raw), C.byref(st), C.byref(n), C.byref(t), C.byref(tn)) != 0:
+            return None
+        return st.value or 0, int(n.value), t.value or 0, int(tn.value)
+
+    def gz_status(self):
+        """one GZ_* status per member of a gz scan (Scanner.scan_gz); None for any other scan"""
+        ga = self._gz_arrays()
+        if ga is None:
+            return None
+        arr = C.cast(ga[0], C.POINTER(C.c_int32))
+        return [arr[i] for i in range(ga[1])]
+
+    def gz_text(self):
+        """the inflated batch of a gz scan with want_text as bytes (a copy); None without want_text or for any other scan"""
+        ga = self._gz_arrays()
+        if ga is None or not ga[2]:
+            return None
+        return C.string_at(ga[2], ga[3])
+
+    def gz_text_len(self):
+        """length of the inflated batch of a gz scan, with or without want_text; None for any other scan"""
+        ga = self._gz_arrays()
+        return None if ga is None else ga[3]
+
     def _line_arrays(self):
         """(lines pointer, ip4_lines pointer, lines_with_matches) of a result scanned with line context, else None"""
         if self._raw is None:
@@ -812,6 +857,22 @@ class Scanner:
         lib().matchy_scanner_get_segment_timing(self._h, out)
         return dict(build=out[0], records=out[1], lines=out[2])
 
+    def scan_gz(self, blobs, want_text=False, out_lens=None, fetch_mode=1) -> ScanResult:
+        """inflate the gzip files `blobs` (bytes each) on the GPU and scan them as one batch of len(blobs) segments
+        (matchy_scanner_scan_gz). out_lens: the inflated length of every file the caller vouches for (0 or None = take ISIZE). The
+        result has .segments / .segment_of like a segmented scan, and gz_status() / gz_text()."""
+        packed, table = _gz_pack(blobs, out_lens)
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_gz(self._h, packed, len(packed), table, len(table), fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_gz failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
+    def gz_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_gz_timing(self._h, out)
+        return dict(inflate=out[0], crc=out[1], seal=out[2])
+
     def set_tally(self, on=True):
         """hit tally for the next scans: matches per distinct (item type, matched text), counted on the GPU across scans (off by default)"""
         lib().matchy_scanner_set_tally(self._h, bool(on))
@@ -848,6 +909,17 @@ class Scanner:
             self.close()
         except Exception:
             pass
+
+
+def _gz_pack(blobs, out_lens=None):
+    """the files end to end as one bytes object, and their matchy_gz_member_t table"""
+    table = (_GzMember * len(blobs))()
+    pos = 0
+    for i, b in enumerate(blobs):
+        table[i].offset, table[i].len = pos, len(b)
+        table[i].out_len = int(out_lens[i]) if out_lens is not None and out_lens[i] else 0
+        pos += len(b)
+    return b"".join(bytes(b) for b in blobs), table
 
 
 class _WorkerScanner:
@@ -910,6 +982,16 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_segments failed ({rc}): " + last_error())
 
+    def submit_gz_ptr(self, host_ptr: int, nbytes: int, members, want_text=False, tag: int = 0):
+        """queue a pack of gzip files that lives at a host address: members = [(offset, len, out_len)] (matchy_multi_scanner_submit_gz).
+        next() then carries gz_status, the segment table and, with want_text, the inflated text"""
+        table = (_GzMember * len(members))()
+        for i, (off, ln, out_len) in enumerate(members):
+            table[i].offset, table[i].len, table[i].out_len = off, ln, out_len
+        rc = lib().matchy_multi_scanner_submit_gz(self._h, host_ptr, nbytes, table, len(members), bool(want_text), tag)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_gz failed ({rc}): " + last_error())
+
     def pending(self) -> int:
         return lib().matchy_multi_scanner_pending(self._h)
 
@@ -946,6 +1028,10 @@ class MultiScanner:
             out["segments"] = r.segments
             if want_hits:
                 out["segment_of"] = r.segment_of
+        gz = r.gz_status()
+        if gz is not None:   # a gz batch: data / len are the inflated text (NULL without want_text) and its length
+            out["gz_status"] = gz
+            out["text"] = C.string_at(b.data, b.len) if b.data else None
         r.close()
         return out
 

@@ -18,6 +18,7 @@
 #include "db_image.h"
 #include "engine.h"
 #include "host_lookup.h"
+#include "inflate_core.h"
 #include "netaddr.h"
 #include "utf8_lossy.h"
 
@@ -1052,6 +1053,66 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+
+// gz scans (Scanner::gz_inflate, inflate.hip): inflate, seal, segment table and scan are queued on the scanner's own stream; the fetch is
+// that of matchy_scanner_scan_device
+static_assert(sizeof(GzMemberIn) == sizeof(matchy_gz_member_t) && offsetof(GzMemberIn, out_len) == offsetof(matchy_gz_member_t, out_len), "the plan reads matchy_gz_member_t directly");
+static_assert(MATCHY_GZ_OK == gz::GZ_OK && MATCHY_GZ_BAD_HEADER == gz::GZ_BAD_HEADER && MATCHY_GZ_TRUNCATED == gz::GZ_TRUNCATED && MATCHY_GZ_BAD_BLOCK == gz::GZ_BAD_BLOCK &&
+                  MATCHY_GZ_BAD_CODES == gz::GZ_BAD_CODES && MATCHY_GZ_BAD_SYMBOL == gz::GZ_BAD_SYMBOL && MATCHY_GZ_BAD_DISTANCE == gz::GZ_BAD_DISTANCE &&
+                  MATCHY_GZ_OVERFLOW == gz::GZ_OVERFLOW && MATCHY_GZ_SIZE_MISMATCH == gz::GZ_SIZE_MISMATCH && MATCHY_GZ_CRC_MISMATCH == gz::GZ_CRC_MISMATCH &&
+                  MATCHY_GZ_TRAILING_DATA == gz::GZ_TRAILING_DATA, "k_gz_inflate writes MATCHY_GZ_* values directly");
+int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, uint32_t fetch_mode,
+                               bool want_text, matchy_scan_result_t* out) {
+    if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    if (!members || n == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
+    ScannerH* h = reinterpret_cast<ScannerH*>(s);
+    try {
+        const Scanner::GzBatch b = h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
+        const bool sorted = (fetch_mode & 2) != 0;
+        ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
+        rq.ptr = b.text; rq.len = b.len; rq.lookup = true;
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode); rq.lines = h->sc->line_context();
+        h->sc->arm_segments(b.len, b.stream);
+        h->sc->scan_device(rq, b.stream);
+        h->sc->gz_queue_results(want_text);
+        ScanOutput so;
+        h->sc->fetch(so, false, b.stream, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
+        const GzInflate::Result g = h->sc->gz_finish();
+        const bool device = (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE;
+        if (device) fill_device_result(*h->sc, so, g.ok_bytes, out);
+        else {
+            fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, g.ok_bytes, !sorted, sorted, out);
+            out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
+            if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
+        }
+        out->lines = so.lines - std::min<uint64_t>(so.lines, g.not_input_nl);
+        attach_lines(*h->sc, so, device, sorted, out);
+        attach_segments(*h->sc, so, device, sorted, out);
+        if (!out->_internal) out->_internal = new ScanResultInternal();
+        auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+        in->has_gz = true;
+        in->gz_status.assign(g.status, g.status + g.n);
+        in->gz_text = g.text; in->gz_text_len = g.text_len;
+        if (sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
+        return MATCHY_SUCCESS;
+    } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+int32_t matchy_scan_result_gz(const matchy_scan_result_t* r, const int32_t** status, size_t* n_members, const uint8_t** text, size_t* text_len) {
+    if (!r) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_gz) { set_error("matchy_scan_result_gz: the result was not produced by a gz scan"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (status) *status = in->gz_status.data();
+    if (n_members) *n_members = in->gz_status.size();
+    if (text) *text = in->gz_text;
+    if (text_len) *text_len = in->gz_text_len;
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_gz_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_timing(out);
 }
 
 void matchy_scan_result_free(matchy_scan_result_t* r) {

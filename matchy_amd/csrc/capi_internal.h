@@ -33,6 +33,13 @@ struct ScanResultInternal {
     std::vector<uint32_t> segment_of_own;
     const uint32_t* segment_of_hit = nullptr;
     const uint32_t* segment_of_ip4_hit = nullptr;
+    // gz scan (matchy_scan_result_gz): the statuses are always owned; the text is the scanner's pinned block, or owned (gz_text_own)
+    // where the hit arrays are
+    bool has_gz = false;
+    std::vector<int32_t> gz_status;
+    std::vector<uint8_t> gz_text_own;
+    const uint8_t* gz_text = nullptr;
+    size_t gz_text_len = 0;
 };
 
 // hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top

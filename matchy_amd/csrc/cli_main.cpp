@@ -16,6 +16,9 @@
 // --tally[=N] adds, behind the match records, {"count","item_type","matched_text","result"} per distinct matched value (tally.hip).
 // --pack-inputs reads consecutive small input files into shared batches (input_packer.h) and scans each as one batch of segments
 // (segments.hip): the output is byte for byte what it is without the flag.
+// --gz-on-gpu sends runs of consecutive small .gz inputs to the GPU compressed (matchy_multi_scanner_submit_gz, inflate.hip): one wave
+// per file inflates them into the segments of one batch. A file the GPU does not accept (a second member, a damaged stream) is read the
+// old way right behind its pack, so it is scanned or reported exactly as without the flag; only its place in the output moves.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -47,6 +50,7 @@
 #include "db_builder.h"
 #include "batch_reader.h"
 #include "db_image.h"
+#include "gz_plan.h"
 #include "input_packer.h"
 
 using namespace mxy;
@@ -62,6 +66,7 @@ int usage() {
             "               [--tally[=N]]   (behind the matches: one JSON line per distinct matched value with its hit count, the N most frequent; default 20,\n"
             "                                0 = all; counted on the GPU; with --format summary nothing else is printed; not with --follow)\n"
             "               [--pack-inputs]   (consecutive small files share a batch and are told apart on the GPU; same output; not with --follow)\n"
+            "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -292,6 +297,21 @@ struct Totals {
     unsigned long long lines = 0, lines_with_matches = 0, matches = 0, candidates = 0, bytes = 0;
 };
 
+// --gz-on-gpu: one file of a gz pack, and the statuses of a pack's members (MATCHY_GZ_*) on their way from the worker that scanned the
+// pack to the reader, which reads the members that failed the old way before it submits anything else
+struct GzFile { size_t input; uint64_t offset; uint32_t len, isize; };
+struct GzVerdict {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool done = false;
+    std::vector<int32_t> status;   // empty with done set: the pack was not scanned at all, every member is read the old way
+    void set(const int32_t* st, size_t n) {
+        { std::lock_guard<std::mutex> lk(mu); if (done) return; status.assign(st, st + n); done = true; }
+        cv.notify_all();
+    }
+    void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done; }); }
+};
+
 // ---- `matchy match`: reader -> batches -> one worker per device entry -> ordered printer
 // The pipeline itself is the library's (matchy_multi_scanner_*: one worker thread and scanner per device entry, batches handed out in
 // sequence, results taken back in sequence — processing/parallel.rs:494-505 behind the C ABI). What stays here is what belongs to
@@ -303,7 +323,10 @@ struct Totals {
 struct Batch { size_t input = 0; Bytes own; const uint8_t* ptr = nullptr; size_t len = 0; bool mapped = false;
                const void* reg = nullptr;   // reg: page range of a batch the reader pinned ahead of the scan (unpinned by the worker)
                // --pack-inputs: the files of a pack, one segment each (empty: an ordinary batch of `input`), and the newlines the packer added
-               std::vector<PackedInput> pack; size_t appended = 0; };
+               std::vector<PackedInput> pack; size_t appended = 0;
+               // --gz-on-gpu: the gzip files of a gz pack (`ptr` holds them compressed, end to end), one segment each, and where the
+               // reader waits for the verdict on them
+               std::vector<GzFile> gz; std::shared_ptr<GzVerdict> verdict; };
 // what a batch contributes to the output: `text` / `text_len` is the buffer matchy_scan_result_to_ndjson returned (written to stdout as
 // it is and released by the printer: 200 bytes per match are not copied again on the way), `out` what --follow builds from it
 struct Done {
@@ -339,7 +362,8 @@ struct MatchPipeline {
 
     // every input a batch carries: its own, or the files of a pack
     template <class F> static void each_input(const Batch& b, F&& f) {
-        if (b.pack.empty()) f(b.input);
+        if (!b.gz.empty()) for (const GzFile& g : b.gz) f(g.input);
+        else if (b.pack.empty()) f(b.input);
         else for (const PackedInput& pi : b.pack) f(pi.input);
     }
     // the batch goes to the library's queue; its Batch object travels as the tag and comes back with the result
@@ -348,7 +372,13 @@ struct MatchPipeline {
         size_t seq;
         { std::lock_guard<std::mutex> lk(mu); seq = submitted++; }
         int32_t rc;
-        if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
+        if (!hb->gz.empty()) {   // the text comes back only where something is rendered from it
+            std::vector<matchy_gz_member_t> table;
+            for (const GzFile& g : hb->gz) table.push_back(matchy_gz_member_t{g.offset, g.len, 0});
+            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json, hb);
+            if (rc != MATCHY_SUCCESS) { hb->verdict->set(nullptr, 0); delete hb; return seq; }   // every member goes the old way
+        }
+        else if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
         else {
             std::vector<uint32_t> starts;
             for (const PackedInput& pi : hb->pack) starts.push_back(pi.start);
@@ -385,9 +415,21 @@ struct MatchPipeline {
         const size_t input = b.input;
         d.input = input;
         Totals& t = d.t;
-        // a pack: the newlines the packer appended are not the inputs'
-        t.lines += r.lines - b.appended; t.candidates += r.candidates; t.bytes += len - b.appended; t.matches += r.n_hits;
-        if (line_ctx && !b.pack.empty()) {   // per segment, from the table the GPU filled
+        const bool segmented = !b.pack.empty() || !b.gz.empty();
+        if (!b.gz.empty()) {
+            // a gz pack: lines and bytes are those of the members the GPU accepted (separators and the regions of the others are not
+            // counted); the others are read the old way by the reader, which waits for this verdict
+            t.lines += r.lines; t.candidates += r.candidates; t.bytes += r.bytes; t.matches += r.n_hits;
+            const int32_t* st = nullptr;
+            size_t n_st = 0;
+            if (matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr) != MATCHY_SUCCESS) { st = nullptr; n_st = 0; d.ok = false; }
+            b.verdict->set(st, n_st);
+            if (!d.ok) { fprintf(stderr, "[ERROR] no gz statuses in the scan result of a gz pack: %s\n", matchy_amd_last_error()); return; }
+        } else {
+            // a pack: the newlines the packer appended are not the inputs'
+            t.lines += r.lines - b.appended; t.candidates += r.candidates; t.bytes += len - b.appended; t.matches += r.n_hits;
+        }
+        if (line_ctx && segmented) {   // per segment, from the table the GPU filled
             const matchy_scan_segment_t* segs = nullptr;
             size_t n_segs = 0;
             if (matchy_scan_result_segments(&r, nullptr, nullptr, &segs, &n_segs) == MATCHY_SUCCESS) for (size_t k = 0; k < n_segs; ++k) t.lines_with_matches += segs[k].lines_with_matches;
@@ -413,7 +455,7 @@ struct MatchPipeline {
             char* text = nullptr;
             size_t n = 0;
             int32_t rc;
-            if (b.pack.empty()) rc = matchy_scan_result_to_ndjson(sc, &r, data, source.c_str(), &text, &n);
+            if (!segmented) rc = matchy_scan_result_to_ndjson(sc, &r, data, source.c_str(), &text, &n);
             else { const std::vector<const char*> src = pack_sources(b); rc = matchy_scan_result_to_ndjson_segments(sc, &r, data, src.data(), nullptr, false, &text, &n); }
             if (rc == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
             else { fprintf(stderr, "[ERROR] rendering failed: %s\n", matchy_amd_last_error()); d.ok = false; }
@@ -422,6 +464,7 @@ struct MatchPipeline {
     std::vector<const char*> pack_sources(const Batch& b) const {
         std::vector<const char*> src;
         for (const PackedInput& pi : b.pack) src.push_back(sources[pi.input].c_str());
+        for (const GzFile& g : b.gz) src.push_back(sources[g.input].c_str());
         return src;
     }
     // the records of a batch of a scan with line context; `base` = lines of its input in front of it
@@ -431,10 +474,10 @@ struct MatchPipeline {
         char* text = nullptr;
         size_t n = 0;
         int32_t rc;
-        if (b.pack.empty()) rc = matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[b.input].c_str(), base, input_line, &text, &n);
+        if (b.pack.empty() && b.gz.empty()) rc = matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[b.input].c_str(), base, input_line, &text, &n);
         else {
             const std::vector<const char*> src = pack_sources(b);
-            const std::vector<uint64_t> bases(b.pack.size(), 0);
+            const std::vector<uint64_t> bases(src.size(), 0);
             rc = matchy_scan_result_to_ndjson_segments(sc, &r, data, src.data(), bases.data(), input_line, &text, &n);
         }
         if (rc == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
@@ -478,12 +521,15 @@ struct MatchPipeline {
             Batch* hb = (Batch*)b.tag;
             Done* d = (Done*)b.payload;
             if (b.status != MATCHY_SUCCESS) {
-                fprintf(stderr, "[ERROR] scan failed: %s\n", matchy_amd_last_error());
-                each_input(*hb, [&](size_t i) { input_failed[i] = 1; });
+                if (!hb->gz.empty()) hb->verdict->set(nullptr, 0);   // the pack was not scanned: the reader reads its files the old way
+                else {
+                    fprintf(stderr, "[ERROR] scan failed: %s\n", matchy_amd_last_error());
+                    each_input(*hb, [&](size_t i) { input_failed[i] = 1; });
+                }
             } else if (d) {
                 if (line_ctx) {   // the worker's scanner renders here: with line context its hook renders nothing, so one thread at a time uses it
                     render_numbered(matchy_multi_scanner_worker_scanner(ms, b.worker), b.result, b.data, *hb, line_base[hb->input], *d);
-                    if (hb->pack.empty()) line_base[hb->input] += b.result.lines;
+                    if (hb->pack.empty() && hb->gz.empty()) line_base[hb->input] += b.result.lines;
                 }
                 if (!d->ok) each_input(*hb, [&](size_t i) { input_failed[i] = 1; });   // rendering failed: the batch's matches are missing, exit status says so
                 if (d->text_len) write_all_stdout(d->text, d->text_len);
@@ -639,10 +685,88 @@ void follow_inputs(MatchPipeline& pl, matchy_scanner_t* sc, const std::vector<st
     if (stats) fprintf(stderr, "[INFO] Follow mode stopped\n");
 }
 
+// --gz-on-gpu, the reader's side. take(i) reads an eligible .gz input — a regular file of at least 18 bytes whose header parses, compressed
+// size and ISIZE both at most batch_bytes / 4 (MATCHY_AMD_GZ_MAX_MEMBER lowers that) — into the pack in hand; a pack holds up to batch_bytes
+// of inflated text and goes out when the next file would pass that. Before anything else is submitted, barrier() sends the pack in
+// hand and waits for the verdict on it: the members the GPU did not accept are read the old way there, right behind their pack, so
+// the order of everything else is that of the command line. While a pack is on the GPU the reader goes on reading files for the next.
+struct GzPacker {
+    MatchPipeline& pl;
+    const std::vector<std::string>& paths;
+    std::vector<char>& read_failed;
+    size_t batch_bytes, max_member;
+    std::vector<uint8_t> buf;          // the files of the pack in hand, compressed, end to end
+    std::vector<GzFile> files;
+    uint64_t text = 0;                 // inflated bytes of the pack in hand, separators included
+    std::shared_ptr<GzVerdict> pending;
+    std::vector<GzFile> pending_files;
+    size_t on_gpu = 0, packs = 0, on_host = 0;
+    unsigned long long packed_bytes = 0, text_bytes = 0;
+
+    GzPacker(MatchPipeline& p, const std::vector<std::string>& ps, std::vector<char>& rf, size_t bb) : pl(p), paths(ps), read_failed(rf) {
+        batch_bytes = std::min<size_t>(bb, ((size_t)1 << 31) - ((size_t)1 << 20));   // a batch stays below 2^31 bytes
+        max_member = batch_bytes / 4;
+        if (const char* e = getenv("MATCHY_AMD_GZ_MAX_MEMBER")) max_member = std::min<size_t>(max_member, strtoull(e, nullptr, 10));
+    }
+    bool take(size_t i) {
+        const std::string& path = paths[i];
+        struct stat sb;
+        if (!pack_ends_with_gz(path) || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18 || (size_t)sb.st_size > max_member) return false;
+        const size_t size = (size_t)sb.st_size, at = buf.size();
+        buf.resize(at + size);
+        uint64_t body = 0;
+        const bool whole = pack_read_file(path, buf.data() + at, size) == (long long)size;
+        const bool parses = whole && gz_parse_header(buf.data() + at, size, body) == GZ_PLAN_OK && size - body >= 8;
+        const uint8_t* t = buf.data() + at + size - 4;
+        const uint32_t isize = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+        if (!parses || isize > max_member) { buf.resize(at); return false; }
+        if (!files.empty() && text + isize + 1 > batch_bytes) {   // the file opens the next pack
+            const std::vector<uint8_t> file(buf.begin() + (long)at, buf.end());
+            buf.resize(at);
+            flush();
+            buf = file;
+        }
+        files.push_back(GzFile{i, buf.size() - size, (uint32_t)size, isize});
+        text += (uint64_t)isize + 1;
+        return true;
+    }
+    // the verdict on the pack that is out: what the GPU accepted is counted, the rest is read the old way now
+    void settle() {
+        if (!pending) return;
+        pending->wait();
+        for (size_t k = 0; k < pending_files.size(); ++k) {
+            const GzFile& g = pending_files[k];
+            if (k < pending->status.size() && pending->status[k] == MATCHY_GZ_OK) { ++on_gpu; packed_bytes += g.len; text_bytes += g.isize; continue; }
+            ++on_host;
+            if (!read_input(pl, g.input, paths[g.input], batch_bytes)) read_failed[g.input] = 1;
+        }
+        pending.reset();
+        pending_files.clear();
+    }
+    void flush() {
+        settle();
+        if (files.empty()) return;
+        Batch b;
+        b.own.reset((uint8_t*)malloc(buf.size()));
+        if (!b.own) {   // no memory for the pack: its files go the old way
+            for (const GzFile& g : files) { ++on_host; if (!read_input(pl, g.input, paths[g.input], batch_bytes)) read_failed[g.input] = 1; }
+        } else {
+            memcpy(b.own.get(), buf.data(), buf.size());
+            b.input = files[0].input; b.ptr = b.own.get(); b.len = buf.size();
+            b.gz = files; b.verdict = std::make_shared<GzVerdict>();
+            pending = b.verdict; pending_files = files;
+            ++packs;
+            pl.submit(std::move(b));
+        }
+        buf.clear(); files.clear(); text = 0;
+    }
+    void barrier() { flush(); settle(); }
+};
+
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -672,6 +796,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--line-numbers") line_numbers = true;
         else if (a == "--input-line") input_line = true;
         else if (a == "--pack-inputs") pack = true;
+        else if (a == "--gz-on-gpu") gz_gpu = true;
         else if (a == "--tally") tally = true;
         else if (a.compare(0, 8, "--tally=") == 0) {
             const std::string n = a.substr(8);
@@ -685,6 +810,7 @@ int cmd_match(int argc, char** argv) {
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
     if (follow && tally) { fprintf(stderr, "Error: --tally is not supported with --follow (the report is printed after the last batch)\n"); return 1; }
     if (follow && pack) { fprintf(stderr, "Error: --pack-inputs is not supported with --follow (a followed file grows; a packed one is whole)\n"); return 1; }
+    if (follow && gz_gpu) { fprintf(stderr, "Error: --gz-on-gpu is not supported with --follow (a followed file grows; a gz pack is whole)\n"); return 1; }
     if (follow && stats) fprintf(stderr, "[INFO] Processing existing file content...\n");
     if (follow) for (size_t i = 1; i < pos.size(); ++i) if (pos[i] == "-") { fprintf(stderr, "Error: --follow mode not supported with stdin\n"); return 1; }
     // device list: one worker (scanner) per entry; an entry may repeat (two scanners on one GPU overlap one batch's
@@ -764,7 +890,9 @@ int cmd_match(int argc, char** argv) {
     MatchPipeline pl;
     pl.ms = ms;
     pl.json = format == "json";
-    pl.line_ctx = line_numbers || input_line;
+    // --gz-on-gpu without records to render: no text comes back from a gz pack, so "Lines with matches" is counted on the GPU for every
+    // batch (line context; with --format summary it changes nothing that is printed)
+    pl.line_ctx = line_numbers || input_line || (gz_gpu && format != "json");
     pl.input_line = input_line;
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     if (tally) matchy_multi_scanner_set_tally(ms, true);
@@ -786,23 +914,31 @@ int cmd_match(int argc, char** argv) {
     std::thread printer([&] { pl.printer(t, input_failed); });
     pl.consumed.assign(paths.size(), -1);
     PackStats packed;
+    GzPacker gzp(pl, paths, read_failed, batch_bytes);
+    // an input that is not part of a plain pack: into the gz pack in hand, or, behind that pack and its verdict, the way it is read without the flags
+    auto single = [&](size_t i) {
+        if (gz_gpu && gzp.take(i)) return;
+        if (gz_gpu) gzp.barrier();
+        if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1;
+    };
     if (pack) {
         // runs of small files go out as packs, everything else the way it goes without the flag, in the order of the command line
         packed = pack_inputs(
             paths, batch_bytes,
             [&](InputPack&& p) {
+                if (gz_gpu) gzp.barrier();
                 Batch b;
                 b.input = p.inputs[0].input; b.ptr = p.data.get(); b.len = p.len; b.own = std::move(p.data);
                 b.pack = std::move(p.inputs); b.appended = p.appended;
                 b.reg = prefault_and_pin(b.ptr, b.len);
                 pl.submit(std::move(b));
             },
-            [&](size_t i) { if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1; },
+            single,
             [&](size_t i, int err) { fprintf(stderr, "[ERROR] Failed to process %s: %s\n", paths[i].c_str(), strerror(err)); read_failed[i] = 1; });
     } else {
-        for (size_t i = 0; i < paths.size(); ++i)
-            if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1;
+        for (size_t i = 0; i < paths.size(); ++i) single(i);
     }
+    if (gz_gpu) gzp.barrier();
     pl.reader_done = true;
     printer.join();
     for (size_t i = 0; i < paths.size(); ++i) if (read_failed[i]) input_failed[i] = 1;
@@ -869,6 +1005,8 @@ int cmd_match(int argc, char** argv) {
         fprintf(stderr, "\n[INFO] === Devices ===\n[INFO] HIP devices: %s (%zu scanner%s, batches of %zu MiB)\n", dl.c_str(), n_scanners,
                 n_scanners == 1 ? "" : "s", batch_bytes >> 20);
         if (pack) fprintf(stderr, "[INFO] Packed %zu inputs into %zu batches (%llu bytes of input in all)\n", packed.inputs, packed.packs, t.bytes);
+        if (gz_gpu) fprintf(stderr, "[INFO] Inflated %zu .gz inputs on the GPU in %zu batches (%llu -> %llu bytes), %zu read on the host\n", gzp.on_gpu, gzp.packs,
+                            gzp.packed_bytes, gzp.text_bytes, gzp.on_host);
     }
     matchy_multi_scanner_free(ms);
     matchy_close(db);

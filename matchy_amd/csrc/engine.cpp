@@ -1409,6 +1409,18 @@ void Scanner::arm_segments(size_t len, hipStream_t stream, bool upload) {
     segments_->upload(stream);
 }
 
+// gz scans (inflate.h). The pass and the scan behind it share this scanner's own stream, so nothing waits on the host in between.
+Scanner::GzBatch Scanner::gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n) {
+    MXY_HIP(hipSetDevice(ddb_->device));
+    host_stream_.create(hipStreamNonBlocking);
+    if (!gz_) gz_ = std::make_unique<GzInflate>();
+    gz_->launch(packed, packed_len, members, n, n_cu_, profile_, host_stream_);
+    set_segments(gz_->starts().data(), gz_->starts().size());
+    return GzBatch{gz_->device_text(), gz_->text_len(), host_stream_};
+}
+void Scanner::gz_queue_results(bool want_text) { gz_->queue_results(want_text, host_stream_); }
+GzInflate::Result Scanner::gz_finish() { return gz_->finish(); }
+
 size_t host_piece_bytes() {
     static const size_t v = [] {
         const unsigned long long maxc = 1ull << 30;

@@ -9,6 +9,7 @@
 
 #include "db_image.h"
 #include "hip_owners.h"
+#include "inflate.h"
 #include "line_index.h"
 #include "result_layout.h"
 #include "scan_types.h"
@@ -212,6 +213,16 @@ public:
     const uint32_t* device_segment_of_c4() const { return segments_ ? segments_->device_of_c4() : nullptr; }
     // with set_profile: milliseconds of the segment pass, the record passes and the lines-with-matches pass of the last fetch
     void segment_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (segments_) segments_->timing(out_ms); }
+    // gz scans (inflate.hip): gz_inflate plans the pack of whole gzip files (throws ParamError for a table that breaks its rules),
+    // queues its copy, k_gz_inflate and k_gz_seal on this scanner's own stream and sets the segment table of the batch — member i is
+    // segment i — for the lookup scan the caller then launches on that stream over (text, len). gz_queue_results goes behind the scan's
+    // kernels, gz_finish behind the fetch. Never called, nothing of it is allocated, launched or copied.
+    struct GzBatch { const uint8_t* text; uint32_t len; hipStream_t stream; };
+    GzBatch gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n);
+    void gz_queue_results(bool want_text);
+    GzInflate::Result gz_finish();
+    // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
+    void gz_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (gz_) gz_->timing(out_ms); }
     // Distinct candidate texts (distinct.hip), for extractor handles: while on, a fetch with want_cands returns only the candidates whose
     // text this scanner has not returned since it was created or reset — the set lives in device memory across scans and pieces, and only
     // the survivors are copied back. Off (the default), nothing of it is allocated, launched or copied.
@@ -335,10 +346,11 @@ private:
     DevBuf<FinalHit> final_sorted_;
     DevBuf<ScanCounters> counters_;            // MAX_SLICES entries
     // the passes behind the scan, each created at first use: line context (line_index.h; line_ctx_ is what scan_host asks for),
-    // segmented scans (segments.h), distinct texts (distinct.h), hit tally (tally.h)
+    // segmented scans (segments.h), gz scans (inflate.h), distinct texts (distinct.h), hit tally (tally.h)
     bool line_ctx_ = false;
     std::unique_ptr<LineContext> lines_;       // created by the first fetch of a scan with line context
     std::unique_ptr<SegmentPass> segments_;    // created by the first set_segments with a table
+    std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
     bool tally_on_ = false;

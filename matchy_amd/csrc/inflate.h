@@ -1,0 +1,65 @@
+// gz scans (inflate.hip): a pack of whole gzip files crosses the bus compressed, one wave per file inflates it into its segment of one
+// batch in device memory, and the scan that exists runs over that batch. Launch wrappers, what host and kernels share, and the pass.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "gz_plan.h"
+#include "hip_owners.h"
+
+namespace mxy {
+
+// One member as the kernels see it (GzPlanned without the host's status): body / body_len in the compressed buffer, start / cap in the batch.
+struct GzMemberDev { uint64_t body; uint32_t body_len, start, cap, reserved[3]; };
+static_assert(sizeof(GzMemberDev) == 32, "one member per 32-byte sector");
+
+// Waves (64-thread workgroups) of k_gz_inflate that are resident on one CU at a time.
+int gz_inflate_waves_per_cu();
+// One wave per member of order[0, n_order), claimed from *counter (zeroed by the caller, on a 128-byte line of its own): inflates
+// packed[body, body + body_len) to text[start, start + cap), verifies CRC-32 and ISIZE and writes the member's status. status[] holds
+// the host's verdict on entry; members outside `order` keep it. Nothing is loaded outside packed[0, packed_len) or stored outside
+// text[0, text_len).
+hipError_t gz_inflate_launch(const uint8_t* packed, uint64_t packed_len, const GzMemberDev* members, uint32_t n_members, const uint32_t* order, uint32_t n_order,
+                             uint32_t* counter, uint8_t* text, uint32_t text_len, int32_t* status, int grid, hipStream_t stream);
+// One wave per member: the separator '\n' behind an OK member, the whole region of a failed one (separator included) set to '\n'.
+hipError_t gz_seal_launch(const GzMemberDev* members, uint32_t n_members, const int32_t* status, uint8_t* text, uint32_t text_len, hipStream_t stream);
+
+// The gz pass of a scanner (Scanner::gz_inflate): the plan of the pack in flight and the buffers of the pass, grown on demand and reused
+// between scans. A scan runs as launch() in front of the scan's kernels, queue_results() behind them on the same stream and finish()
+// behind the wait. Not thread-safe, like the scanner. Throws mxy::HipError and, for a table that breaks its rules, mxy::ParamError.
+class GzInflate {
+public:
+    // Plans the pack (gz_plan.h), queues the copies of the compressed bytes and the tables, k_gz_inflate and k_gz_seal on `stream`.
+    void launch(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n, int n_cu, bool profile, hipStream_t stream);
+    const uint8_t* device_text() const { return text_.p; }
+    uint32_t text_len() const { return (uint32_t)plan_.total; }
+    const std::vector<uint32_t>& starts() const { return plan_.starts; }
+    // The statuses, and with want_text the inflated batch, come back into pinned memory.
+    void queue_results(bool want_text, hipStream_t stream);
+    // Behind the wait for `stream`. status / text are BORROWED from the pinned blocks and valid until the next launch(); text is null
+    // without want_text (text_len is the length of the batch either way). ok_bytes: inflated bytes of the OK members; not_input_nl: the '\n' bytes of the batch that are not the input's
+    // (separators and the regions of failed members).
+    struct Result { const int32_t* status = nullptr; size_t n = 0; const uint8_t* text = nullptr; size_t text_len = 0; uint64_t ok_bytes = 0, not_input_nl = 0; };
+    Result finish();
+    // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal of the last profiled launch()
+    void timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = ms_[k]; }
+
+private:
+    GzPlan plan_;
+    std::vector<GzMemberDev> members_host_;
+    std::vector<int32_t> status_host_;
+    DevBuf<uint8_t> packed_, text_;
+    DevBuf<GzMemberDev> members_;
+    DevBuf<uint32_t> order_, counter_;
+    DevBuf<int32_t> status_;
+    PinnedBuf<int32_t> status_pinned_;
+    PinnedBuf<uint8_t> text_pinned_;
+    Event ev_[3];                 // created by the first profiled launch()
+    float ms_[3] = {0, 0, 0};
+    bool timed_ = false, with_text_ = false;
+    int waves_per_cu_ = 0;
+};
+
+}  // namespace mxy

@@ -1,0 +1,332 @@
+// DEFLATE (RFC 1951) decoder rules and the gzip trailer check (RFC 1952), host + device: everything that decides whether a stream is
+// valid and what it decodes to lives here, so that the CPU suite can run the rules of k_gz_inflate (inflate.hip) over corrupt streams
+// under a sanitizer before any of them reaches a GPU (tests/cpp/test_inflate_core.cpp drives this header sequentially).
+//
+// One decoder (the state of one member) turns compressed bits into TOKENS: a literal byte, a (length, distance) match or a run of stored
+// bytes, each with the output position it writes. Whoever executes the tokens (a wave, or the test's loop) only copies bytes. A token
+// is handed out only after its bounds are known to hold: position + length <= the member's capacity, distance <= bytes produced.
+//
+// Tables are canonical: count[len] codes of every length and the symbols in code order, decoded bit by bit (<= 15 turns), with a
+// first-level table of FAST_BITS bits in front for the literal/length code. A code is refused the way zlib's inflate_table refuses it:
+// over-subscribed always; incomplete unless it is a single code of one bit (literal/length and distance codes only).
+//
+// Loop bounds: the bit reader loads at most 8 bytes per refill and never at or behind `end`; a symbol takes at most 15 turns; a code
+// build takes n + 15 turns and at most 2^FAST_BITS table stores (Kraft sum <= 1, checked first); the code-length loop of a dynamic
+// header advances by at least one of its HLIT + HDIST <= 316 entries per turn; a batch of tokens consumes at least one input bit per
+// turn of its loop or ends.
+#pragma once
+#include <cstdint>
+
+#include "hashes.h"   // MXY_HD
+
+namespace mxy {
+namespace gz {
+
+// Status of one member, bit-identical to MATCHY_GZ_* (include/matchy_amd.h). The first error in stream order ends the member; behind a
+// stream that ended, the trailer checks run in the order TRUNCATED, SIZE_MISMATCH, CRC_MISMATCH, TRAILING_DATA.
+enum : int32_t {
+    GZ_OK = 0, GZ_BAD_HEADER = 1, GZ_TRUNCATED = 2, GZ_BAD_BLOCK = 3, GZ_BAD_CODES = 4, GZ_BAD_SYMBOL = 5, GZ_BAD_DISTANCE = 6,
+    GZ_OVERFLOW = 7, GZ_SIZE_MISMATCH = 8, GZ_CRC_MISMATCH = 9, GZ_TRAILING_DATA = 10
+};
+
+constexpr uint32_t FAST_BITS = 9, FAST_SIZE = 1u << FAST_BITS;
+constexpr uint32_t MAX_LENS = 320;   // HLIT + HDIST <= 286 + 30, and the 288 + 32 lengths of the fixed codes
+
+// 2176 bytes; k_gz_inflate keeps one per wave in LDS.
+struct Tables {
+    uint16_t fast[FAST_SIZE];   // literal/length codes of <= FAST_BITS bits by their (bit-reversed) code: symbol << 4 | bits; 0 = none
+    uint16_t len_count[16], len_sym[288];
+    uint16_t dist_count[16], dist_sym[32];   // while a dynamic header is read: the code-length code
+    uint16_t offs[16], next[16];             // scratch of build_code
+    uint8_t lens[MAX_LENS];                  // code lengths as read
+};
+
+// Compressed bytes of one member: in[0, end). Low bits of `buf` come first; cnt of them are valid, the rest is zero.
+struct BitReader {
+    const uint8_t* in;
+    uint32_t pos, end;
+    uint64_t buf;
+    uint32_t cnt;
+};
+
+MXY_HD void br_fill(BitReader& b) {
+    while (b.cnt <= 56u && b.pos < b.end) { b.buf |= (uint64_t)b.in[b.pos++] << b.cnt; b.cnt += 8u; }
+}
+// n <= 16 bits; false: the input ends first (nothing is consumed)
+MXY_HD bool br_take(BitReader& b, uint32_t n, uint32_t& v) {
+    if (b.cnt < n) { br_fill(b); if (b.cnt < n) return false; }
+    v = (uint32_t)b.buf & ((1u << n) - 1u);
+    b.buf >>= n; b.cnt -= n;
+    return true;
+}
+// drops the bits up to the next byte boundary and returns the position of that byte
+MXY_HD uint32_t br_align(BitReader& b) {
+    const uint32_t drop = b.cnt & 7u;
+    b.buf >>= drop; b.cnt -= drop;
+    return b.pos - b.cnt / 8u;
+}
+MXY_HD void br_seek(BitReader& b, uint32_t pos) { b.pos = pos; b.buf = 0; b.cnt = 0; }
+
+constexpr int SYM_TRUNCATED = -1, SYM_NONE = -2;
+
+// One symbol of a canonical code, bit by bit: the code of length len is `code`, the first code of that length is `first`.
+MXY_HD int decode_sym(BitReader& b, const uint16_t* count, const uint16_t* sym) {
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= 15; ++len) {
+        uint32_t bit;
+        if (!br_take(b, 1, bit)) return SYM_TRUNCATED;
+        code |= (int)bit;
+        const int c = count[len];
+        if (code - c < first) return sym[index + (code - first)];
+        index += c; first += c;
+        first <<= 1; code <<= 1;
+    }
+    return SYM_NONE;   // an incomplete code, and these bits are none of its codes
+}
+MXY_HD int decode_lit(BitReader& b, const Tables& t) {
+    br_fill(b);
+    const uint32_t e = t.fast[(uint32_t)b.buf & (FAST_SIZE - 1u)];
+    const uint32_t bits = e & 15u;
+    if (e && bits <= b.cnt) { b.buf >>= bits; b.cnt -= bits; return (int)(e >> 4); }
+    return decode_sym(b, t.len_count, t.len_sym);
+}
+
+enum CodeKind { CODE_LENGTHS = 0, CODE_LITLEN = 1, CODE_DIST = 2 };
+
+// lens[0, n) -> count[16] and sym[n] (and t.fast for CODE_LITLEN). GZ_OK or GZ_BAD_CODES.
+MXY_HD int32_t build_code(Tables& t, const uint8_t* lens, uint32_t n, uint16_t* count, uint16_t* sym, CodeKind kind) {
+    for (int l = 0; l < 16; ++l) count[l] = 0;
+    for (uint32_t i = 0; i < n; ++i) count[lens[i] & 15u]++;
+    int max = 15;
+    while (max > 0 && count[max] == 0) --max;
+    int left = 1;
+    for (int l = 1; l <= 15; ++l) {
+        left = (left << 1) - (int)count[l];
+        if (left < 0) return GZ_BAD_CODES;   // over-subscribed
+    }
+    if (max == 0) {                          // no code at all: every symbol read through it fails; a code-length code cannot be empty
+        if (kind == CODE_LENGTHS) return GZ_BAD_CODES;
+    } else if (left > 0 && (kind == CODE_LENGTHS || max != 1)) return GZ_BAD_CODES;   // incomplete
+    t.offs[1] = 0; t.next[1] = 0;
+    for (int l = 1; l < 15; ++l) {
+        t.offs[l + 1] = (uint16_t)(t.offs[l] + count[l]);
+        t.next[l + 1] = (uint16_t)((t.next[l] + count[l]) << 1);
+    }
+    if (kind == CODE_LITLEN) for (uint32_t i = 0; i < FAST_SIZE; ++i) t.fast[i] = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = lens[i] & 15u;
+        if (!l) continue;
+        sym[t.offs[l]++] = (uint16_t)i;
+        const uint32_t code = t.next[l]++;
+        if (kind != CODE_LITLEN || l > FAST_BITS) continue;
+        uint32_t rev = 0;
+        for (uint32_t k = 0; k < l; ++k) rev |= ((code >> k) & 1u) << (l - 1u - k);
+        for (uint32_t e = rev; e < FAST_SIZE; e += 1u << l) t.fast[e] = (uint16_t)(i << 4 | l);
+    }
+    return GZ_OK;
+}
+
+MXY_HD int32_t build_fixed(Tables& t) {
+    for (uint32_t i = 0; i < 288u; ++i) t.lens[i] = (uint8_t)(i < 144u ? 8 : i < 256u ? 9 : i < 280u ? 7 : 8);
+    for (uint32_t i = 288u; i < 320u; ++i) t.lens[i] = 5;   // 32 distance codes: 30 and 31 decode, and are refused as symbols
+    const int32_t e = build_code(t, t.lens, 288, t.len_count, t.len_sym, CODE_LITLEN);
+    return e ? e : build_code(t, t.lens + 288, 32, t.dist_count, t.dist_sym, CODE_DIST);
+}
+
+// The header of a dynamic block. GZ_OK, GZ_TRUNCATED or GZ_BAD_CODES.
+MXY_HD int32_t read_dynamic(BitReader& b, Tables& t) {
+    uint32_t hlit, hdist, hclen, v;
+    if (!br_take(b, 5, hlit) || !br_take(b, 5, hdist) || !br_take(b, 4, hclen)) return GZ_TRUNCATED;
+    hlit += 257u; hdist += 1u; hclen += 4u;
+    if (hlit > 286u || hdist > 30u) return GZ_BAD_CODES;
+    // the order of the code-length code's lengths, five bits each: 16 17 18 0 8 7 9 6 10 5 11 4 | 12 3 13 2 14 1 15
+    const uint64_t order_lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 | 5ull << 45 | 11ull << 50 | 4ull << 55;
+    const uint64_t order_hi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
+    for (uint32_t i = 0; i < 19u; ++i) t.lens[i] = 0;
+    for (uint32_t i = 0; i < hclen; ++i) {
+        if (!br_take(b, 3, v)) return GZ_TRUNCATED;
+        const uint32_t at = (uint32_t)((i < 12u ? order_lo >> (5u * i) : order_hi >> (5u * (i - 12u))) & 31u);
+        t.lens[at] = (uint8_t)v;
+    }
+    if (build_code(t, t.lens, 19, t.dist_count, t.dist_sym, CODE_LENGTHS)) return GZ_BAD_CODES;
+    const uint32_t total = hlit + hdist;
+    for (uint32_t idx = 0; idx < total;) {
+        const int s = decode_sym(b, t.dist_count, t.dist_sym);
+        if (s < 0) return s == SYM_TRUNCATED ? GZ_TRUNCATED : GZ_BAD_CODES;
+        if (s < 16) { t.lens[idx++] = (uint8_t)s; continue; }
+        uint32_t prev = 0, rep;
+        if (s == 16) {
+            if (idx == 0) return GZ_BAD_CODES;   // nothing to repeat
+            prev = t.lens[idx - 1];
+            if (!br_take(b, 2, v)) return GZ_TRUNCATED;
+            rep = 3u + v;
+        } else if (s == 17) {
+            if (!br_take(b, 3, v)) return GZ_TRUNCATED;
+            rep = 3u + v;
+        } else {
+            if (!br_take(b, 7, v)) return GZ_TRUNCATED;
+            rep = 11u + v;
+        }
+        if (idx + rep > total) return GZ_BAD_CODES;   // a repeat may cross from the literal/length lengths into the distance lengths, not past both
+        for (uint32_t k = 0; k < rep; ++k) t.lens[idx++] = (uint8_t)prev;
+    }
+    if (t.lens[256] == 0) return GZ_BAD_CODES;   // no end of block
+    // the code-length code in dist_count / dist_sym is done with: the distance code takes its place
+    if (build_code(t, t.lens, hlit, t.len_count, t.len_sym, CODE_LITLEN)) return GZ_BAD_CODES;
+    return build_code(t, t.lens + hlit, hdist, t.dist_count, t.dist_sym, CODE_DIST);
+}
+
+// A token: `pos` is the first output byte it writes (relative to the member). v: bit 31 clear = literal, the byte in bits 0..7; bit 31
+// set = match, length (3..258) in bits 0..8 and distance (1..32768) in bits 9..24.
+struct Token { uint32_t pos, v; };
+constexpr uint32_t TOKEN_MATCH = 0x80000000u;
+MXY_HD bool token_is_match(const Token& t) { return (t.v & TOKEN_MATCH) != 0; }
+MXY_HD uint32_t token_len(const Token& t) { return t.v & 511u; }
+MXY_HD uint32_t token_dist(const Token& t) { return (t.v >> 9) & 0xFFFFu; }
+// byte i of a match at `pos` is a copy of this byte; a distance below the length repeats the last `dist` bytes
+MXY_HD uint32_t match_src(uint32_t pos, uint32_t dist, uint32_t i) { return pos - dist + (i < dist ? i : i % dist); }
+
+struct Decoder {
+    BitReader br;
+    uint32_t produced, cap;   // bytes handed out as tokens so far; the member's capacity
+    int32_t status;           // GZ_OK while the stream is sound
+    bool in_block, final, done;   // inside a Huffman block; the block in hand is the last; the last block has ended
+};
+MXY_HD void decoder_init(Decoder& d, const uint8_t* in, uint32_t in_len, uint32_t cap) {
+    d.br.in = in; d.br.pos = 0; d.br.end = in_len; d.br.buf = 0; d.br.cnt = 0;
+    d.produced = 0; d.cap = cap; d.status = GZ_OK;
+    d.in_block = false; d.final = false; d.done = false;
+}
+
+// What one call of decode_batch hands out: q[0, n) in stream order, then (stored_len != 0) stored_len bytes from in[stored_src ..) to
+// stored_pos. The executor writes the literals, then the matches one after another, then the stored run.
+struct Batch { uint32_t n, stored_src, stored_len, stored_pos; };
+
+// Decodes until the queue is full, a stored run is due, the stream ends (d.done) or an error (d.status).
+MXY_HD void decode_batch(Decoder& d, Tables& t, Token* q, uint32_t max_q, Batch& out) {
+    BitReader& b = d.br;
+    out.n = 0; out.stored_src = 0; out.stored_len = 0; out.stored_pos = 0;
+    uint32_t v;
+    while (out.n < max_q && !d.done && d.status == GZ_OK) {
+        if (!d.in_block) {
+            if (d.final) { d.done = true; break; }
+            uint32_t type;
+            if (!br_take(b, 1, v) || !br_take(b, 2, type)) { d.status = GZ_TRUNCATED; break; }
+            d.final = v != 0;
+            if (type == 0) {
+                uint32_t len, nlen;
+                (void)br_align(b);
+                if (!br_take(b, 16, len) || !br_take(b, 16, nlen)) { d.status = GZ_TRUNCATED; break; }
+                if ((len ^ 0xFFFFu) != nlen) { d.status = GZ_BAD_BLOCK; break; }
+                const uint32_t at = br_align(b);
+                if (len > b.end - at) { d.status = GZ_TRUNCATED; break; }
+                if (len > d.cap - d.produced) { d.status = GZ_OVERFLOW; break; }
+                br_seek(b, at + len);
+                if (len) {
+                    out.stored_src = at; out.stored_len = len; out.stored_pos = d.produced;
+                    d.produced += len;
+                    break;   // what follows may copy from these bytes: they are written first
+                }
+            } else if (type == 1) {
+                d.status = build_fixed(t);
+                d.in_block = true;
+            } else if (type == 2) {
+                d.status = read_dynamic(b, t);
+                d.in_block = true;
+            } else d.status = GZ_BAD_BLOCK;
+            continue;
+        }
+        const int s = decode_lit(b, t);
+        if (s < 0) { d.status = s == SYM_TRUNCATED ? GZ_TRUNCATED : GZ_BAD_SYMBOL; break; }
+        if (s < 256) {
+            if (d.produced >= d.cap) { d.status = GZ_OVERFLOW; break; }
+            q[out.n].pos = d.produced++; q[out.n].v = (uint32_t)s; ++out.n;
+            continue;
+        }
+        if (s == 256) { d.in_block = false; continue; }
+        if (s >= 286) { d.status = GZ_BAD_SYMBOL; break; }
+        // lengths 3..258 from symbols 257..285, distances 1..32768 from symbols 0..29: base and extra bits follow from the symbol
+        const uint32_t ls = (uint32_t)s - 257u;
+        uint32_t len = 3u + ls;
+        if (ls == 28u) len = 258u;
+        else if (ls >= 8u) {
+            const uint32_t eb = (ls >> 2) - 1u;
+            if (!br_take(b, eb, v)) { d.status = GZ_TRUNCATED; break; }
+            len = 3u + ((4u + (ls & 3u)) << eb) + v;
+        }
+        const int ds = decode_sym(b, t.dist_count, t.dist_sym);
+        if (ds < 0) { d.status = ds == SYM_TRUNCATED ? GZ_TRUNCATED : GZ_BAD_SYMBOL; break; }
+        if (ds >= 30) { d.status = GZ_BAD_SYMBOL; break; }
+        uint32_t dist = 1u + (uint32_t)ds;
+        if (ds >= 4) {
+            const uint32_t eb = ((uint32_t)ds >> 1) - 1u;
+            if (!br_take(b, eb, v)) { d.status = GZ_TRUNCATED; break; }
+            dist = 1u + ((2u + ((uint32_t)ds & 1u)) << eb) + v;
+        }
+        if (dist > d.produced) { d.status = GZ_BAD_DISTANCE; break; }
+        if (len > d.cap - d.produced) { d.status = GZ_OVERFLOW; break; }
+        q[out.n].pos = d.produced; q[out.n].v = TOKEN_MATCH | len | dist << 9; ++out.n;
+        d.produced += len;
+    }
+}
+
+// Behind a stream that ended (d.done): the 8-byte trailer follows the last block's last byte. `crc` is the CRC-32 of the output.
+MXY_HD int32_t check_trailer(Decoder& d, uint32_t crc) {
+    const uint32_t at = br_align(d.br);
+    const BitReader& b = d.br;
+    if (b.end - at < 8u) return GZ_TRUNCATED;
+    const uint8_t* p = b.in + at;
+    const uint32_t want_crc = p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+    const uint32_t isize = p[4] | (uint32_t)p[5] << 8 | (uint32_t)p[6] << 16 | (uint32_t)p[7] << 24;
+    if (d.produced != d.cap || isize != d.produced) return GZ_SIZE_MISMATCH;
+    if (want_crc != crc) return GZ_CRC_MISMATCH;
+    return b.end - at == 8u ? GZ_OK : GZ_TRAILING_DATA;
+}
+
+// ---- CRC-32 (reflected, polynomial 0xEDB88320) in pieces: a lane takes crc_bytes over its chunk, multiplies it by x^(8 * bytes behind
+// the chunk) mod the polynomial, and the xor of all lanes' products is the CRC of the whole (the CRC of the empty string is 0).
+constexpr uint32_t CRC_POLY = 0xEDB88320u;
+MXY_HD uint32_t crc_table_entry(uint32_t i) {
+    uint32_t c = i;
+    for (int k = 0; k < 8; ++k) c = (c & 1u) ? CRC_POLY ^ (c >> 1) : c >> 1;
+    return c;
+}
+MXY_HD uint32_t crc_bytes(const uint32_t* table, const uint8_t* p, uint32_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t i = 0; i < n; ++i) c = table[(c ^ p[i]) & 255u] ^ (c >> 8);
+    return ~c;
+}
+// a * b mod the polynomial, bit 31 = x^0: 32 shift-and-xor steps
+MXY_HD uint32_t crc_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int k = 31; k >= 0; --k) {
+        if (a >> k & 1u) p ^= b;
+        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    return p;
+}
+// x^(8 * nbytes): square and multiply over the 35 bits of the exponent
+MXY_HD uint32_t crc_xpow8(uint32_t nbytes) {
+    uint64_t e = (uint64_t)nbytes * 8u;
+    uint32_t r = 0x80000000u, sq = 0x40000000u;   // x^0, x^1
+    for (int k = 0; k < 36 && e; ++k, e >>= 1) {
+        if (e & 1u) r = crc_mul(sq, r);
+        sq = crc_mul(sq, sq);
+    }
+    return r;
+}
+// chunk of lane `lane` of `lanes` over n bytes: [begin, begin + len)
+MXY_HD void crc_chunk(uint32_t n, uint32_t lane, uint32_t lanes, uint32_t& begin, uint32_t& len) {
+    const uint32_t per = (n + lanes - 1u) / lanes;
+    begin = lane * per < n ? lane * per : n;
+    len = n - begin < per ? n - begin : per;
+}
+MXY_HD uint32_t crc_lane_part(const uint32_t* table, const uint8_t* out, uint32_t n, uint32_t lane, uint32_t lanes) {
+    uint32_t begin, len;
+    crc_chunk(n, lane, lanes, begin, len);
+    if (!len) return 0;
+    return crc_mul(crc_bytes(table, out + begin, len), crc_xpow8(n - begin - len));
+}
+
+}  // namespace gz
+}  // namespace mxy

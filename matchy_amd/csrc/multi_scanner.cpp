@@ -28,7 +28,7 @@ using namespace mxy;
 using namespace mxy::capi;
 
 namespace {
-struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments)
+struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz)
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
     const matchy_t* db = nullptr;
@@ -86,6 +86,14 @@ struct MultiScanner {
             if (!scanners[w]) scanners[w] = matchy_scanner_create(db, flags, devices[w]);
             std::string err;
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
+            else if (!j.gz.empty()) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
+                matchy_scanner_set_line_context(scanners[w], want_lines);
+                if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
+                d.status = matchy_scanner_scan_gz(scanners[w], j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res);
+                d.data = nullptr; d.len = 0;
+                if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
+                else (void)matchy_scan_result_gz(&d.res, nullptr, nullptr, &d.data, &d.len);
+            }
             else if (j.len || !j.starts.empty()) {   // an empty batch with a table is scanned too: its result carries the table
                 matchy_scanner_set_line_context(scanners[w], want_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
@@ -93,7 +101,7 @@ struct MultiScanner {
                 if (d.status == MATCHY_SUCCESS) d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
-            if (d.status == MATCHY_SUCCESS && hook) d.payload = hook(hook_user, w, scanners[w], &d.res, j.data, j.len, j.tag);
+            if (d.status == MATCHY_SUCCESS && hook) d.payload = hook(hook_user, w, scanners[w], &d.res, d.data, d.len, j.tag);
             if (j.pinned) matchy_amd_host_unregister(j.pinned);   // behind the hook: the unpin of this batch then runs beside the next worker's copy, not in front of this one's per-hit work
             std::lock_guard<std::mutex> lk(mu);
             if (!err.empty() && first_error.empty()) first_error = err;
@@ -232,7 +240,7 @@ int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t* h, const uint8_
     // blocks while the job queue is full OR max_inflight batches are out (someone has to call matchy_multi_scanner_next: a caller that
     // submits and gathers on ONE thread interleaves the two — matchy_multi_scanner_pending() tells it when a next() is due)
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}});
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}, {}, false});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }
@@ -243,7 +251,18 @@ int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t* h, const ui
     std::vector<uint32_t> table(starts, starts + n);   // copied in front of the lock
     std::unique_lock<std::mutex> lk(ms->mu);
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table)});
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table), {}, false});
+    ms->cv_work.notify_one();
+    return MATCHY_SUCCESS;
+}
+int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, bool want_text,
+                                       void* tag) {
+    if (!h || (!packed && packed_len) || !members || n == 0) { set_error("matchy_multi_scanner_submit_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::vector<matchy_gz_member_t> table(members, members + n);   // copied in front of the lock
+    std::unique_lock<std::mutex> lk(ms->mu);
+    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
+    ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, std::move(table), want_text});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }
