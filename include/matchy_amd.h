@@ -339,6 +339,38 @@ int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t *scanner, const matc
                                            const char *source, uint64_t line_base, bool with_input_line, char **out, size_t *out_len);
 /* With matchy_scanner_set_profile: milliseconds of the streaming '\n' count, the prefix sum, and resolve + distinct set of the last scan. */
 void matchy_scanner_get_line_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* ---- Hit lines (opt-in, off by default: a scanner that never enabled it allocates, launches and copies nothing more, and every other
+ * output stays byte for byte what it is). A caller that renders records needs the bytes of the lines that hit, not the batch: a pass
+ * behind line context packs the DISTINCT lines with at least one hit into one contiguous block on the GPU, in ascending line order,
+ * each ended by one '\n', and only that block and small index arrays cross the bus. With n_lines == lines_with_matches lines k = 0 ..
+ * n_lines - 1:
+ *   text[line_off[k] .. line_off[k+1] - 1) are the bytes batch[line_start .. line_end) of the line (a '\r' in front of the '\n' belongs
+ *   to it, as in matchy_scan_line_t); text[line_off[k+1] - 1] == '\n' always, also for an unterminated last line;
+ *   line_off[n_lines] == text_len, and text_len <= len + 1 (the lines are disjoint pieces of the batch and only an unterminated last
+ *   line gains a byte), so the offsets are 32-bit; line_no[k] is the line's index in the batch, strictly ascending;
+ *   line_of_hit[i] / line_of_ip4_hit[i] give k for hits[i] / ip4_hits[i], in the order of those arrays.
+ * The text of hit i lies at text + line_off[k] + (hits[i].start - lines[i].line_start), with lines from matchy_scan_result_lines: a
+ * match never spans a '\n'. The block depends on the batch and the set of hits alone, not on the order of the device's records. */
+typedef struct matchy_scan_hit_lines_t {
+  const uint8_t *text;
+  uint64_t text_len;
+  uint32_t n_lines;
+  const uint32_t *line_off, *line_no, *line_of_hit, *line_of_ip4_hit;
+} matchy_scan_hit_lines_t;
+/* Applies to the scanner's next scan through every entry (read at submit, like line context, which it turns on for that scan: the
+ * result also answers matchy_scan_result_lines). */
+void matchy_scanner_set_hit_lines(matchy_scanner_t *scanner, bool enabled);
+bool matchy_scanner_hit_lines(const matchy_scanner_t *scanner);
+/* Ownership, lifetime and residency follow the hit arrays of the result, as for matchy_scan_result_lines: borrowed from the scanner
+ * until its next scan, owned by the result for MATCHY_SCAN_FETCH_SORTED and matchy_scanner_scan, DEVICE pointers (text included; nothing
+ * of the block is copied) for MATCHY_SCAN_FETCH_DEVICE. For MATCHY_SCAN_FETCH_COUNTS the gather does not run: the pointers are NULL,
+ * text_len is 0 and n_lines = lines_with_matches. MATCHY_ERROR_INVALID_PARAM for a result produced with the setting off.
+ * For a host-resident result that carries hit lines, matchy_scan_hit_to_json and the matchy_scan_result_to_ndjson* calls take the
+ * matched text and "input_line" from the block and ignore `text`, which may be NULL; their output is what the whole batch gives. */
+int32_t matchy_scan_result_hit_lines(const matchy_scan_result_t *result, matchy_scan_hit_lines_t *out);
+/* With matchy_scanner_set_profile: milliseconds of the index steps (mark, rank, lengths, offsets), of the copy kernel, and of the
+ * block's device-to-host copy (0 where nothing is copied) of the last scan. */
+void matchy_scanner_get_hit_lines_timing(const matchy_scanner_t *scanner, float out_ms[3]);
 /* ---- Segmented scans: many small inputs as one batch.
  * The caller describes a buffer as a sequence of segments (the files of a pack): the scan runs once, as for any buffer, and a pass
  * behind it attributes every hit record to its segment on the GPU and counts per segment. '\n' is a boundary for every extractor, so
@@ -542,6 +574,10 @@ int32_t matchy_multi_scanner_scan_file(matchy_multi_scanner_t *ms, const char *p
 /* Line context for the scanner of every worker (from the next batch a worker takes). Batches from _next carry values relative to
  * their batch; matchy_multi_scanner_scan merges them into values relative to `data`, like matchy_scanner_scan. */
 void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t *ms, bool enabled);
+/* Hit lines for the scanner of every worker (from the next batch a worker takes). Batches from _next answer
+ * matchy_scan_result_hit_lines (and _lines), owned by the result, and render with text == NULL — a gz batch submitted without want_text
+ * included, whose `data` is NULL. The merged results of matchy_multi_scanner_scan / _scan_file do not carry the block. */
+void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t *ms, bool enabled);
 
 /* ---- Hit tally (opt-in, off by default: with it never enabled a scanner allocates, launches and copies nothing more and every output
  * stays as it is). How often every distinct matched value hit: a table in device memory, owned by the scanner, keyed by (item type,

@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_set_segments", "matchy_scan_result_segments", "matchy_scan_result_to_ndjson_segments",
     "matchy_multi_scanner_submit_segments", "matchy_scanner_get_segment_timing",
     "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
+    "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
+    "matchy_multi_scanner_set_hit_lines",
 ]
 
 # MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
@@ -69,6 +71,9 @@ GZ_STATUS_NAMES = ["OK", "BAD_HEADER", "TRUNCATED", "BAD_BLOCK", "BAD_CODES", "B
 # kernels take another path
 LINE_TILE = 1024
 LINE_SCAN_CHUNK = 2048
+# bytes of the block of hit lines one wave of the copy kernel owns, and entries per workgroup of its prefix sums (csrc/hit_lines.h)
+HIT_LINES_SLICE = 4096
+HIT_LINES_SCAN_CHUNK = 2048
 
 
 class _Result(C.Structure):
@@ -120,6 +125,12 @@ class _ScanResult(C.Structure):
                 ("data_offsets", C.POINTER(C.c_int64)), ("n_ids", C.c_size_t), ("lines", C.c_uint64),
                 ("candidates", C.c_uint64), ("bytes", C.c_uint64), ("ip4_hits", C.POINTER(C.c_uint32 * 2)),
                 ("n_ip4_hits", C.c_size_t), ("_internal", C.c_void_p)]
+
+
+class _ScanHitLines(C.Structure):
+    # matchy_scan_hit_lines_t
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_uint64), ("n_lines", C.c_uint32), ("line_off", C.c_void_p), ("line_no", C.c_void_p),
+                ("line_of_hit", C.c_void_p), ("line_of_ip4_hit", C.c_void_p)]
 
 
 class _ScanLine(C.Structure):
@@ -264,6 +275,11 @@ def lib():
         "matchy_multi_scanner_set_line_context": (None, [vp, C.c_bool]),
         "matchy_scan_result_to_ndjson_lines": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, cp, C.c_uint64, C.c_bool, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_line_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_set_hit_lines": (None, [vp, C.c_bool]),
+        "matchy_scanner_hit_lines": (C.c_bool, [vp]),
+        "matchy_scan_result_hit_lines": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(_ScanHitLines)]),
+        "matchy_scanner_get_hit_lines_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_multi_scanner_set_hit_lines": (None, [vp, C.c_bool]),
         "matchy_scanner_set_segments": (C.c_int32, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "matchy_scan_result_segments": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scan_result_to_ndjson_segments": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, C.POINTER(cp), C.POINTER(C.c_uint64), C.c_bool,
@@ -665,6 +681,34 @@ class ScanResult:
         ga = self._gz_arrays()
         return None if ga is None else ga[3]
 
+    def hit_lines(self):
+        """the block of the distinct lines with a hit (Scanner.set_hit_lines; matchy_scan_result_hit_lines) as a dict: text (bytes),
+        text_len, n_lines and the uint32 numpy arrays line_off (n_lines + 1), line_no, line_of_hit, line_of_ip4_hit (None where the
+        result has none: a counts-only fetch). For a device result (fetch_mode 4) text and the arrays are raw device addresses (0 =
+        none). None for a result scanned with the setting off."""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        h = _ScanHitLines()
+        if lib().matchy_scan_result_hit_lines(C.byref(self._raw), C.byref(h)) != 0:
+            return None
+        n_hits = self._raw.n_hits if self._raw.hits else 0
+        n_ip4 = self._raw.n_ip4_hits if self._raw.ip4_hits else 0
+        out = dict(text_len=int(h.text_len), n_lines=int(h.n_lines), on_device=self.on_device)
+        if self.on_device:
+            out.update(text=h.text or 0, line_off=h.line_off or 0, line_no=h.line_no or 0, line_of_hit=h.line_of_hit or 0, line_of_ip4_hit=h.line_of_ip4_hit or 0)
+            return out
+        import numpy as np
+
+        def arr(ptr, n):
+            if not ptr:
+                return None
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        gathered = bool(h.line_off)   # false: a counts-only fetch, which carries n_lines alone
+        out.update(text=C.string_at(h.text, h.text_len) if h.text else (b"" if gathered else None),
+                   line_off=arr(h.line_off, h.n_lines + 1), line_no=arr(h.line_no, h.n_lines),
+                   line_of_hit=arr(h.line_of_hit, n_hits), line_of_ip4_hit=arr(h.line_of_ip4_hit, n_ip4))
+        return out
+
     def _line_arrays(self):
         """(lines pointer, ip4_lines pointer, lines_with_matches) of a result scanned with line context, else None"""
         if self._raw is None:
@@ -839,6 +883,19 @@ class Scanner:
     def line_context(self) -> bool:
         return bool(lib().matchy_scanner_line_context(self._h))
 
+    def set_hit_lines(self, on: bool):
+        """hit lines for the next scans: ScanResult.hit_lines(), and the NDJSON calls render with text=None (off by default; turns
+        line context on for those scans)"""
+        lib().matchy_scanner_set_hit_lines(self._h, bool(on))
+
+    def hit_lines_enabled(self) -> bool:
+        return bool(lib().matchy_scanner_hit_lines(self._h))
+
+    def hit_lines_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_hit_lines_timing(self._h, out)
+        return dict(index=out[0], copy_kernel=out[1], d2h=out[2])
+
     def line_timing_ms(self):
         out = (C.c_float * 3)()
         lib().matchy_scanner_get_line_timing(self._h, out)
@@ -954,6 +1011,10 @@ class MultiScanner:
         """line context for every worker's scanner, from the next batch on"""
         lib().matchy_multi_scanner_set_line_context(self._h, bool(on))
 
+    def set_hit_lines(self, on: bool):
+        """hit lines for every worker's scanner, from the next batch on: batches from next() answer hit_lines() and render without text"""
+        lib().matchy_multi_scanner_set_hit_lines(self._h, bool(on))
+
     def set_tally(self, on=True):
         """hit tally on every worker's scanner, from the next batch on"""
         rc = lib().matchy_multi_scanner_set_tally(self._h, bool(on))
@@ -1028,6 +1089,11 @@ class MultiScanner:
             out["segments"] = r.segments
             if want_hits:
                 out["segment_of"] = r.segment_of
+        hl = r.hit_lines()
+        if hl is not None:   # set_hit_lines: the block, and with want_hits the records rendered from it alone
+            out["hit_lines"] = hl
+            if want_hits:
+                out["ndjson_lines"] = r.ndjson_lines_text(None, with_input_line=True)
         gz = r.gz_status()
         if gz is not None:   # a gz batch: data / len are the inflated text (NULL without want_text) and its length
             out["gz_status"] = gz

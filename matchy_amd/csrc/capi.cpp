@@ -133,6 +133,7 @@ struct ScannerH {
     size_t pending_len = 0;
     uint32_t pending_mode = 0;
     void* pending_stream = nullptr;
+    bool pending_hit_lines = false;   // the scanner's hit-lines setting when the batch was submitted
 };
 
 int type_rank(uint32_t t) {  // chunk-path extractor order (matchy-extractor/src/lib.rs:449-485)
@@ -272,6 +273,58 @@ void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, ma
         in->lines = reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines);
         in->ip4_lines = reinterpret_cast<const matchy_scan_line_t*>(so.c4_lines);
     }
+}
+
+// Hit lines. What the scan entries ask of the engine for a fetch mode: the setting turns line context on for the scan, and a fetch that
+// hands out no records (MATCHY_SCAN_FETCH_COUNTS) gathers nothing. Returns the setting, which the entry hands to attach_hit_lines.
+bool request_lines(const Scanner& sc, uint32_t fetch_mode, ScanRequest& rq) {
+    rq.lines = sc.line_context() || sc.hit_lines();
+    rq.hit_lines = sc.hit_lines() && ((fetch_mode & 1u) || (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE);
+    return sc.hit_lines();
+}
+
+// Hit lines of a result (`wanted`: the setting of its scan): the block and its arrays follow the hit arrays of the same result — device
+// pointers, the scanner's pinned blocks, or an owned copy. A scan that gathered nothing answers with the count alone.
+void attach_hit_lines(const ScanOutput& so, bool wanted, bool owned, matchy_scan_result_t* out) {
+    if (!wanted) return;
+    if (!out->_internal) out->_internal = new ScanResultInternal();
+    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    in->has_hit_lines = true;
+    matchy_scan_hit_lines_t& h = in->hit_lines;
+    h = matchy_scan_hit_lines_t{};
+    h.n_lines = (uint32_t)so.lines_with_matches;
+    if (!so.has_hit_lines) return;
+    const HitLinesView& v = so.hit_lines;
+    h.text = v.text; h.text_len = v.text_len; h.n_lines = v.n_lines;
+    h.line_off = v.line_off; h.line_no = v.line_no; h.line_of_hit = v.line_of_fin; h.line_of_ip4_hit = v.line_of_c4;
+    if (!owned) return;   // an owned result has no compact records
+    if (v.text_len) in->hl_text_own.assign(v.text, v.text + v.text_len);
+    h.text = in->hl_text_own.empty() ? nullptr : in->hl_text_own.data();
+    const size_t n_hits = v.line_of_fin ? out->n_hits : 0;
+    in->hl_index_own.reserve((size_t)2 * v.n_lines + 1 + n_hits);
+    in->hl_index_own.assign(v.line_off, v.line_off + v.n_lines + 1);
+    if (v.n_lines) in->hl_index_own.insert(in->hl_index_own.end(), v.line_no, v.line_no + v.n_lines);
+    if (n_hits) in->hl_index_own.insert(in->hl_index_own.end(), v.line_of_fin, v.line_of_fin + n_hits);
+    const uint32_t* w = in->hl_index_own.data();
+    h.line_off = w; h.line_no = v.n_lines ? w + v.n_lines + 1 : nullptr; h.line_of_hit = n_hits ? w + 2 * (size_t)v.n_lines + 1 : nullptr;
+    h.line_of_ip4_hit = nullptr;
+}
+
+// The text of hit i of a host-resident result that carries hit lines, and its whole line, inside the block; false when the result has
+// none (the caller then reads the batch).
+struct BlockLine { const uint8_t* hit; const uint8_t* line; uint32_t line_len; };
+bool block_line_of(const ScanResultInternal* in, bool in_hits, size_t i, uint32_t hit_start, BlockLine& bl) {
+    if (!in || !in->has_hit_lines || in->on_device || !in->hit_lines.text || !in->has_lines) return false;
+    const matchy_scan_hit_lines_t& h = in->hit_lines;
+    const uint32_t* of = in_hits ? h.line_of_hit : h.line_of_ip4_hit;
+    const matchy_scan_line_t* ln = in_hits ? in->lines : in->ip4_lines;
+    if (!of || !ln) return false;
+    const uint32_t k = of[i];
+    if (k >= h.n_lines) return false;
+    bl.line = h.text + h.line_off[k];
+    bl.line_len = h.line_off[k + 1] - 1u - h.line_off[k];
+    bl.hit = bl.line + (hit_start - ln[i].line_start);
+    return true;
 }
 
 static_assert(sizeof(SegmentRec) == sizeof(matchy_scan_segment_t) && offsetof(SegmentRec, lines_with_matches) == offsetof(matchy_scan_segment_t, lines_with_matches),
@@ -904,6 +957,20 @@ int32_t matchy_scan_result_lines(const matchy_scan_result_t* r, const matchy_sca
     return MATCHY_SUCCESS;
 }
 
+// hit lines (Scanner::set_hit_lines, hit_lines.hip)
+void matchy_scanner_set_hit_lines(matchy_scanner_t* s, bool on) { if (s) reinterpret_cast<ScannerH*>(s)->sc->set_hit_lines(on); }
+bool matchy_scanner_hit_lines(const matchy_scanner_t* s) { return s && reinterpret_cast<const ScannerH*>(s)->sc->hit_lines(); }
+int32_t matchy_scan_result_hit_lines(const matchy_scan_result_t* r, matchy_scan_hit_lines_t* out) {
+    if (!r || !out) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_hit_lines) { set_error("matchy_scan_result_hit_lines: the result was produced with hit lines off"); return MATCHY_ERROR_INVALID_PARAM; }
+    *out = in->hit_lines;
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_hit_lines_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->hit_lines_timing(out);
+}
+
 // segmented scans (Scanner::set_segments, segments.hip)
 int32_t matchy_scanner_set_segments(matchy_scanner_t* s, const uint32_t* starts, size_t n) {
     if (!s) return MATCHY_ERROR_INVALID_PARAM;
@@ -979,6 +1046,21 @@ int32_t matchy_scanner_scan(matchy_scanner_t* s, const uint8_t* data, size_t len
             in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
         }
         attach_segments(*h->sc, so, false, true, out);
+        if (h->sc->hit_lines()) {   // scan_host merged the pieces' blocks into vectors of its own: the result takes them
+            auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+            in->has_hit_lines = true;
+            in->hl_text_own.swap(so.hl_text_own);
+            in->hl_index_own = std::move(so.hl_off_own);
+            if (in->hl_index_own.empty()) in->hl_index_own.push_back(0);
+            const size_t n_lines = so.hl_no_own.size(), n_of = so.hl_of_own.size();
+            in->hl_index_own.insert(in->hl_index_own.end(), so.hl_no_own.begin(), so.hl_no_own.end());
+            in->hl_index_own.insert(in->hl_index_own.end(), so.hl_of_own.begin(), so.hl_of_own.end());
+            const uint32_t* w = in->hl_index_own.data();
+            matchy_scan_hit_lines_t& hl = in->hit_lines;
+            hl = matchy_scan_hit_lines_t{};
+            hl.text = in->hl_text_own.empty() ? nullptr : in->hl_text_own.data(); hl.text_len = in->hl_text_own.size(); hl.n_lines = (uint32_t)n_lines;
+            hl.line_off = w; hl.line_no = n_lines ? w + n_lines + 1 : nullptr; hl.line_of_hit = n_of ? w + 2 * n_lines + 1 : nullptr;
+        }
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -995,17 +1077,18 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
         ScanRequest rq;
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
-        rq.lines = h->sc->line_context();
+        const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(len, st);
         h->sc->scan_device(rq, st);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
         attach_lines(*h->sc, so, false, sorted, out);
         attach_segments(*h->sc, so, false, sorted, out);
+        attach_hit_lines(so, hit_lines, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1023,7 +1106,8 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: several batches in flight (ScanRequest::fork)
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode); rq.lines = h->sc->line_context();
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
+        h->pending_hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(len, reinterpret_cast<hipStream_t>(stream));
         h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
@@ -1040,15 +1124,17 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
     try {
         const uint32_t fetch_mode = h->pending_mode;
         const bool sorted = (fetch_mode & 2) != 0;
+        const bool hit_lines = h->pending_hit_lines;
         hipStream_t st = reinterpret_cast<hipStream_t>(h->pending_stream);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, h->pending_len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
         attach_lines(*h->sc, so, false, sorted, out);
         attach_segments(*h->sc, so, false, sorted, out);
+        attach_hit_lines(so, hit_lines, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1073,7 +1159,8 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
         rq.ptr = b.text; rq.len = b.len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode); rq.lines = h->sc->line_context();
+        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
+        const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(b.len, b.stream);
         h->sc->scan_device(rq, b.stream);
         h->sc->gz_queue_results(want_text);
@@ -1090,6 +1177,7 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
         out->lines = so.lines - std::min<uint64_t>(so.lines, g.not_input_nl);
         attach_lines(*h->sc, so, device, sorted, out);
         attach_segments(*h->sc, so, device, sorted, out);
+        attach_hit_lines(so, hit_lines, !device && sorted, out);
         if (!out->_internal) out->_internal = new ScanResultInternal();
         auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
         in->has_gz = true;
@@ -1127,13 +1215,17 @@ bool matchy_scan_result_on_device(const matchy_scan_result_t* r) {
 
 char* matchy_scan_hit_to_json(const matchy_scanner_t* s, const matchy_scan_result_t* r, size_t i, const uint8_t* text, const char* source) {
     // i counts through hits, then through the compact IPv4 records of a MATCHY_SCAN_FETCH_COMPACT result
-    if (!s || !r || !text || i >= r->n_hits + r->n_ip4_hits) return nullptr;
+    if (!s || !r || i >= r->n_hits + r->n_ip4_hits) return nullptr;
     if (i < r->n_hits ? !r->hits : !r->ip4_hits) return nullptr;
     if (matchy_scan_result_on_device(r)) { set_error("matchy_scan_hit_to_json: the records of this result are in device memory (MATCHY_SCAN_FETCH_DEVICE)"); return nullptr; }
     const DbImage& img = reinterpret_cast<const ScannerH*>(s)->sc->image();
     const matchy_scan_hit_t h = i < r->n_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - r->n_hits]);
     const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
-    std::string matched((const char*)text + h.start, hlen), o = "{";
+    // a result with hit lines carries the text of its hits itself; any other needs the batch
+    BlockLine bl{};
+    const bool from_block = block_line_of(reinterpret_cast<const ScanResultInternal*>(r->_internal), i < r->n_hits, i < r->n_hits ? i : i - r->n_hits, h.start, bl);
+    if (!from_block && !text) return nullptr;
+    std::string matched(from_block ? (const char*)bl.hit : (const char*)text + h.start, hlen), o = "{";
     if (h.kind == 2) {
         IpAddr ip;
         std::string cidr;
@@ -1178,7 +1270,11 @@ char* matchy_scan_hit_to_json(const matchy_scanner_t* s, const matchy_scan_resul
 // and with lines its number counts inside its segment: line_bases[s] + (line - segments[s].line_base) + 1
 static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, bool with_lines, uint64_t line_base,
                                 bool with_input_line, char** out, size_t* out_len, const char* const* sources = nullptr, const uint64_t* line_bases = nullptr) {
-    if (!s || !r || !out || !out_len || (!text && (r->n_hits || r->n_ip4_hits))) return MATCHY_ERROR_INVALID_PARAM;
+    if (!s || !r || !out || !out_len) return MATCHY_ERROR_INVALID_PARAM;
+    // a host-resident result with hit lines renders from its block (`text` may be NULL); any other needs the batch
+    const ScanResultInternal* internal = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    const bool from_block = internal && internal->has_hit_lines && !internal->on_device && internal->has_lines && (internal->hit_lines.text || !internal->hit_lines.n_lines);
+    if (!from_block && !text && (r->n_hits || r->n_ip4_hits)) return MATCHY_ERROR_INVALID_PARAM;
     const uint32_t* seg_of_hit = nullptr;
     const uint32_t* seg_of_ip4 = nullptr;
     const matchy_scan_segment_t* segs = nullptr;
@@ -1249,7 +1345,10 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
             const bool in_hits = r->hits && i < r->n_hits;
             const matchy_scan_hit_t h = in_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - (r->hits ? r->n_hits : 0)]);
             const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
-            const char* mt = (const char*)text + h.start;
+            BlockLine bl{};
+            if (from_block && !block_line_of(internal, in_hits, in_hits ? i : i - (r->hits ? r->n_hits : 0), h.start, bl))
+                throw std::out_of_range("matchy_scan_result_to_ndjson: a record has no line in the block of hit lines");
+            const char* mt = from_block ? (const char*)bl.hit : (const char*)text + h.start;
             const uint32_t seg = !sources ? 0u : in_hits ? seg_of_hit[i] : seg_of_ip4[i - (r->hits ? r->n_hits : 0)];
             if (sources && seg >= n_segs) throw std::out_of_range("matchy_scan_result_to_ndjson_segments: a segment index lies outside the table");
             auto append_line_keys = [&] {
@@ -1258,7 +1357,8 @@ static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t*
                 if (with_input_line) {
                     o += "\"input_line\":";
                     raw_line.clear();
-                    utf8_lossy_append(text + ln.line_start, ln.line_end - ln.line_start, raw_line);
+                    if (from_block) utf8_lossy_append(bl.line, bl.line_len, raw_line);
+                    else utf8_lossy_append(text + ln.line_start, ln.line_end - ln.line_start, raw_line);
                     json_escape(raw_line, o);
                     o.push_back(',');
                 }

@@ -33,6 +33,12 @@ struct ScanResultInternal {
     std::vector<uint32_t> segment_of_own;
     const uint32_t* segment_of_hit = nullptr;
     const uint32_t* segment_of_ip4_hit = nullptr;
+    // hit lines (matchy_scan_result_hit_lines): the block and its arrays point into the owned vectors, at the scanner's pinned blocks
+    // (borrowed results) or into device memory (on_device), like the hit arrays of the same result; all NULL for a counts-only fetch
+    bool has_hit_lines = false;
+    matchy_scan_hit_lines_t hit_lines{};
+    std::vector<uint8_t> hl_text_own;
+    std::vector<uint32_t> hl_index_own;   // line_off, line_no, line_of_hit end to end
     // gz scan (matchy_scan_result_gz): the statuses are always owned; the text is the scanner's pinned block, or owned (gz_text_own)
     // where the hit arrays are
     bool has_gz = false;

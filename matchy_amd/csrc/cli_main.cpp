@@ -67,6 +67,8 @@ int usage() {
             "                                0 = all; counted on the GPU; with --format summary nothing else is printed; not with --follow)\n"
             "               [--pack-inputs]   (consecutive small files share a batch and are told apart on the GPU; same output; not with --follow)\n"
             "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
+            "               [--gather-lines]   (the lines with a match are gathered on the GPU and records are rendered from them: with --gz-on-gpu no inflated\n"
+            "                                   text crosses the bus; same output; gains nothing where nearly every line matches)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -358,6 +360,9 @@ struct MatchPipeline {
     // such batches are rendered by the ordered printer (line_base: '\n' bytes of the input's earlier batches; batches end at newlines),
     // not by the batch hook.
     bool line_ctx = false, input_line = false;
+    // --gather-lines: the scanners run with hit lines. Every result carries the lines of its matches, the renderers read those (the
+    // text of a gz pack stays on the device), and "Lines with matches" is the device's count as with line context.
+    bool gather = false;
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
 
     // every input a batch carries: its own, or the files of a pack
@@ -375,7 +380,7 @@ struct MatchPipeline {
         if (!hb->gz.empty()) {   // the text comes back only where something is rendered from it
             std::vector<matchy_gz_member_t> table;
             for (const GzFile& g : hb->gz) table.push_back(matchy_gz_member_t{g.offset, g.len, 0});
-            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json, hb);
+            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather, hb);
             if (rc != MATCHY_SUCCESS) { hb->verdict->set(nullptr, 0); delete hb; return seq; }   // every member goes the old way
         }
         else if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
@@ -429,28 +434,28 @@ struct MatchPipeline {
             // a pack: the newlines the packer appended are not the inputs'
             t.lines += r.lines - b.appended; t.candidates += r.candidates; t.bytes += len - b.appended; t.matches += r.n_hits;
         }
-        if (line_ctx && segmented) {   // per segment, from the table the GPU filled
+        if ((line_ctx || gather) && segmented) {   // per segment, from the table the GPU filled
             const matchy_scan_segment_t* segs = nullptr;
             size_t n_segs = 0;
             if (matchy_scan_result_segments(&r, nullptr, nullptr, &segs, &n_segs) == MATCHY_SUCCESS) for (size_t k = 0; k < n_segs; ++k) t.lines_with_matches += segs[k].lines_with_matches;
             else { fprintf(stderr, "[ERROR] no segments in the scan result of a pack: %s\n", matchy_amd_last_error()); d.ok = false; }
-            return;
-        }
-        if (line_ctx) {
+            if (line_ctx || !d.ok) return;
+        } else if (line_ctx || gather) {
             uint64_t lwm = 0;
             if (matchy_scan_result_lines(&r, nullptr, nullptr, &lwm) == MATCHY_SUCCESS) t.lines_with_matches += lwm;
             else { fprintf(stderr, "[ERROR] no line context in a scan result: %s\n", matchy_amd_last_error()); d.ok = false; }
-            return;   // the records: render_numbered, in sequence order
+            if (line_ctx || !d.ok) return;   // the records of a scan with line numbers: render_numbered, in sequence order
+        } else {
+            // lines with matches: hits come sorted by offset; a new line starts when a '\n' lies between two hit starts (and a '\n' lies
+            // between any two segments of a pack)
+            size_t prev = (size_t)-1;
+            for (size_t i = 0; i < r.n_hits; ++i) {
+                const size_t s = (size_t)r.hits[i].start;
+                if (prev == (size_t)-1 || memchr(data + prev, '\n', s - prev)) ++t.lines_with_matches;
+                prev = s;
+            }
         }
-        // lines with matches: hits come sorted by offset; a new line starts when a '\n' lies between two hit starts (and a '\n' lies
-        // between any two segments of a pack)
         const std::string& source = sources[input];
-        size_t prev = (size_t)-1;
-        for (size_t i = 0; i < r.n_hits; ++i) {
-            const size_t s = (size_t)r.hits[i].start;
-            if (prev == (size_t)-1 || memchr(data + prev, '\n', s - prev)) ++t.lines_with_matches;
-            prev = s;
-        }
         if (json && r.n_hits) {   // every match of the batch in one call (the scanner caches the rendered data payloads)
             char* text = nullptr;
             size_t n = 0;
@@ -766,7 +771,7 @@ struct GzPacker {
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -797,6 +802,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--input-line") input_line = true;
         else if (a == "--pack-inputs") pack = true;
         else if (a == "--gz-on-gpu") gz_gpu = true;
+        else if (a == "--gather-lines") gather_lines = true;
         else if (a == "--tally") tally = true;
         else if (a.compare(0, 8, "--tally=") == 0) {
             const std::string n = a.substr(8);
@@ -895,6 +901,8 @@ int cmd_match(int argc, char** argv) {
     pl.line_ctx = line_numbers || input_line || (gz_gpu && format != "json");
     pl.input_line = input_line;
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
+    pl.gather = gather_lines;
+    if (pl.gather) matchy_multi_scanner_set_hit_lines(ms, true);
     if (tally) matchy_multi_scanner_set_tally(ms, true);
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
     std::vector<std::string> paths;
@@ -979,7 +987,7 @@ int cmd_match(int argc, char** argv) {
     if (follow) {
         matchy_scanner_t* fsc = matchy_scanner_create(db, mask, devs[0]);
         if (!fsc) fprintf(stderr, "Error: Failed to create the GPU scanner on device %d: %s\n", devs[0], matchy_amd_last_error());
-        else { matchy_scanner_set_line_context(fsc, pl.line_ctx); follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
+        else { matchy_scanner_set_line_context(fsc, pl.line_ctx); matchy_scanner_set_hit_lines(fsc, pl.gather); follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
     }
     size_t failed = 0;
     for (char f : input_failed) failed += f != 0;

@@ -1326,6 +1326,13 @@ void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool 
         lines_->resolve(batch, to_host, n_cu_, profile_, stream);
         out.has_lines = true;
     }
+    // hit lines: the lines of the records, packed where the batch lies, behind the line records they are read from
+    out.has_hit_lines = false; out.hit_lines = HitLinesView{};
+    if (out.has_lines && last_.hit_lines) {
+        if (!hit_lines_) hit_lines_ = std::make_unique<HitLines>();
+        hit_lines_->resolve(batch, lines_->device_lines(), lines_->device_c4_lines(), c.lines, to_host, n_cu_, profile_, stream);
+        out.has_hit_lines = true;
+    }
     // hit tally: the records of the batch are counted where they lie, once per fetch — behind the regrow loop and the spill pass. With
     // set_profile or MATCHY_AMD_TRACE the pass times its kernels (one more host wait between them)
     if (tally_on_ && last_.lookup && !single_) {
@@ -1361,6 +1368,12 @@ void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, h
     if (out.has_lines) {
         const LineContext::Result r = lines_->finish();
         out.lines_with_matches = r.lines_with_matches; out.fin_lines = r.fin_lines; out.c4_lines = r.c4_lines;
+    }
+    if (out.has_hit_lines) {
+        out.hit_lines = hit_lines_->finish();   // a second wait: the demand of the block is known only now
+        if (getenv("MATCHY_AMD_TRACE") && !single_)
+            fprintf(stderr, "[matchy_amd] hit lines: %u lines, block of %llu bytes, %llu bytes copied to the host\n", out.hit_lines.n_lines,
+                    (unsigned long long)out.hit_lines.text_len, (unsigned long long)hit_lines_->last_copied_bytes());
     }
     if (out.has_segments) {
         const SegmentPass::Result r = segments_->finish();
@@ -1541,7 +1554,8 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             if (tail) MXY_HIP(hipMemcpyAsync(staging_.p + head + reg_len, reg_lo + reg_len, tail, hipMemcpyHostToDevice, host_stream_));
         } else if (n) MXY_HIP(hipMemcpyAsync(staging_.p, src, n, hipMemcpyHostToDevice, host_stream_));
         ScanRequest rq;
-        rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = line_ctx_ && lookup;
+        rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = (line_ctx_ || hit_lines_on_) && lookup;
+        rq.hit_lines = hit_lines_on_ && lookup && fin;
         size_t seg_first = 0;
         if (!seg_all.empty()) {
             // the last segment that starts at or in front of the piece .. the last that starts inside it (the last piece: the last of all)
@@ -1566,6 +1580,17 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             out.has_lines = true; out.lines_with_matches += part.lines_with_matches;
             if (fin_lines && part.n_fin) append_shifted_lines(part.fin_lines, part.n_fin, (uint32_t)pos, (uint32_t)out.lines, *fin_lines);
         }
+        // a piece ends at a line end: its block goes behind the blocks of the pieces in front of it
+        if (part.has_hit_lines) {
+            out.has_hit_lines = true;
+            const HitLinesView& v = part.hit_lines;
+            const uint32_t text_base = (uint32_t)out.hl_text_own.size(), k_base = (uint32_t)out.hl_no_own.size();
+            if (out.hl_off_own.empty()) out.hl_off_own.push_back(0);
+            for (uint32_t k = 0; k < v.n_lines; ++k) { out.hl_off_own.push_back(text_base + v.line_off[k + 1]); out.hl_no_own.push_back((uint32_t)out.lines + v.line_no[k]); }
+            for (size_t i = 0; i < part.n_fin; ++i) out.hl_of_own.push_back(k_base + v.line_of_fin[i]);
+            if ((uint64_t)text_base + v.text_len > 0xFFFFFFFFull) throw HipError{"scan_host: the hit lines of the pieces exceed 4 GiB (32-bit offsets)"};
+            if (v.text_len) out.hl_text_own.insert(out.hl_text_own.end(), v.text, v.text + v.text_len);
+        }
         if (part.has_segments) {
             out.has_segments = true;
             for (size_t k = 0; k < part.n_segments; ++k) {
@@ -1583,6 +1608,13 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         pos += n;
     } while (pos < len);
     out.cands.swap(all_cands);
+    if (out.has_hit_lines) {
+        HitLinesView& v = out.hit_lines;
+        v.text = out.hl_text_own.empty() ? nullptr : out.hl_text_own.data(); v.text_len = out.hl_text_own.size();
+        v.n_lines = (uint32_t)out.hl_no_own.size();
+        v.line_off = out.hl_off_own.data(); v.line_no = out.hl_no_own.empty() ? nullptr : out.hl_no_own.data();
+        v.line_of_fin = out.hl_of_own.empty() ? nullptr : out.hl_of_own.data(); v.line_of_c4 = nullptr;
+    }
     if (out.has_segments) {
         out.segments = out.seg_own.data(); out.n_segments = out.seg_own.size();
         out.seg_of_fin = out.seg_of_own.empty() ? nullptr : out.seg_of_own.data();

@@ -9,6 +9,7 @@
 
 #include "db_image.h"
 #include "hip_owners.h"
+#include "hit_lines.h"
 #include "inflate.h"
 #include "line_index.h"
 #include "result_layout.h"
@@ -111,6 +112,12 @@ struct ScanOutput {
     const uint32_t* seg_of_c4 = nullptr;
     std::vector<SegmentRec> seg_own;
     std::vector<uint32_t> seg_of_own;
+    // hit lines (ScanRequest::hit_lines): the block of the distinct lines with a hit and its index arrays (hit_lines.h). A scan_device
+    // fetch BORROWS them like fin (device pointers unless HITS_FINAL); scan_host owns them in hl_*_own, merged over its pieces
+    bool has_hit_lines = false;
+    HitLinesView hit_lines;
+    std::vector<uint8_t> hl_text_own;
+    std::vector<uint32_t> hl_off_own, hl_no_own, hl_of_own;
 };
 
 // Process-wide registry of the host ranges this library pinned (hipHostRegister): the caller's (matchy_amd_host_register, kept until
@@ -159,6 +166,7 @@ struct ScanRequest {
     int slices = 0;            // with fork: cut the batch into that many slices (see Scanner::MAX_SLICES); 0 = the default (one slice)
     bool compact = false;      // IPv4 results leave as 8-byte records (ScanOutput::c4, scan_types.h c4_pack) when compact_possible()
     bool lines = false;        // line context: fetch() resolves every final record to its line (line_index.hip); needs `lookup`
+    bool hit_lines = false;    // fetch() packs the distinct lines with a hit into one block (hit_lines.hip); needs `lines`
 };
 
 // Moves the line records of a piece that starts `base` bytes and `line_base` lines into the whole (append_shifted for the line array).
@@ -201,6 +209,12 @@ public:
     const LineRec* device_c4_lines() const { return lines_ ? lines_->device_c4_lines() : nullptr; }
     // with set_profile: milliseconds of the streaming count kernel, of the prefix sum, and of resolve + distinct set of the last fetch
     void line_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (lines_) lines_->timing(out_ms); }
+    // Hit lines (hit_lines.hip): scans launched through scan_host gather them when set, and resolve lines for it (scan_device callers
+    // pass ScanRequest::hit_lines together with ::lines). Never set, nothing of it is allocated, launched or copied.
+    void set_hit_lines(bool on) { hit_lines_on_ = on; }
+    bool hit_lines() const { return hit_lines_on_; }
+    // with set_profile: milliseconds of mark + rank + lengths + offsets, of the copy kernel, and of the block's device-to-host copy
+    void hit_lines_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (hit_lines_) hit_lines_->timing(out_ms); }
     // Segmented scans (segments.hip): `starts` (copied) describes the buffer of the NEXT lookup scan as n segments — starts[0] == 0,
     // non-decreasing, every start <= the scan's length, every non-empty segment in front of the last ends in '\n'. n == 0 or null
     // clears a pending table. arm_segments(len) is what the entries of a lookup scan call before scan_device: it consumes the pending
@@ -346,9 +360,12 @@ private:
     DevBuf<FinalHit> final_sorted_;
     DevBuf<ScanCounters> counters_;            // MAX_SLICES entries
     // the passes behind the scan, each created at first use: line context (line_index.h; line_ctx_ is what scan_host asks for),
+    // hit lines (hit_lines.h),
     // segmented scans (segments.h), gz scans (inflate.h), distinct texts (distinct.h), hit tally (tally.h)
     bool line_ctx_ = false;
     std::unique_ptr<LineContext> lines_;       // created by the first fetch of a scan with line context
+    bool hit_lines_on_ = false;
+    std::unique_ptr<HitLines> hit_lines_;      // created by the first fetch of a scan with hit lines
     std::unique_ptr<SegmentPass> segments_;    // created by the first set_segments with a table
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
     bool unique_ = false;

@@ -47,6 +47,7 @@ struct MultiScanner {
     size_t max_inflight = 4;
     bool closing = false;
     bool line_ctx = false;   // matchy_multi_scanner_set_line_context: every worker sets its scanner to it before a scan
+    bool hit_lines = false;  // matchy_multi_scanner_set_hit_lines: likewise
     bool tally = false, tally_ever = false;   // matchy_multi_scanner_set_tally: likewise
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
@@ -66,7 +67,7 @@ struct MultiScanner {
         }
         for (;;) {
             MultiJob j;
-            bool want_lines = false, want_tally = false, touch_tally = false;
+            bool want_lines = false, want_hit_lines = false, want_tally = false, touch_tally = false;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return closing || !q.empty(); });
@@ -78,7 +79,7 @@ struct MultiScanner {
                 j = std::move(*it);
                 q.erase(it);
                 cv_space.notify_one();
-                want_lines = line_ctx;
+                want_lines = line_ctx; want_hit_lines = hit_lines;
                 want_tally = tally; touch_tally = tally_ever;
             }
             MultiDone d;
@@ -88,6 +89,7 @@ struct MultiScanner {
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
             else if (!j.gz.empty()) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
                 matchy_scanner_set_line_context(scanners[w], want_lines);
+                matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
                 d.status = matchy_scanner_scan_gz(scanners[w], j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res);
                 d.data = nullptr; d.len = 0;
@@ -96,6 +98,7 @@ struct MultiScanner {
             }
             else if (j.len || !j.starts.empty()) {   // an empty batch with a table is scanned too: its result carries the table
                 matchy_scanner_set_line_context(scanners[w], want_lines);
+                matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
                 if (!j.starts.empty()) d.status = matchy_scanner_set_segments(scanners[w], j.starts.data(), j.starts.size());
                 if (d.status == MATCHY_SUCCESS) d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
@@ -170,6 +173,12 @@ void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t* h, bool enabl
     MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
     std::lock_guard<std::mutex> lk(ms->mu);
     ms->line_ctx = enabled;
+}
+void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t* h, bool enabled) {
+    if (!h) return;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    ms->hit_lines = enabled;
 }
 // Hit tally: the workers switch their scanners' tallies before a scan, like line context; the read-out and the reset touch the scanners
 // themselves and therefore need the workers idle (nothing pending).
