@@ -371,6 +371,40 @@ int32_t matchy_scan_result_hit_lines(const matchy_scan_result_t *result, matchy_
 /* With matchy_scanner_set_profile: milliseconds of the index steps (mark, rank, lengths, offsets), of the copy kernel, and of the
  * block's device-to-host copy (0 where nothing is copied) of the last scan. */
 void matchy_scanner_get_hit_lines_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* ---- Rendered records: the records of a scan leave the device as NDJSON text.
+ * The text is the one matchy_scan_result_to_ndjson / _lines / _segments give for the same result, byte for byte: one line per record, in
+ * the order of `hits`, then `ip4_hits`. The payload JSON of the database's entries is made by the host once per data offset and kept in
+ * device memory across scans; everything else of a record is written by the GPU (csrc/render.hip). */
+#define MATCHY_RENDER_LINE_NUMBERS 1u   /* "line_number": needs line context (matchy_scanner_set_line_context) */
+#define MATCHY_RENDER_INPUT_LINE   2u   /* "input_line" as well (implies LINE_NUMBERS) */
+typedef struct matchy_render_params_t {
+  uint32_t flags;
+  const char *source;            /* one source (NULL = "-"), or */
+  const char *const *sources;    /* one per segment of the scan it arms (then `source` is ignored) */
+  size_t n_sources;
+  uint64_t line_base;            /* lines in front of the buffer; or, with sources, */
+  const uint64_t *line_bases;    /* one per segment (NULL = zeros) */
+} matchy_render_params_t;
+/* Arms the scanner's NEXT scan through matchy_scanner_scan, _scan_device, _submit_device or _scan_gz (the parameters are copied at the
+ * call; NULL disarms), and that scan consumes them whether it succeeds or not. A scan armed with parameters that do not fit it — line flags without
+ * line context, `sources` for a scan without segments, n_sources other than the segment count — fails with MATCHY_ERROR_INVALID_PARAM
+ * and a message; the scanner stays usable. matchy_scanner_scan renders piece by piece and hands out the blocks end to end. */
+int32_t matchy_scanner_set_render(matchy_scanner_t *scanner, const matchy_render_params_t *params);
+#define MATCHY_RENDER_OK 0
+#define MATCHY_RENDER_TOO_LARGE 1   /* more text than MATCHY_AMD_RENDER_MAX_BYTES (default 1 GiB), more distinct payloads in one batch than
+                                       MATCHY_AMD_RENDER_PAYLOADS (default 2^20), or a "data" array above 16 MiB: nothing is handed out */
+/* The block of a result whose scan was armed. Ownership and residency follow the hit arrays of the result: borrowed until the scanner's
+ * next scan, owned by the result for MATCHY_SCAN_FETCH_SORTED and matchy_scanner_scan, a device pointer with nothing copied for MATCHY_SCAN_FETCH_DEVICE; a
+ * MATCHY_SCAN_FETCH_COUNTS fetch renders nothing (text NULL, len 0). MATCHY_ERROR_INVALID_PARAM for a result whose scan was not armed.
+ * Any out pointer may be NULL. */
+int32_t matchy_scan_result_ndjson(const matchy_scan_result_t *result, const char **text, uint64_t *len, int32_t *status);
+/* With matchy_scanner_set_profile: milliseconds of measure + offsets, of the write step, and of the block's device-to-host copy (0 where
+ * nothing is copied) of the last scan that rendered. */
+void matchy_scanner_get_render_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* Of the last scan that rendered: repeats of the pass (0 in the steady state), payload-table misses over all its rounds, payloads the
+ * host rendered and uploaded, bytes of the block copied to the host, growths of the payload table's slot array and of its device pool
+ * (they start at MATCHY_AMD_RENDER_PAYLOADS_SLOTS = 64 slots and MATCHY_AMD_RENDER_PAYLOADS_POOL_BYTES = 64 KiB; the variables are for tests). */
+void matchy_scanner_get_render_counters(const matchy_scanner_t *scanner, uint64_t out[6]);
 /* ---- Segmented scans: many small inputs as one batch.
  * The caller describes a buffer as a sequence of segments (the files of a pack): the scan runs once, as for any buffer, and a pass
  * behind it attributes every hit record to its segment on the GPU and counts per segment. '\n' is a boundary for every extractor, so
@@ -578,6 +612,12 @@ void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t *ms, bool enab
  * matchy_scan_result_hit_lines (and _lines), owned by the result, and render with text == NULL — a gz batch submitted without want_text
  * included, whose `data` is NULL. The merged results of matchy_multi_scanner_scan / _scan_file do not carry the block. */
 void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t *ms, bool enabled);
+/* Rendered records (matchy_scanner_set_render) on the multi-device scanner: arms the NEXT batch submitted (matchy_multi_scanner_submit / _submit_near / _submit_segments / _submit_gz;
+ * copied at the call, NULL disarms). The worker that takes the batch arms its scanner; the batch's result owns the block. An armed gz
+ * batch submitted without want_text is scanned with line context whatever matchy_multi_scanner_set_line_context says: its result carries
+ * the lines with matches per segment, which nobody could count from a text that does not come back. A batch whose
+ * parameters do not fit it comes back with MATCHY_ERROR_INVALID_PARAM in its status, like any batch that failed. */
+int32_t matchy_multi_scanner_set_render(matchy_multi_scanner_t *scanner, const matchy_render_params_t *params);
 
 /* ---- Hit tally (opt-in, off by default: with it never enabled a scanner allocates, launches and copies nothing more and every output
  * stays as it is). How often every distinct matched value hit: a table in device memory, owned by the scanner, keyed by (item type,

@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
     "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
     "matchy_multi_scanner_set_hit_lines",
+    "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
+    "matchy_multi_scanner_set_render",
 ]
 
 # MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
@@ -74,6 +76,14 @@ LINE_SCAN_CHUNK = 2048
 # bytes of the block of hit lines one wave of the copy kernel owns, and entries per workgroup of its prefix sums (csrc/hit_lines.h)
 HIT_LINES_SLICE = 4096
 HIT_LINES_SCAN_CHUNK = 2048
+
+
+RENDER_LINE_NUMBERS, RENDER_INPUT_LINE = 1, 2   # matchy_render_params_t.flags
+RENDER_OK, RENDER_TOO_LARGE = 0, 1
+
+
+class RenderTooLarge(RuntimeError):
+    """ScanResult.rendered_ndjson: the pass ended with MATCHY_RENDER_TOO_LARGE"""
 
 
 class _Result(C.Structure):
@@ -131,6 +141,12 @@ class _ScanHitLines(C.Structure):
     # matchy_scan_hit_lines_t
     _fields_ = [("text", C.c_void_p), ("text_len", C.c_uint64), ("n_lines", C.c_uint32), ("line_off", C.c_void_p), ("line_no", C.c_void_p),
                 ("line_of_hit", C.c_void_p), ("line_of_ip4_hit", C.c_void_p)]
+
+
+class _RenderParams(C.Structure):
+    # matchy_render_params_t
+    _fields_ = [("flags", C.c_uint32), ("source", C.c_char_p), ("sources", C.POINTER(C.c_char_p)), ("n_sources", C.c_size_t),
+                ("line_base", C.c_uint64), ("line_bases", C.POINTER(C.c_uint64))]
 
 
 class _ScanLine(C.Structure):
@@ -280,6 +296,11 @@ def lib():
         "matchy_scan_result_hit_lines": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(_ScanHitLines)]),
         "matchy_scanner_get_hit_lines_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_multi_scanner_set_hit_lines": (None, [vp, C.c_bool]),
+        "matchy_scanner_set_render": (C.c_int32, [vp, C.POINTER(_RenderParams)]),
+        "matchy_scan_result_ndjson": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+        "matchy_scanner_get_render_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_get_render_counters": (None, [vp, C.POINTER(C.c_uint64)]),
+        "matchy_multi_scanner_set_render": (C.c_int32, [vp, C.POINTER(_RenderParams)]),
         "matchy_scanner_set_segments": (C.c_int32, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "matchy_scan_result_segments": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scan_result_to_ndjson_segments": (C.c_int32, [vp, C.POINTER(_ScanResult), cp, C.POINTER(cp), C.POINTER(C.c_uint64), C.c_bool,
@@ -709,6 +730,21 @@ class ScanResult:
                    line_of_hit=arr(h.line_of_hit, n_hits), line_of_ip4_hit=arr(h.line_of_ip4_hit, n_ip4))
         return out
 
+    def rendered_ndjson(self):
+        """the NDJSON block of a result whose scan was armed with Scanner.set_render (matchy_scan_result_ndjson): bytes, or for a
+        device result (fetch_mode 4) the tuple (device address, length). Raises RenderTooLarge when the pass ended with
+        MATCHY_RENDER_TOO_LARGE and ValueError for a result whose scan was not armed."""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        text, n, status = C.c_void_p(), C.c_uint64(), C.c_int32()
+        if lib().matchy_scan_result_ndjson(C.byref(self._raw), C.byref(text), C.byref(n), C.byref(status)) != 0:
+            raise ValueError("matchy_scan_result_ndjson failed: " + last_error())
+        if status.value != RENDER_OK:
+            raise RenderTooLarge("the rendered records exceed a limit of the renderer (MATCHY_RENDER_TOO_LARGE)")
+        if self.on_device:
+            return (text.value or 0, int(n.value))
+        return C.string_at(text.value, n.value) if text.value else b""
+
     def _line_arrays(self):
         """(lines pointer, ip4_lines pointer, lines_with_matches) of a result scanned with line context, else None"""
         if self._raw is None:
@@ -827,6 +863,22 @@ class TallyList(list):
     matches = 0
 
 
+def _render_params(flags, source, sources, line_base, line_bases):
+    """matchy_render_params_t of Scanner.set_render / MultiScanner.set_render (None: disarm); the arrays stay alive with the struct"""
+    if flags is None:
+        return None
+    p = _RenderParams(flags=flags, line_base=line_base)
+    if sources is not None:
+        enc = [None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in sources]
+        p.sources = (C.c_char_p * max(len(enc), 1))(*enc)
+        p.n_sources = len(enc)
+        if line_bases is not None:
+            p.line_bases = (C.c_uint64 * max(len(line_bases), 1))(*line_bases)
+    elif source is not None:
+        p.source = source if isinstance(source, bytes) else source.encode()
+    return p
+
+
 class Scanner:
     """Bulk scan session (the device-side Worker). One per thread / stream."""
 
@@ -890,6 +942,27 @@ class Scanner:
 
     def hit_lines_enabled(self) -> bool:
         return bool(lib().matchy_scanner_hit_lines(self._h))
+
+    def set_render(self, flags=0, source=None, sources=None, line_base=0, line_bases=None):
+        """arms the NEXT scan / scan_device / submit_device / scan_gz: its result answers rendered_ndjson() with the NDJSON text of its
+        records, written on the GPU (matchy_scanner_set_render). flags: RENDER_LINE_NUMBERS / RENDER_INPUT_LINE (need line context).
+        sources (one str per segment of a segmented scan, with line_bases) or source (one for the buffer, with line_base).
+        flags=None disarms."""
+        p = _render_params(flags, source, sources, line_base, line_bases)
+        rc = lib().matchy_scanner_set_render(self._h, None if p is None else C.byref(p))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_set_render failed ({rc}): " + last_error())
+
+    def render_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_render_timing(self._h, out)
+        return dict(measure=out[0], write=out[1], d2h=out[2])
+
+    def render_counters(self):
+        """of the last scan that rendered: repeats of the pass, payload-table misses, payloads rendered by the host, bytes copied"""
+        out = (C.c_uint64 * 6)()
+        lib().matchy_scanner_get_render_counters(self._h, out)
+        return dict(rounds=int(out[0]), misses=int(out[1]), payloads_added=int(out[2]), copied=int(out[3]), rehashes=int(out[4]), pool_regrows=int(out[5]))
 
     def hit_lines_timing_ms(self):
         out = (C.c_float * 3)()
@@ -1015,6 +1088,14 @@ class MultiScanner:
         """hit lines for every worker's scanner, from the next batch on: batches from next() answer hit_lines() and render without text"""
         lib().matchy_multi_scanner_set_hit_lines(self._h, bool(on))
 
+    def set_render(self, flags=0, source=None, sources=None, line_base=0, line_bases=None):
+        """arms the NEXT batch submitted (submit_ptr / submit_segments_ptr / submit_gz_ptr) like Scanner.set_render: next() then carries
+        "rendered", the NDJSON text of the batch written on the GPU (matchy_multi_scanner_set_render). flags=None disarms."""
+        p = _render_params(flags, source, sources, line_base, line_bases)
+        rc = lib().matchy_multi_scanner_set_render(self._h, None if p is None else C.byref(p))
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_set_render failed ({rc}): " + last_error())
+
     def set_tally(self, on=True):
         """hit tally on every worker's scanner, from the next batch on"""
         rc = lib().matchy_multi_scanner_set_tally(self._h, bool(on))
@@ -1094,6 +1175,8 @@ class MultiScanner:
             out["hit_lines"] = hl
             if want_hits:
                 out["ndjson_lines"] = r.ndjson_lines_text(None, with_input_line=True)
+        if lib().matchy_scan_result_ndjson(C.byref(r._raw), None, None, None) == 0:   # the batch was armed with set_render
+            out["rendered"] = r.rendered_ndjson()
         gz = r.gz_status()
         if gz is not None:   # a gz batch: data / len are the inflated text (NULL without want_text) and its length
             out["gz_status"] = gz

@@ -20,6 +20,7 @@
 #include "host_lookup.h"
 #include "inflate_core.h"
 #include "netaddr.h"
+#include "render_core.h"
 #include "utf8_lossy.h"
 
 #include <deque>
@@ -281,6 +282,21 @@ bool request_lines(const Scanner& sc, uint32_t fetch_mode, ScanRequest& rq) {
     rq.lines = sc.line_context() || sc.hit_lines();
     rq.hit_lines = sc.hit_lines() && ((fetch_mode & 1u) || (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE);
     return sc.hit_lines();
+}
+
+// which fetches render: those that hand records out (on the host or on the device), not a counts-only fetch
+bool fetch_renders(uint32_t fetch_mode) { return (fetch_mode & 1u) || (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE; }
+
+// The rendered block of a result whose scan was armed: it follows the hit arrays of the same result.
+void attach_render(const ScanOutput& so, bool owned, matchy_scan_result_t* out) {
+    if (!so.render.armed) return;
+    if (!out->_internal) out->_internal = new ScanResultInternal();
+    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    in->has_render = true;
+    in->render_status = (int32_t)so.render.status;
+    in->render_len = so.render.len;
+    in->render_text = so.render.text;
+    if (owned && so.render.text) { in->render_own.assign(so.render.text, so.render.text + so.render.len); in->render_text = in->render_own.data(); }
 }
 
 // Hit lines of a result (`wanted`: the setting of its scan): the block and its arrays follow the hit arrays of the same result — device
@@ -1046,6 +1062,7 @@ int32_t matchy_scanner_scan(matchy_scanner_t* s, const uint8_t* data, size_t len
             in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
         }
         attach_segments(*h->sc, so, false, true, out);
+        attach_render(so, true, out);   // scan_host put the pieces' blocks end to end: the result takes a copy
         if (h->sc->hit_lines()) {   // scan_host merged the pieces' blocks into vectors of its own: the result takes them
             auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
             in->has_hit_lines = true;
@@ -1079,16 +1096,18 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
         const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(len, st);
+        h->sc->arm_render(rq, fetch_renders(fetch_mode), st);
         h->sc->scan_device(rq, st);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); attach_render(so, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
         attach_lines(*h->sc, so, false, sorted, out);
         attach_segments(*h->sc, so, false, sorted, out);
         attach_hit_lines(so, hit_lines, sorted, out);
+        attach_render(so, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1109,6 +1128,7 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
         h->pending_hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(len, reinterpret_cast<hipStream_t>(stream));
+        h->sc->arm_render(rq, fetch_renders(fetch_mode), reinterpret_cast<hipStream_t>(stream));
         h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
         return MATCHY_SUCCESS;
@@ -1128,13 +1148,14 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
         hipStream_t st = reinterpret_cast<hipStream_t>(h->pending_stream);
         ScanOutput so;
         h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); return MATCHY_SUCCESS; }
+        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); attach_render(so, false, out); return MATCHY_SUCCESS; }
         fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, h->pending_len, !sorted, sorted, out);
         out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
         if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
         attach_lines(*h->sc, so, false, sorted, out);
         attach_segments(*h->sc, so, false, sorted, out);
         attach_hit_lines(so, hit_lines, sorted, out);
+        attach_render(so, sorted, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1162,6 +1183,7 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
         const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
         h->sc->arm_segments(b.len, b.stream);
+        h->sc->arm_render(rq, fetch_renders(fetch_mode), b.stream);
         h->sc->scan_device(rq, b.stream);
         h->sc->gz_queue_results(want_text);
         ScanOutput so;
@@ -1178,6 +1200,7 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
         attach_lines(*h->sc, so, device, sorted, out);
         attach_segments(*h->sc, so, device, sorted, out);
         attach_hit_lines(so, hit_lines, !device && sorted, out);
+        attach_render(so, !device && sorted, out);
         if (!out->_internal) out->_internal = new ScanResultInternal();
         auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
         in->has_gz = true;
@@ -1201,6 +1224,46 @@ int32_t matchy_scan_result_gz(const matchy_scan_result_t* r, const int32_t** sta
 }
 void matchy_scanner_get_gz_timing(const matchy_scanner_t* s, float out[3]) {
     if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_timing(out);
+}
+
+// rendered records (Scanner::set_render, render.hip)
+static_assert(MATCHY_RENDER_LINE_NUMBERS == render::FLAG_LINE_NUMBERS && MATCHY_RENDER_INPUT_LINE == render::FLAG_INPUT_LINE, "the kernels read the flags directly");
+static_assert(MATCHY_RENDER_OK == RENDER_OK && MATCHY_RENDER_TOO_LARGE == RENDER_TOO_LARGE, "the kernels write MATCHY_RENDER_* values directly");
+static_assert(MATCHY_SCAN_IP4_DATA_BITS == 22, "render.hip expands compact records with this layout");
+int32_t matchy_scanner_set_render(matchy_scanner_t* s, const matchy_render_params_t* p) {
+    if (!s) return MATCHY_ERROR_INVALID_PARAM;
+    Scanner& sc = *reinterpret_cast<ScannerH*>(s)->sc;
+    if (!p) { sc.set_render(nullptr); return MATCHY_SUCCESS; }
+    if (p->flags & ~(MATCHY_RENDER_LINE_NUMBERS | MATCHY_RENDER_INPUT_LINE)) { set_error("matchy_scanner_set_render: unknown flags"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (p->sources && !p->n_sources) { set_error("matchy_scanner_set_render: sources without n_sources"); return MATCHY_ERROR_INVALID_PARAM; }
+    try {
+        RenderParams rp;
+        rp.flags = p->flags | ((p->flags & MATCHY_RENDER_INPUT_LINE) ? MATCHY_RENDER_LINE_NUMBERS : 0u);
+        auto escaped = [](const char* src) { std::string o; json_escape(src ? src : "-", o); return o; };
+        if (p->sources) {
+            rp.per_segment = true;
+            for (size_t k = 0; k < p->n_sources; ++k) { rp.sources.push_back(escaped(p->sources[k])); rp.line_bases.push_back(p->line_bases ? p->line_bases[k] : 0); }
+        } else { rp.sources.push_back(escaped(p->source)); rp.line_bases.push_back(p->line_base); }
+        sc.set_render(&rp);
+        return MATCHY_SUCCESS;
+    } catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_OUT_OF_MEMORY; }
+}
+int32_t matchy_scan_result_ndjson(const matchy_scan_result_t* r, const char** text, uint64_t* len, int32_t* status) {
+    if (!r) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_render) { set_error("matchy_scan_result_ndjson: the scan of this result was not armed with matchy_scanner_set_render"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (text) *text = reinterpret_cast<const char*>(in->render_text);
+    if (len) *len = in->render_len;
+    if (status) *status = in->render_status;
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_render_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->render_timing(out);
+}
+void matchy_scanner_get_render_counters(const matchy_scanner_t* s, uint64_t out[6]) {
+    if (!s || !out) return;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    if (const NdjsonRender::Events* ev = reinterpret_cast<const ScannerH*>(s)->sc->render_events()) { out[0] = ev->rounds; out[1] = ev->misses; out[2] = ev->payloads_added; out[3] = ev->copied; out[4] = ev->rehashes; out[5] = ev->pool_regrows; }
 }
 
 void matchy_scan_result_free(matchy_scan_result_t* r) {

@@ -39,6 +39,13 @@ struct ScanResultInternal {
     matchy_scan_hit_lines_t hit_lines{};
     std::vector<uint8_t> hl_text_own;
     std::vector<uint32_t> hl_index_own;   // line_off, line_no, line_of_hit end to end
+    // rendered records (matchy_scan_result_ndjson): the block follows the hit arrays of the same result — the scanner's pinned block, an
+    // owned copy (render_own), or device memory (on_device)
+    bool has_render = false;
+    std::vector<uint8_t> render_own;
+    const uint8_t* render_text = nullptr;
+    uint64_t render_len = 0;
+    int32_t render_status = 0;
     // gz scan (matchy_scan_result_gz): the statuses are always owned; the text is the scanner's pinned block, or owned (gz_text_own)
     // where the hit arrays are
     bool has_gz = false;

@@ -69,6 +69,8 @@ int usage() {
             "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
             "               [--gather-lines]   (the lines with a match are gathered on the GPU and records are rendered from them: with --gz-on-gpu no inflated\n"
             "                                   text crosses the bus; same output; gains nothing where nearly every line matches)\n"
+            "               [--render-on-gpu]   (with --format json: batches whose line numbers are known when they are submitted leave the GPU as\n"
+            "                                    finished NDJSON; the others, and any the GPU refuses, are rendered on the host; same output; not with --follow)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -328,11 +330,13 @@ struct Batch { size_t input = 0; Bytes own; const uint8_t* ptr = nullptr; size_t
                std::vector<PackedInput> pack; size_t appended = 0;
                // --gz-on-gpu: the gzip files of a gz pack (`ptr` holds them compressed, end to end), one segment each, and where the
                // reader waits for the verdict on them
-               std::vector<GzFile> gz; std::shared_ptr<GzVerdict> verdict; };
+               std::vector<GzFile> gz; std::shared_ptr<GzVerdict> verdict;
+               bool armed = false; };   // --render-on-gpu: the batch was submitted with matchy_multi_scanner_set_render
 // what a batch contributes to the output: `text` / `text_len` is the buffer matchy_scan_result_to_ndjson returned (written to stdout as
 // it is and released by the printer: 200 bytes per match are not copied again on the way), `out` what --follow builds from it
 struct Done {
     std::string out; char* text = nullptr; size_t text_len = 0; Totals t; bool ok = true; size_t input = 0;
+    bool skip = false;   // nothing of the batch is printed from its result: its inputs are read again the old way
     Done() = default;
     Done(const Done&) = delete;
     Done& operator=(const Done&) = delete;
@@ -363,7 +367,48 @@ struct MatchPipeline {
     // --gather-lines: the scanners run with hit lines. Every result carries the lines of its matches, the renderers read those (the
     // text of a gz pack stays on the device), and "Lines with matches" is the device's count as with line context.
     bool gather = false;
+    // --render-on-gpu: a batch whose line bases are known when it is submitted leaves the device as finished NDJSON
+    // (matchy_multi_scanner_set_render): every batch without line numbers; with them the packs (every segment is a whole file: base 0)
+    // and an input's first batch. Any other batch, and a batch whose render status is not OK, goes through the host renderer as before.
+    bool render_gpu = false;
+    std::vector<char> input_started;   // the reader's: the input has had a batch submitted
+    std::atomic<size_t> gpu_batches{0}, gpu_fallback{0};
+    std::atomic<unsigned long long> gpu_bytes{0};
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
+    // arms the library for the batch about to be submitted, where its line bases are known
+    void arm(Batch& b) {
+        if (!render_gpu || !json) return;
+        const bool segmented = !b.pack.empty() || !b.gz.empty();
+        bool first = true;
+        if (!segmented) {
+            if (input_started.size() <= b.input) input_started.resize(b.input + 1, 0);
+            first = !input_started[b.input];
+            input_started[b.input] = 1;
+        }
+        if (line_ctx && !segmented && !first) return;
+        matchy_render_params_t p;
+        memset(&p, 0, sizeof(p));
+        p.flags = line_ctx ? (MATCHY_RENDER_LINE_NUMBERS | (input_line ? MATCHY_RENDER_INPUT_LINE : 0u)) : 0u;
+        std::vector<const char*> src;
+        if (segmented) { src = pack_sources(b); p.sources = src.data(); p.n_sources = src.size(); }
+        else p.source = sources[b.input].c_str();
+        b.armed = matchy_multi_scanner_set_render(ms, &p) == MATCHY_SUCCESS;   // copied at the call
+    }
+    // the block of an armed batch as the text of its Done; false: not rendered there (the host renderer takes over)
+    bool take_gpu_text(const matchy_scan_result_t& r, Done& d) {
+        const char* text = nullptr;
+        uint64_t n = 0;
+        int32_t status = MATCHY_RENDER_OK;
+        if (matchy_scan_result_ndjson(&r, &text, &n, &status) != MATCHY_SUCCESS || status != MATCHY_RENDER_OK) { ++gpu_fallback; return false; }
+        if (n) {
+            char* copy = (char*)malloc(n);   // the result goes when the hook returns; the printer frees this like the host renderer's buffer
+            if (!copy) { ++gpu_fallback; return false; }
+            memcpy(copy, text, n);
+            d.text = copy; d.text_len = n;
+        }
+        ++gpu_batches; gpu_bytes += n;
+        return true;
+    }
 
     // every input a batch carries: its own, or the files of a pack
     template <class F> static void each_input(const Batch& b, F&& f) {
@@ -377,11 +422,12 @@ struct MatchPipeline {
         size_t seq;
         { std::lock_guard<std::mutex> lk(mu); seq = submitted++; }
         int32_t rc;
+        arm(*hb);
         if (!hb->gz.empty()) {   // the text comes back only where something is rendered from it
             std::vector<matchy_gz_member_t> table;
             for (const GzFile& g : hb->gz) table.push_back(matchy_gz_member_t{g.offset, g.len, 0});
-            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather, hb);
-            if (rc != MATCHY_SUCCESS) { hb->verdict->set(nullptr, 0); delete hb; return seq; }   // every member goes the old way
+            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather && !hb->armed, hb);
+            if (rc != MATCHY_SUCCESS) { matchy_multi_scanner_set_render(ms, nullptr); hb->verdict->set(nullptr, 0); delete hb; return seq; }   // every member goes the old way
         }
         else if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
         else {
@@ -390,6 +436,7 @@ struct MatchPipeline {
             rc = matchy_multi_scanner_submit_segments(ms, hb->ptr, hb->len, starts.data(), starts.size(), hb, hb->reg);
         }
         if (rc != MATCHY_SUCCESS) {
+            matchy_multi_scanner_set_render(ms, nullptr);   // the parameters go with a batch that was queued, never with the next one
             // not queued (cannot happen for batches below 4 GiB): the printer never sees it
             fprintf(stderr, "[ERROR] batch of %zu bytes rejected: %s\n", hb->len, matchy_amd_last_error());
             { std::lock_guard<std::mutex> lk(mu); each_input(*hb, [&](size_t i) { rejected_inputs.push_back(i); }); }   // its matches are missing: the inputs count as failed
@@ -421,6 +468,12 @@ struct MatchPipeline {
         d.input = input;
         Totals& t = d.t;
         const bool segmented = !b.pack.empty() || !b.gz.empty();
+        if (!b.gz.empty() && b.armed && data == nullptr) {
+            // an armed gz pack came without its text: where its block is not to be had nothing can be rendered from it, and every
+            // member is read the old way, as if the GPU had accepted none
+            int32_t status = MATCHY_RENDER_OK;
+            if (matchy_scan_result_ndjson(&r, nullptr, nullptr, &status) != MATCHY_SUCCESS || status != MATCHY_RENDER_OK) { ++gpu_fallback; d.skip = true; b.verdict->set(nullptr, 0); return; }
+        }
         if (!b.gz.empty()) {
             // a gz pack: lines and bytes are those of the members the GPU accepted (separators and the regions of the others are not
             // counted); the others are read the old way by the reader, which waits for this verdict
@@ -434,7 +487,10 @@ struct MatchPipeline {
             // a pack: the newlines the packer appended are not the inputs'
             t.lines += r.lines - b.appended; t.candidates += r.candidates; t.bytes += len - b.appended; t.matches += r.n_hits;
         }
-        if ((line_ctx || gather) && segmented) {   // per segment, from the table the GPU filled
+        // an armed gz pack comes back without its text: the library scans it with line context, and its "Lines with matches" are the
+        // table's like those of any pack scanned with line context (plain batches of the same run are counted from their text as before)
+        const bool table_counts = line_ctx || gather || (b.armed && !b.gz.empty());
+        if (table_counts && segmented) {   // per segment, from the table the GPU filled
             const matchy_scan_segment_t* segs = nullptr;
             size_t n_segs = 0;
             if (matchy_scan_result_segments(&r, nullptr, nullptr, &segs, &n_segs) == MATCHY_SUCCESS) for (size_t k = 0; k < n_segs; ++k) t.lines_with_matches += segs[k].lines_with_matches;
@@ -456,6 +512,7 @@ struct MatchPipeline {
             }
         }
         const std::string& source = sources[input];
+        if (json && r.n_hits && b.armed && take_gpu_text(r, d)) return;
         if (json && r.n_hits) {   // every match of the batch in one call (the scanner caches the rendered data payloads)
             char* text = nullptr;
             size_t n = 0;
@@ -475,7 +532,8 @@ struct MatchPipeline {
     // the records of a batch of a scan with line context; `base` = lines of its input in front of it
     // (a packed input is whole: its lines count from zero)
     void render_numbered(matchy_scanner_t* sc, const matchy_scan_result_t& r, const uint8_t* data, const Batch& b, unsigned long long base, Done& d) {
-        if (!json || !r.n_hits || !d.ok) return;
+        if (!json || !r.n_hits || !d.ok || d.skip) return;
+        if (b.armed && take_gpu_text(r, d)) return;   // armed batches have base 0: a pack, or an input's first batch
         char* text = nullptr;
         size_t n = 0;
         int32_t rc;
@@ -771,7 +829,7 @@ struct GzPacker {
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false, render_gpu = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -803,6 +861,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--pack-inputs") pack = true;
         else if (a == "--gz-on-gpu") gz_gpu = true;
         else if (a == "--gather-lines") gather_lines = true;
+        else if (a == "--render-on-gpu") render_gpu = true;
         else if (a == "--tally") tally = true;
         else if (a.compare(0, 8, "--tally=") == 0) {
             const std::string n = a.substr(8);
@@ -816,6 +875,7 @@ int cmd_match(int argc, char** argv) {
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
     if (follow && tally) { fprintf(stderr, "Error: --tally is not supported with --follow (the report is printed after the last batch)\n"); return 1; }
     if (follow && pack) { fprintf(stderr, "Error: --pack-inputs is not supported with --follow (a followed file grows; a packed one is whole)\n"); return 1; }
+    if (follow && render_gpu) { fprintf(stderr, "Error: --render-on-gpu is not supported with --follow (a followed file's batches continue a line count only the printer knows)\n"); return 1; }
     if (follow && gz_gpu) { fprintf(stderr, "Error: --gz-on-gpu is not supported with --follow (a followed file grows; a gz pack is whole)\n"); return 1; }
     if (follow && stats) fprintf(stderr, "[INFO] Processing existing file content...\n");
     if (follow) for (size_t i = 1; i < pos.size(); ++i) if (pos[i] == "-") { fprintf(stderr, "Error: --follow mode not supported with stdin\n"); return 1; }
@@ -900,8 +960,9 @@ int cmd_match(int argc, char** argv) {
     // batch (line context; with --format summary it changes nothing that is printed)
     pl.line_ctx = line_numbers || input_line || (gz_gpu && format != "json");
     pl.input_line = input_line;
-    if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     pl.gather = gather_lines;
+    pl.render_gpu = render_gpu;   // takes effect with --format json only (MatchPipeline::arm)
+    if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     if (pl.gather) matchy_multi_scanner_set_hit_lines(ms, true);
     if (tally) matchy_multi_scanner_set_tally(ms, true);
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
@@ -1012,6 +1073,7 @@ int cmd_match(int argc, char** argv) {
         for (int d : devs) { if (!dl.empty()) dl += ","; dl += std::to_string(d); }
         fprintf(stderr, "\n[INFO] === Devices ===\n[INFO] HIP devices: %s (%zu scanner%s, batches of %zu MiB)\n", dl.c_str(), n_scanners,
                 n_scanners == 1 ? "" : "s", batch_bytes >> 20);
+        if (render_gpu) fprintf(stderr, "[INFO] Rendered %zu batches on the GPU (%llu bytes of NDJSON), %zu fell back to the host renderer\n", pl.gpu_batches.load(), pl.gpu_bytes.load(), pl.gpu_fallback.load());
         if (pack) fprintf(stderr, "[INFO] Packed %zu inputs into %zu batches (%llu bytes of input in all)\n", packed.inputs, packed.packs, t.bytes);
         if (gz_gpu) fprintf(stderr, "[INFO] Inflated %zu .gz inputs on the GPU in %zu batches (%llu -> %llu bytes), %zu read on the host\n", gzp.on_gpu, gzp.packs,
                             gzp.packed_bytes, gzp.text_bytes, gzp.on_host);

@@ -1,6 +1,7 @@
 #include "engine.h"
 #include "batch_reader.h"
 #include "distinct.h"
+#include "render_core.h"
 #include "tally.h"
 #include "unicode_lower.h"
 
@@ -1352,6 +1353,21 @@ void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool 
         segments_->resolve(batch, with_lines, to_host, profile_, stream);
         out.has_segments = true;
     }
+    // rendered records: behind the line pass and the segment pass, whose device arrays it reads, over the records where they lie
+    out.render = RenderView{};
+    if (last_.render && render_ && last_.lookup && !single_) {
+        RenderInput in;
+        in.b = batch;
+        in.data_offsets = reinterpret_cast<const int64_t*>(final_offs_.p); in.n_data_offsets = c.n_final_ids;
+        if (out.has_lines) { in.fin_lines = lines_->device_lines(); in.c4_lines = lines_->device_c4_lines(); }
+        if (out.has_segments) {
+            in.n_segments = (uint32_t)segments_->armed_count();
+            in.seg_of_fin = segments_->device_of_fin(); in.seg_of_c4 = segments_->device_of_c4();
+            in.seg_line_base = out.has_lines ? segments_->device_line_base() : nullptr;
+        }
+        render_->resolve(in, to_host, n_cu_, profile_, stream);
+        out.render.armed = true;
+    }
     // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
     if (want_cands && unique_) {
         distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);
@@ -1359,6 +1375,8 @@ void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool 
                            distinct_->last_ms(), timing_.total_ms);
     }
 }
+
+static void payload_json(const void* ctx, uint32_t data_off, std::string& json);   // below, with set_render
 
 // The wait for everything queued, what the passes read behind it, and the padding slots of partially filled chunks dropped.
 void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, hipStream_t stream) {
@@ -1378,6 +1396,15 @@ void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, h
     if (out.has_segments) {
         const SegmentPass::Result r = segments_->finish();
         out.segments = r.segments; out.n_segments = r.n_segments; out.seg_of_fin = r.seg_of_fin; out.seg_of_c4 = r.seg_of_c4;
+    }
+    if (out.render.armed) {
+        // further waits: payloads the table missed are rendered here and the pass repeated; the demand of the block is known only now
+        out.render = render_->finish(&payload_json, img_.get());
+        if (getenv("MATCHY_AMD_TRACE") && !single_) {
+            const NdjsonRender::Events& ev = render_->last_events();
+            fprintf(stderr, "[matchy_amd] render: block of %llu bytes, status %u, %u repeats, %llu misses, %u payloads rendered, %llu bytes copied to the host\n",
+                    (unsigned long long)out.render.len, out.render.status, ev.rounds, (unsigned long long)ev.misses, ev.payloads_added, (unsigned long long)ev.copied);
+        }
     }
     // drop the padding slots of partially filled chunks
     if (get_raw) {
@@ -1406,6 +1433,34 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
     queue_post_passes(out, dev_recs, want_cands, hit_mode, trace, stream);
     finish_fetch(out, want_cands, hit_mode, stream);
     if (trace) fprintf(stderr, "[matchy_amd] fetch: counters after %.3f ms, records after %.3f ms\n", t_counters, since());
+}
+
+// Rendered records (render.h). The parameters are the caller's until arm_render() takes them for one scan.
+static void payload_json(const void* ctx, uint32_t data_off, std::string& json) {
+    json.clear();
+    DataValue dv;
+    if (static_cast<const DbImage*>(ctx)->decode_data(data_off, dv)) to_json(dv, json); else json = "null";
+}
+
+void Scanner::set_render(const RenderParams* p) {
+    render_pending_.reset(p ? new RenderParams(*p) : nullptr);
+}
+
+void Scanner::arm_render(ScanRequest& rq, bool fetch_renders, hipStream_t stream) {
+    rq.render = false;
+    if (!render_pending_) return;
+    const std::unique_ptr<RenderParams> p = std::move(render_pending_);
+    if (!fetch_renders || !rq.lookup) return;
+    if ((p->flags & (render::FLAG_LINE_NUMBERS | render::FLAG_INPUT_LINE)) && !rq.lines)
+        throw ParamError{"set_render: line numbers and input lines need line context (set_line_context)"};
+    const size_t n_segments = segments_ ? segments_->armed_count() : 0;
+    if (p->per_segment && !n_segments) throw ParamError{"set_render: sources are given per segment, and the scan has no segments"};
+    if (p->per_segment && p->sources.size() != n_segments)
+        throw ParamError{"set_render: " + std::to_string(p->sources.size()) + " sources for a scan of " + std::to_string(n_segments) + " segments"};
+    MXY_HIP(hipSetDevice(ddb_->device));
+    if (!render_) render_ = std::make_unique<NdjsonRender>();
+    render_->arm(*p, stream);
+    rq.render = true;
 }
 
 // Segmented scans (segments.h). The table is the caller's until arm_segments() takes it for one scan.
@@ -1520,6 +1575,19 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             out.seg_own[s] = r;
         }
     }
+    // rendered records: the parameters of set_render arm every piece, with the lines of the pieces in front added to the line bases
+    const std::unique_ptr<RenderParams> render_all = std::move(render_pending_);
+    const bool render_on = render_all && lookup && fin;
+    if (render_on) {
+        if ((render_all->flags & (render::FLAG_LINE_NUMBERS | render::FLAG_INPUT_LINE)) && !(line_ctx_ || hit_lines_on_))
+            throw ParamError{"set_render: line numbers and input lines need line context (set_line_context)"};
+        if (render_all->per_segment && seg_all.empty()) throw ParamError{"set_render: sources are given per segment, and the scan has no segments"};
+        if (render_all->per_segment && render_all->sources.size() != seg_all.size())
+            throw ParamError{"set_render: " + std::to_string(render_all->sources.size()) + " sources for a scan of " + std::to_string(seg_all.size()) + " segments"};
+        out.render = RenderView{};
+        out.render.armed = true;
+        out.render_own.clear();
+    }
     do {
         const size_t n = newline_cut(data, pos, len, MAXC) - pos;
         if (n > ((size_t)1 << 30)) throw HipError{"scan_host: a single line exceeds 1 GiB"};
@@ -1556,15 +1624,26 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         ScanRequest rq;
         rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = (line_ctx_ || hit_lines_on_) && lookup;
         rq.hit_lines = hit_lines_on_ && lookup && fin;
-        size_t seg_first = 0;
+        size_t seg_first = 0, seg_last = 0;
         if (!seg_all.empty()) {
             // the last segment that starts at or in front of the piece .. the last that starts inside it (the last piece: the last of all)
             // (a run of empty segments that starts exactly at the piece's start belongs to this piece: from the first start equal to pos)
             const size_t at_pos = (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)pos) - seg_all.begin());
             seg_first = at_pos < seg_all.size() && seg_all[at_pos] == pos ? at_pos : at_pos - 1;
-            const size_t seg_last = pos + n >= len ? seg_all.size() - 1 : (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)(pos + n)) - seg_all.begin()) - 1;
+            seg_last = pos + n >= len ? seg_all.size() - 1 : (size_t)(std::lower_bound(seg_all.begin(), seg_all.end(), (uint32_t)(pos + n)) - seg_all.begin()) - 1;
             segments_->arm_piece(seg_all, seg_first, seg_last, (uint32_t)pos);
             segments_->upload(host_stream_);
+        }
+        if (render_on) {
+            // a segment that began in an earlier piece goes on at the piece's first byte: its lines so far join its base
+            RenderParams p;
+            p.flags = render_all->flags; p.per_segment = render_all->per_segment;
+            if (p.per_segment)
+                for (size_t k = seg_first; k <= seg_last; ++k) { p.sources.push_back(render_all->sources[k]); p.line_bases.push_back(render_all->line_bases[k] + out.seg_own[k].lines); }
+            else { p.sources = render_all->sources; p.line_bases.assign(1, (render_all->line_bases.empty() ? 0 : render_all->line_bases[0]) + out.lines); }
+            if (!render_) render_ = std::make_unique<NdjsonRender>();
+            render_->arm(p, host_stream_);
+            rq.render = true;
         }
         scan_device(rq, host_stream_);
         ScanOutput part;
@@ -1579,6 +1658,11 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         if (part.has_lines) {
             out.has_lines = true; out.lines_with_matches += part.lines_with_matches;
             if (fin_lines && part.n_fin) append_shifted_lines(part.fin_lines, part.n_fin, (uint32_t)pos, (uint32_t)out.lines, *fin_lines);
+        }
+        // a piece renders its own records: the blocks go end to end, and one piece that was too large is the verdict of the whole
+        if (part.render.armed) {
+            if (part.render.status != RENDER_OK) out.render.status = part.render.status;
+            else if (part.render.len) out.render_own.insert(out.render_own.end(), part.render.text, part.render.text + part.render.len);
         }
         // a piece ends at a line end: its block goes behind the blocks of the pieces in front of it
         if (part.has_hit_lines) {
@@ -1615,6 +1699,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         v.line_off = out.hl_off_own.data(); v.line_no = out.hl_no_own.empty() ? nullptr : out.hl_no_own.data();
         v.line_of_fin = out.hl_of_own.empty() ? nullptr : out.hl_of_own.data(); v.line_of_c4 = nullptr;
     }
+    if (out.render.armed && out.render.status == RENDER_OK) { out.render.text = out.render_own.empty() ? nullptr : out.render_own.data(); out.render.len = out.render_own.size(); }
     if (out.has_segments) {
         out.segments = out.seg_own.data(); out.n_segments = out.seg_own.size();
         out.seg_of_fin = out.seg_of_own.empty() ? nullptr : out.seg_of_own.data();

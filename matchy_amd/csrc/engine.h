@@ -12,6 +12,7 @@
 #include "hit_lines.h"
 #include "inflate.h"
 #include "line_index.h"
+#include "render.h"
 #include "result_layout.h"
 #include "scan_types.h"
 #include "segments.h"
@@ -118,6 +119,10 @@ struct ScanOutput {
     HitLinesView hit_lines;
     std::vector<uint8_t> hl_text_own;
     std::vector<uint32_t> hl_off_own, hl_no_own, hl_of_own;
+    // rendered records (ScanRequest::render): the NDJSON block of the records of this fetch, BORROWED like fin (a device pointer unless
+    // HITS_FINAL); scan_host owns it in render_own, the blocks of its pieces end to end
+    RenderView render;
+    std::vector<uint8_t> render_own;
 };
 
 // Process-wide registry of the host ranges this library pinned (hipHostRegister): the caller's (matchy_amd_host_register, kept until
@@ -167,6 +172,7 @@ struct ScanRequest {
     bool compact = false;      // IPv4 results leave as 8-byte records (ScanOutput::c4, scan_types.h c4_pack) when compact_possible()
     bool lines = false;        // line context: fetch() resolves every final record to its line (line_index.hip); needs `lookup`
     bool hit_lines = false;    // fetch() packs the distinct lines with a hit into one block (hit_lines.hip); needs `lines`
+    bool render = false;       // fetch() renders the records as NDJSON on the device (render.hip); set by Scanner::arm_render
 };
 
 // Moves the line records of a piece that starts `base` bytes and `line_base` lines into the whole (append_shifted for the line array).
@@ -215,6 +221,18 @@ public:
     bool hit_lines() const { return hit_lines_on_; }
     // with set_profile: milliseconds of mark + rank + lengths + offsets, of the copy kernel, and of the block's device-to-host copy
     void hit_lines_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (hit_lines_) hit_lines_->timing(out_ms); }
+    // Rendered records (render.hip): set_render arms the NEXT lookup scan (copied; null disarms). arm_render is what the entries of a
+    // lookup scan call behind arm_segments and in front of scan_device: it consumes the pending parameters whether the scan succeeds or
+    // not, checks them against the request (ParamError: line flags without line context, per-segment sources without segments or in
+    // another number), queues the copy of the source table on `stream` and sets rq.render. fetch_renders false (a counts-only fetch):
+    // nothing is rendered. Never armed, nothing of it is allocated, launched or copied.
+    void set_render(const RenderParams* p);
+    void arm_render(ScanRequest& rq, bool fetch_renders, hipStream_t stream);
+    bool render_pending() const { return (bool)render_pending_; }
+    // with set_profile: milliseconds of measure + offsets, of the write step, and of the block's device-to-host copy of the last fetch
+    void render_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (render_) render_->timing(out_ms); }
+    // repeats of the pass, payloads rendered and misses of the last fetch that rendered (null: none yet)
+    const NdjsonRender::Events* render_events() const { return render_ ? &render_->last_events() : nullptr; }
     // Segmented scans (segments.hip): `starts` (copied) describes the buffer of the NEXT lookup scan as n segments — starts[0] == 0,
     // non-decreasing, every start <= the scan's length, every non-empty segment in front of the last ends in '\n'. n == 0 or null
     // clears a pending table. arm_segments(len) is what the entries of a lookup scan call before scan_device: it consumes the pending
@@ -367,6 +385,8 @@ private:
     bool hit_lines_on_ = false;
     std::unique_ptr<HitLines> hit_lines_;      // created by the first fetch of a scan with hit lines
     std::unique_ptr<SegmentPass> segments_;    // created by the first set_segments with a table
+    std::unique_ptr<RenderParams> render_pending_;   // set_render, until arm_render takes it
+    std::unique_ptr<NdjsonRender> render_;     // created by the first arm_render that arms a scan
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off

@@ -12,6 +12,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -28,7 +29,23 @@ using namespace mxy;
 using namespace mxy::capi;
 
 namespace {
-struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz)
+// matchy_multi_scanner_set_render: the caller's parameters, copied, until the worker that takes the batch arms its scanner with them
+struct RenderSpec {
+    uint32_t flags = 0;
+    bool per_segment = false;
+    std::vector<std::string> sources;   // one, or one per segment
+    std::vector<uint64_t> line_bases;   // parallel to sources
+    void arm(matchy_scanner_t* sc) const {
+        matchy_render_params_t p{};
+        p.flags = flags;
+        std::vector<const char*> ptrs;
+        for (const std::string& s : sources) ptrs.push_back(s.c_str());
+        if (per_segment) { p.sources = ptrs.data(); p.n_sources = ptrs.size(); p.line_bases = line_bases.data(); }
+        else { p.source = ptrs[0]; p.line_base = line_bases[0]; }
+        (void)matchy_scanner_set_render(sc, &p);   // copies
+    }
+};
+struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; std::shared_ptr<const RenderSpec> render; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz)
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
     const matchy_t* db = nullptr;
@@ -49,6 +66,7 @@ struct MultiScanner {
     bool line_ctx = false;   // matchy_multi_scanner_set_line_context: every worker sets its scanner to it before a scan
     bool hit_lines = false;  // matchy_multi_scanner_set_hit_lines: likewise
     bool tally = false, tally_ever = false;   // matchy_multi_scanner_set_tally: likewise
+    std::shared_ptr<const RenderSpec> render_next;   // matchy_multi_scanner_set_render: goes with the next batch submitted
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
     std::string first_error;   // of a worker (scanner creation, scan): reported through matchy_amd_last_error by next()
@@ -88,9 +106,12 @@ struct MultiScanner {
             std::string err;
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
             else if (!j.gz.empty()) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
-                matchy_scanner_set_line_context(scanners[w], want_lines);
+                // an armed pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
+                // (lines with matches per segment) whatever the setting is
+                matchy_scanner_set_line_context(scanners[w], want_lines || (j.render && !j.gz_text));
                 matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
+                if (j.render) j.render->arm(scanners[w]);
                 d.status = matchy_scanner_scan_gz(scanners[w], j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res);
                 d.data = nullptr; d.len = 0;
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
@@ -101,6 +122,7 @@ struct MultiScanner {
                 matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
                 if (!j.starts.empty()) d.status = matchy_scanner_set_segments(scanners[w], j.starts.data(), j.starts.size());
+                if (j.render) j.render->arm(scanners[w]);
                 if (d.status == MATCHY_SUCCESS) d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
@@ -180,6 +202,26 @@ void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t* h, bool enabled)
     std::lock_guard<std::mutex> lk(ms->mu);
     ms->hit_lines = enabled;
 }
+// Rendered records: the parameters arm the NEXT batch submitted (whichever submit call that is) and no other; the worker that takes
+// the batch arms its scanner with them. The result of the batch owns the block (matchy_scan_result_ndjson).
+int32_t matchy_multi_scanner_set_render(matchy_multi_scanner_t* h, const matchy_render_params_t* p) {
+    if (!h) return MATCHY_ERROR_INVALID_PARAM;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::shared_ptr<RenderSpec> spec;
+    if (p) {
+        if (p->flags & ~(MATCHY_RENDER_LINE_NUMBERS | MATCHY_RENDER_INPUT_LINE)) { set_error("matchy_multi_scanner_set_render: unknown flags"); return MATCHY_ERROR_INVALID_PARAM; }
+        if (p->sources && !p->n_sources) { set_error("matchy_multi_scanner_set_render: sources without n_sources"); return MATCHY_ERROR_INVALID_PARAM; }
+        spec = std::make_shared<RenderSpec>();
+        spec->flags = p->flags;
+        if (p->sources) {
+            spec->per_segment = true;
+            for (size_t k = 0; k < p->n_sources; ++k) { spec->sources.push_back(p->sources[k] ? p->sources[k] : "-"); spec->line_bases.push_back(p->line_bases ? p->line_bases[k] : 0); }
+        } else { spec->sources.push_back(p->source ? p->source : "-"); spec->line_bases.push_back(p->line_base); }
+    }
+    std::lock_guard<std::mutex> lk(ms->mu);
+    ms->render_next = std::move(spec);
+    return MATCHY_SUCCESS;
+}
 // Hit tally: the workers switch their scanners' tallies before a scan, like line context; the read-out and the reset touch the scanners
 // themselves and therefore need the workers idle (nothing pending).
 int32_t matchy_multi_scanner_set_tally(matchy_multi_scanner_t* h, bool enabled) {
@@ -249,7 +291,7 @@ int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t* h, const uint8_
     // blocks while the job queue is full OR max_inflight batches are out (someone has to call matchy_multi_scanner_next: a caller that
     // submits and gathers on ONE thread interleaves the two — matchy_multi_scanner_pending() tells it when a next() is due)
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}, {}, false});
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}, {}, false, std::move(ms->render_next)});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }
@@ -260,7 +302,7 @@ int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t* h, const ui
     std::vector<uint32_t> table(starts, starts + n);   // copied in front of the lock
     std::unique_lock<std::mutex> lk(ms->mu);
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table), {}, false});
+    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table), {}, false, std::move(ms->render_next)});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }
@@ -271,7 +313,7 @@ int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t* h, const uint8_t*
     std::vector<matchy_gz_member_t> table(members, members + n);   // copied in front of the lock
     std::unique_lock<std::mutex> lk(ms->mu);
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, std::move(table), want_text});
+    ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, std::move(table), want_text, std::move(ms->render_next)});
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }

@@ -1,10 +1,18 @@
-// Host-side IP address text <-> binary helpers with Rust std semantics (the reference parses keys with
-// `str::parse::<IpAddr>()`, crates/matchy-format/src/mmdb_builder.rs:338-365, and prints with Display).
+// IP address text <-> binary helpers with Rust std semantics (the reference parses keys with
+// `str::parse::<IpAddr>()`, crates/matchy-format/src/mmdb_builder.rs:338-365, and prints with Display). Parsing and the
+// formatting into a caller's buffer (format_*_to) are host/device code: the NDJSON renderer on the GPU (render_core.h) uses
+// the same definitions as the host. The std::string forms wrap them.
 #pragma once
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <string>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MXY_ADDR_HD __host__ __device__ inline
+#else
+#define MXY_ADDR_HD inline
+#endif
 
 namespace mxy {
 
@@ -13,12 +21,16 @@ struct IpAddr {
     uint8_t b[16] = {0};  // v4: b[0..4]
 };
 
+// room for any text format_cidr_to writes: 39 bytes of IPv6, '/', and a 32-bit prefix in decimal
+constexpr uint32_t IP_CIDR_TEXT_MAX = 56;
+
 namespace detail {
+// Every loop of the parser is bounded by its digit limits and the eight groups, not by n: a text of any length costs the same.
 struct AddrParser {
     const char* s;
     size_t n, pos = 0;
     // read_number(radix, max_digits, allow_zero_prefix) — atomic
-    bool number(int radix, int max_digits, bool allow_zero_prefix, uint32_t maxval, uint32_t& out) {
+    MXY_ADDR_HD bool number(int radix, int max_digits, bool allow_zero_prefix, uint32_t maxval, uint32_t& out) {
         size_t p = pos;
         uint32_t v = 0;
         int digits = 0;
@@ -42,7 +54,7 @@ struct AddrParser {
         pos = p;
         return true;
     }
-    bool ipv4(uint8_t o[4]) {
+    MXY_ADDR_HD bool ipv4(uint8_t o[4]) {
         size_t save = pos;
         for (int i = 0; i < 4; ++i) {
             if (i > 0) {
@@ -56,7 +68,7 @@ struct AddrParser {
         return true;
     }
     // read_groups: returns (count, ends_with_ipv4)
-    size_t groups(uint16_t* g, size_t limit, bool& v4) {
+    MXY_ADDR_HD size_t groups(uint16_t* g, size_t limit, bool& v4) {
         v4 = false;
         for (size_t i = 0; i < limit; ++i) {
             if (i + 1 < limit) {  // try a trailing embedded IPv4 (needs two groups)
@@ -80,11 +92,11 @@ struct AddrParser {
         }
         return limit;
     }
-    bool ipv6(uint16_t seg[8]) {
+    MXY_ADDR_HD bool ipv6(uint16_t seg[8]) {
         uint16_t head[8] = {0};
         bool head_v4;
         size_t hs = groups(head, 8, head_v4);
-        if (hs == 8) { memcpy(seg, head, 16); return true; }
+        if (hs == 8) { for (int i = 0; i < 8; ++i) seg[i] = head[i]; return true; }
         if (head_v4) return false;
         if (!(pos < n && s[pos] == ':')) return false;
         ++pos;
@@ -95,58 +107,79 @@ struct AddrParser {
         size_t limit = 8 - (hs + 1);
         size_t ts = groups(tail, limit, tv4);
         for (size_t i = 0; i < ts; ++i) head[8 - ts + i] = tail[i];
-        memcpy(seg, head, 16);
+        for (int i = 0; i < 8; ++i) seg[i] = head[i];
         return true;
     }
 };
+
+// v in decimal / lower-case hex without leading zeros; returns the number of characters (at most 10 / 4)
+MXY_ADDR_HD uint32_t put_u32_dec(uint32_t v, char* o) {
+    uint32_t n = 1;
+    for (uint32_t t = v; t >= 10; t /= 10) ++n;
+    for (uint32_t k = n; k-- > 0; v /= 10) o[k] = (char)('0' + v % 10);
+    return n;
+}
+MXY_ADDR_HD uint32_t put_u16_hex(uint32_t v, char* o) {
+    uint32_t n = 1;
+    for (uint32_t t = v; t >= 16; t /= 16) ++n;
+    for (uint32_t k = n; k-- > 0; v /= 16) o[k] = (char)((v & 15) < 10 ? '0' + (v & 15) : 'a' + ((v & 15) - 10));
+    return n;
+}
 }  // namespace detail
 
-inline bool parse_ipv4(const char* s, size_t n, uint8_t out[4]) {
+MXY_ADDR_HD bool parse_ipv4(const char* s, size_t n, uint8_t out[4]) {
     detail::AddrParser p{s, n};
     return p.ipv4(out) && p.pos == n;
 }
-inline bool parse_ipv6(const char* s, size_t n, uint8_t out[16]) {
+MXY_ADDR_HD bool parse_ipv6(const char* s, size_t n, uint8_t out[16]) {
     detail::AddrParser p{s, n};
     uint16_t seg[8];
     if (!p.ipv6(seg) || p.pos != n) return false;
     for (int i = 0; i < 8; ++i) { out[2 * i] = (uint8_t)(seg[i] >> 8); out[2 * i + 1] = (uint8_t)seg[i]; }
     return true;
 }
-inline bool parse_ip(const char* s, size_t n, IpAddr& a) {
+MXY_ADDR_HD bool parse_ip(const char* s, size_t n, IpAddr& a) {
     a = IpAddr();
     if (parse_ipv4(s, n, a.b)) { a.v6 = false; return true; }
     if (parse_ipv6(s, n, a.b)) { a.v6 = true; return true; }
     return false;
 }
 
-inline std::string format_ipv4(const uint8_t a[4]) {
-    char b[20];
-    snprintf(b, sizeof(b), "%u.%u.%u.%u", a[0], a[1], a[2], a[3]);
-    return b;
+// The *_to forms write into `o` (no terminator) and return the length: at most 15, 39 and IP_CIDR_TEXT_MAX characters.
+MXY_ADDR_HD uint32_t format_ipv4_to(const uint8_t a[4], char* o) {
+    uint32_t n = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (i) o[n++] = '.';
+        n += detail::put_u32_dec(a[i], o + n);
+    }
+    return n;
 }
 // <Ipv6Addr as Display>: "::ffff:a.b.c.d" for IPv4-mapped, otherwise RFC 5952 (longest zero run >= 2 compressed, first wins)
-inline std::string format_ipv6(const uint8_t a[16]) {
+MXY_ADDR_HD uint32_t format_ipv6_to(const uint8_t a[16], char* o) {
     uint16_t seg[8];
     for (int i = 0; i < 8; ++i) seg[i] = (uint16_t)((a[2 * i] << 8) | a[2 * i + 1]);
-    if (!seg[0] && !seg[1] && !seg[2] && !seg[3] && !seg[4] && seg[5] == 0xffff) return "::ffff:" + format_ipv4(a + 12);
+    uint32_t n = 0;
+    if (!seg[0] && !seg[1] && !seg[2] && !seg[3] && !seg[4] && seg[5] == 0xffff) {
+        const char* lead = "::ffff:";
+        for (int i = 0; i < 7; ++i) o[n++] = lead[i];
+        return n + format_ipv4_to(a + 12, o + n);
+    }
     int bs = 0, bl = 0, cs = 0, cl = 0;
     for (int i = 0; i < 8; ++i) {
         if (seg[i] == 0) { if (cl == 0) cs = i; ++cl; if (cl > bl) { bl = cl; bs = cs; } }
         else cl = 0;
     }
-    auto sub = [&](int lo, int hi) {
-        std::string r;
-        char b[8];
-        for (int i = lo; i < hi; ++i) { if (i > lo) r.push_back(':'); snprintf(b, sizeof(b), "%x", seg[i]); r += b; }
-        return r;
-    };
-    if (bl > 1) return sub(0, bs) + "::" + sub(bs + bl, 8);
-    return sub(0, 8);
+    if (bl <= 1) { bs = 8; bl = 0; }   // nothing to compress: one run of eight groups
+    for (int i = 0; i < bs; ++i) { if (i) o[n++] = ':'; n += detail::put_u16_hex(seg[i], o + n); }
+    if (bs == 8) return n;
+    o[n++] = ':'; o[n++] = ':';
+    for (int i = bs + bl; i < 8; ++i) { if (i > bs + bl) o[n++] = ':'; n += detail::put_u16_hex(seg[i], o + n); }
+    return n;
 }
-inline std::string format_ip(const IpAddr& a) { return a.v6 ? format_ipv6(a.b) : format_ipv4(a.b); }
+MXY_ADDR_HD uint32_t format_ip_to(const IpAddr& a, char* o) { return a.v6 ? format_ipv6_to(a.b, o) : format_ipv4_to(a.b, o); }
 
 // format_cidr_into (crates/matchy/src/bin/cli_utils.rs:107-141)
-inline std::string format_cidr(const IpAddr& a, unsigned prefix) {
+MXY_ADDR_HD uint32_t format_cidr_to(const IpAddr& a, unsigned prefix, char* o) {
     IpAddr net = a;
     int nb = a.v6 ? 16 : 4;
     for (int i = 0; i < nb; ++i) {
@@ -154,7 +187,14 @@ inline std::string format_cidr(const IpAddr& a, unsigned prefix) {
         uint8_t mask = left >= 8 ? 0xFF : left <= 0 ? 0 : (uint8_t)(0xFF << (8 - left));
         net.b[i] &= mask;
     }
-    return format_ip(net) + "/" + std::to_string(prefix);
+    uint32_t n = format_ip_to(net, o);
+    o[n++] = '/';
+    return n + detail::put_u32_dec(prefix, o + n);
 }
+
+inline std::string format_ipv4(const uint8_t a[4]) { char b[IP_CIDR_TEXT_MAX]; return std::string(b, format_ipv4_to(a, b)); }
+inline std::string format_ipv6(const uint8_t a[16]) { char b[IP_CIDR_TEXT_MAX]; return std::string(b, format_ipv6_to(a, b)); }
+inline std::string format_ip(const IpAddr& a) { return a.v6 ? format_ipv6(a.b) : format_ipv4(a.b); }
+inline std::string format_cidr(const IpAddr& a, unsigned prefix) { char b[IP_CIDR_TEXT_MAX]; return std::string(b, format_cidr_to(a, prefix, b)); }
 
 }  // namespace mxy

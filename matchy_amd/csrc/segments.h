@@ -81,6 +81,9 @@ public:
     void timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = ms_[k]; }
     const uint32_t* device_of_fin() const { return of_fin_.p; }
     const uint32_t* device_of_c4() const { return of_c4_.p; }
+    // what the renderer of the same fetch reads: the segments of the scan in flight, and the '\n' count in front of each (line context)
+    size_t armed_count() const { return active_ ? starts_.size() : 0; }
+    const uint32_t* device_line_base() const { return line_base_.p; }
 
 private:
     std::vector<uint32_t> pending_, starts_;   // the table set() left, and the one of the scan in flight
