@@ -645,6 +645,33 @@ int32_t matchy_multi_scanner_set_tally(matchy_multi_scanner_t *ms, bool enabled)
 int32_t matchy_multi_scanner_tally_top(matchy_multi_scanner_t *ms, size_t limit, matchy_tally_t *out);
 void matchy_multi_scanner_reset_tally(matchy_multi_scanner_t *ms);
 void matchy_tally_free(matchy_tally_t *tally);
+
+/* ---- Whole-line queries (opt-in, off by default: with it never enabled a scanner allocates, launches and copies nothing more and every
+ * output stays as it is). While on, a lookup scan — matchy_scanner_scan, _scan_device, _submit_device / _wait and the multi-device
+ * scanner's entries — treats its buffer as a LIST OF QUERIES instead of log text, and answers every line like matchy_query answers one
+ * value (Database::lookup without the cache). Extraction, the extract flags of the scanner and the label rules play no part.
+ *   Lines are cut at '\n'; a final piece without '\n' is a line; a buffer that ends in '\n' has no empty line behind it; len == 0 has none.
+ *   The query is the line without exactly one trailing '\r'. Nothing else is trimmed; an empty line is a query.
+ *   A query the IP address parser accepts as a whole (IPv4, IPv6, IPv6 with an embedded dotted quad; no zone, no prefix length) walks the
+ *   tree, IPv4 in an IPv6 tree from its IPv4 start node. Anything else takes the string path: literal table, then every glob over the
+ *   whole query, with the case folding of the database. A query that is not valid UTF-8 is not looked up and is counted.
+ *   A found query is ONE ordinary hit record: start / length = the query inside the buffer (without the '\r'); kind, prefix, value and
+ *   ids as the single query reports them; item type MATCHY_ITEM_TYPE_IPV4 / _IPV6 for addresses and _DOMAIN for strings. A sorted fetch
+ *   is in line order, `lines` stays the number of '\n' bytes, `candidates` counts the queries that were looked up.
+ *   A query of 16 MiB or more, or more than 65535 glob ids on one query, fail the scan as they do without the mode.
+ * Works with sorted fetches, line context (`line` is the 0-based index of the query), the hit tally (hits per distinct query text) and the
+ * multi-device scanner. NOT combined with segments, gz scans, hit lines or rendered records: a scan that finds one of them set together
+ * with the mode launches nothing and returns MATCHY_ERROR_INVALID_PARAM, matchy_amd_last_error() names the pair, and a pending segment
+ * table or render parameters are dropped. The scan runs on one stream: matchy_scanner_set_slices has no effect on it. */
+void matchy_scanner_set_whole_lines(matchy_scanner_t *scanner, bool enabled);
+bool matchy_scanner_whole_lines(const matchy_scanner_t *scanner);
+/* queries, address queries, string queries and queries that are not valid UTF-8 of the last scan in the mode (matchy_scanner_scan: summed
+ * over its pieces) */
+void matchy_scanner_get_whole_lines_counters(const matchy_scanner_t *scanner, uint64_t out[4]);
+/* With matchy_scanner_set_profile: milliseconds of count + prefix, of scatter + classify, and of the lookups of the last scan in the mode. */
+void matchy_scanner_get_whole_lines_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* The mode for every worker's scanner; needs matchy_multi_scanner_pending() == 0 (MATCHY_ERROR_INVALID_PARAM otherwise). */
+int32_t matchy_multi_scanner_set_whole_lines(matchy_multi_scanner_t *ms, bool enabled);
 /* Deterministic builds for tests: fixes the build_epoch metadata value. */
 int32_t matchy_builder_set_build_epoch(matchy_builder_t *b, uint64_t epoch);
 

@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_set_hit_lines",
     "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
     "matchy_multi_scanner_set_render",
+    "matchy_scanner_set_whole_lines", "matchy_scanner_whole_lines", "matchy_scanner_get_whole_lines_counters",
+    "matchy_scanner_get_whole_lines_timing", "matchy_multi_scanner_set_whole_lines",
 ]
 
 # MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
@@ -311,6 +313,11 @@ def lib():
         "matchy_scan_result_gz": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_gz_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_multi_scanner_submit_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_bool, vp]),
+        "matchy_scanner_set_whole_lines": (None, [vp, C.c_bool]),
+        "matchy_scanner_whole_lines": (C.c_bool, [vp]),
+        "matchy_scanner_get_whole_lines_counters": (None, [vp, C.POINTER(C.c_uint64)]),
+        "matchy_scanner_get_whole_lines_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_multi_scanner_set_whole_lines": (C.c_int32, [vp, C.c_bool]),
         "matchy_scanner_set_tally": (None, [vp, C.c_bool]),
         "matchy_scanner_tally": (C.c_bool, [vp]),
         "matchy_scanner_reset_tally": (None, [vp]),
@@ -943,6 +950,25 @@ class Scanner:
     def hit_lines_enabled(self) -> bool:
         return bool(lib().matchy_scanner_hit_lines(self._h))
 
+    def set_whole_lines(self, on=True):
+        """whole-line queries for the next lookup scans: every line of the buffer is one query, looked up like Database.query does a
+        single value (off by default; not together with segments, gz scans, hit lines or rendered records)"""
+        lib().matchy_scanner_set_whole_lines(self._h, bool(on))
+
+    def whole_lines_enabled(self) -> bool:
+        return bool(lib().matchy_scanner_whole_lines(self._h))
+
+    def whole_lines_counters(self):
+        """of the last scan in whole-line mode: queries, address queries, string queries, queries that are not valid UTF-8"""
+        out = (C.c_uint64 * 4)()
+        lib().matchy_scanner_get_whole_lines_counters(self._h, out)
+        return dict(queries=int(out[0]), address=int(out[1]), string=int(out[2]), invalid_utf8=int(out[3]))
+
+    def whole_lines_timing_ms(self):
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_whole_lines_timing(self._h, out)
+        return dict(count_prefix=out[0], scatter_classify=out[1], lookup=out[2])
+
     def set_render(self, flags=0, source=None, sources=None, line_base=0, line_bases=None):
         """arms the NEXT scan / scan_device / submit_device / scan_gz: its result answers rendered_ndjson() with the NDJSON text of its
         records, written on the GPU (matchy_scanner_set_render). flags: RENDER_LINE_NUMBERS / RENDER_INPUT_LINE (need line context).
@@ -1095,6 +1121,12 @@ class MultiScanner:
         rc = lib().matchy_multi_scanner_set_render(self._h, None if p is None else C.byref(p))
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_set_render failed ({rc}): " + last_error())
+
+    def set_whole_lines(self, on=True):
+        """whole-line queries on every worker's scanner, from the next batch on; needs pending() == 0"""
+        rc = lib().matchy_multi_scanner_set_whole_lines(self._h, bool(on))
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_set_whole_lines failed ({rc}): " + last_error())
 
     def set_tally(self, on=True):
         """hit tally on every worker's scanner, from the next batch on"""

@@ -987,6 +987,16 @@ void matchy_scanner_get_hit_lines_timing(const matchy_scanner_t* s, float out[3]
     if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->hit_lines_timing(out);
 }
 
+// whole-line queries (Scanner::set_whole_lines, whole_lines.hip)
+void matchy_scanner_set_whole_lines(matchy_scanner_t* s, bool on) { if (s) reinterpret_cast<ScannerH*>(s)->sc->set_whole_lines(on); }
+bool matchy_scanner_whole_lines(const matchy_scanner_t* s) { return s && reinterpret_cast<const ScannerH*>(s)->sc->whole_lines(); }
+void matchy_scanner_get_whole_lines_counters(const matchy_scanner_t* s, uint64_t out[4]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->whole_lines_counters(out);
+}
+void matchy_scanner_get_whole_lines_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->whole_lines_timing(out);
+}
+
 // segmented scans (Scanner::set_segments, segments.hip)
 int32_t matchy_scanner_set_segments(matchy_scanner_t* s, const uint32_t* starts, size_t n) {
     if (!s) return MATCHY_ERROR_INVALID_PARAM;
@@ -1095,6 +1105,7 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
         const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
+        h->sc->arm_whole_lines(rq);
         h->sc->arm_segments(len, st);
         h->sc->arm_render(rq, fetch_renders(fetch_mode), st);
         h->sc->scan_device(rq, st);
@@ -1127,6 +1138,7 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
         rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
         rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
         h->pending_hit_lines = request_lines(*h->sc, fetch_mode, rq);
+        h->sc->arm_whole_lines(rq);
         h->sc->arm_segments(len, reinterpret_cast<hipStream_t>(stream));
         h->sc->arm_render(rq, fetch_renders(fetch_mode), reinterpret_cast<hipStream_t>(stream));
         h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
@@ -1176,6 +1188,7 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
     if (!members || n == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
     ScannerH* h = reinterpret_cast<ScannerH*>(s);
     try {
+        { ScanRequest mode; mode.lookup = true; h->sc->arm_whole_lines(mode, true); }   // refused in front of the inflate kernels
         const Scanner::GzBatch b = h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it

@@ -71,6 +71,8 @@ int usage() {
             "                                   text crosses the bus; same output; gains nothing where nearly every line matches)\n"
             "               [--render-on-gpu]   (with --format json: batches whose line numbers are known when they are submitted leave the GPU as\n"
             "                                    finished NDJSON; the others, and any the GPU refuses, are rendered on the host; same output; not with --follow)\n"
+            "               [--whole-lines]   (every input line is ONE query, looked up whole like `matchy query` does a value: lists of addresses, names or\n"
+            "                                  hashes; no extraction; not with --extractors, --pack-inputs, --gz-on-gpu, --gather-lines, --render-on-gpu)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
@@ -374,6 +376,14 @@ struct MatchPipeline {
     std::vector<char> input_started;   // the reader's: the input has had a batch submitted
     std::atomic<size_t> gpu_batches{0}, gpu_fallback{0};
     std::atomic<unsigned long long> gpu_bytes{0};
+    // --whole-lines: the scanners' counters of every batch (queries, address, string, invalid UTF-8), summed for -s
+    bool whole_lines = false;
+    std::atomic<unsigned long long> wl_counters[4] = {{0}, {0}, {0}, {0}};
+    void add_whole_lines(const matchy_scanner_t* sc) {
+        uint64_t c[4] = {0, 0, 0, 0};
+        matchy_scanner_get_whole_lines_counters(sc, c);
+        for (int k = 0; k < 4; ++k) wl_counters[k] += c[k];
+    }
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
     // arms the library for the batch about to be submitted, where its line bases are known
     void arm(Batch& b) {
@@ -549,6 +559,7 @@ struct MatchPipeline {
     static void* batch_hook(void* user, size_t, matchy_scanner_t* sc, const matchy_scan_result_t* r, const uint8_t* data, size_t len, void* tag) {
         MatchPipeline* pl = (MatchPipeline*)user;
         Done* d = new Done();
+        if (pl->whole_lines) pl->add_whole_lines(sc);
         pl->render(sc, *r, data, len, *(const Batch*)tag, *d);
         return d;
     }
@@ -563,6 +574,7 @@ struct MatchPipeline {
             d.ok = false;
             return;
         }
+        if (whole_lines) add_whole_lines(sc);
         render(sc, r, b.ptr, b.len, b, d);
         if (line_ctx) {   // --follow: batches of an input come one after the other, the count continues across the polls
             render_numbered(sc, r, b.ptr, b, line_base[b.input], d);
@@ -829,7 +841,7 @@ struct GzPacker {
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false, render_gpu = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -862,6 +874,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--gz-on-gpu") gz_gpu = true;
         else if (a == "--gather-lines") gather_lines = true;
         else if (a == "--render-on-gpu") render_gpu = true;
+        else if (a == "--whole-lines") whole_lines = true;
         else if (a == "--tally") tally = true;
         else if (a.compare(0, 8, "--tally=") == 0) {
             const std::string n = a.substr(8);
@@ -873,6 +886,11 @@ int cmd_match(int argc, char** argv) {
     }
     if (pos.size() < 2) return usage();
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
+    if (whole_lines) {
+        // the mode has no extraction to configure, and the library refuses it together with segments, gz scans, hit lines and rendered records
+        const char* other = !extractors.empty() ? "--extractors" : pack ? "--pack-inputs" : gz_gpu ? "--gz-on-gpu" : gather_lines ? "--gather-lines" : render_gpu ? "--render-on-gpu" : nullptr;
+        if (other) { fprintf(stderr, "Error: --whole-lines is not supported with %s\n", other); return 1; }
+    }
     if (follow && tally) { fprintf(stderr, "Error: --tally is not supported with --follow (the report is printed after the last batch)\n"); return 1; }
     if (follow && pack) { fprintf(stderr, "Error: --pack-inputs is not supported with --follow (a followed file grows; a packed one is whole)\n"); return 1; }
     if (follow && render_gpu) { fprintf(stderr, "Error: --render-on-gpu is not supported with --follow (a followed file's batches continue a line count only the printer knows)\n"); return 1; }
@@ -965,6 +983,8 @@ int cmd_match(int argc, char** argv) {
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     if (pl.gather) matchy_multi_scanner_set_hit_lines(ms, true);
     if (tally) matchy_multi_scanner_set_tally(ms, true);
+    pl.whole_lines = whole_lines;
+    if (whole_lines) matchy_multi_scanner_set_whole_lines(ms, true);
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
     std::vector<std::string> paths;
     bool stdin_seen = false;
@@ -1048,7 +1068,7 @@ int cmd_match(int argc, char** argv) {
     if (follow) {
         matchy_scanner_t* fsc = matchy_scanner_create(db, mask, devs[0]);
         if (!fsc) fprintf(stderr, "Error: Failed to create the GPU scanner on device %d: %s\n", devs[0], matchy_amd_last_error());
-        else { matchy_scanner_set_line_context(fsc, pl.line_ctx); matchy_scanner_set_hit_lines(fsc, pl.gather); follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
+        else { matchy_scanner_set_line_context(fsc, pl.line_ctx); matchy_scanner_set_hit_lines(fsc, pl.gather); matchy_scanner_set_whole_lines(fsc, whole_lines); follow_inputs(pl, fsc, paths, stats, t); matchy_scanner_free(fsc); }
     }
     size_t failed = 0;
     for (char f : input_failed) failed += f != 0;
@@ -1065,6 +1085,8 @@ int cmd_match(int argc, char** argv) {
                 t.lines ? 100.0 * (double)t.lines_with_matches / (double)t.lines : 0.0);
         fprintf(stderr, "[INFO] Total matches: %s\n", fmt_num(t.matches).c_str());
         fprintf(stderr, "[INFO] Candidates tested: %s\n", fmt_num(t.candidates).c_str());
+        if (whole_lines) fprintf(stderr, "[INFO] Whole-line queries: %s (%s addresses, %s strings, %s not valid UTF-8)\n", fmt_num(pl.wl_counters[0].load()).c_str(),
+                                 fmt_num(pl.wl_counters[1].load()).c_str(), fmt_num(pl.wl_counters[2].load()).c_str(), fmt_num(pl.wl_counters[3].load()).c_str());
         if (tally && !tally_failed) fprintf(stderr, "[INFO] Distinct matched values: %s\n", fmt_num(tally_distinct).c_str());
         fprintf(stderr, "[INFO] Throughput: %.2f MB/s\n", secs > 0 ? (double)t.bytes / 1e6 / secs : 0.0);
         fprintf(stderr, "[INFO] Total time: %.2fs\n", secs);

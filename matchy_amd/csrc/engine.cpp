@@ -604,6 +604,7 @@ int Scanner::grid_for(uint32_t n_hint, uint32_t per_wg, int dflt, int max_per_cu
 }
 
 namespace {
+size_t grown_list(uint32_t n) { return (size_t)n + n / 4 + 1024; }   // a list regrown for a demand of n entries
 // point the parameters of a kernel at the candidate list `l` of a slice and at the counter `n` of its entries
 void point_at(TokParams& t, const DevBuf<Candidate>& l, uint32_t* n) { t.cands = l.p; t.cand_cap = (uint32_t)l.n; t.n_cand = n; }
 void point_at(LookupParams& p, const DevBuf<Candidate>& l, const uint32_t* n) { p.cands = l.p; p.cand_cap = (uint32_t)l.n; p.n_in = n; }
@@ -776,6 +777,7 @@ void Scanner::scan_device(const ScanRequest& rq, hipStream_t stream) {
     last_forked_ = false;
     spill_done_ = false;
     expect_chains_ = 0;
+    if (rq.whole_lines) { launch_whole_lines(rq, stream); return; }
     // MATCHY_AMD_NO_FORK=1 keeps everything on one stream.
     static const bool env_no_fork = getenv("MATCHY_AMD_NO_FORK") != nullptr;
     const bool no_fork = env_no_fork || !rq.fork;
@@ -1055,12 +1057,76 @@ void Scanner::launch_one_stream(hipStream_t stream) {
     }
 }
 
+// Whole-line mode (whole_lines.hip): count + prefix, scatter + classify, then the lookup passes over the candidate list — query k is
+// candidate k — all on the scan's stream. A list of addresses has a line every ~13 bytes and every line may hit: the candidate list
+// (and with it the arrays of the front end, the glob work list and the record arrays) is sized at len / 8 or for the lines of the
+// previous batch; a list that is still too short is counted past and regrown by fetch() like every other list.
+void Scanner::launch_whole_lines(const ScanRequest& rq, hipStream_t stream) {
+    if (!rq.lookup) throw ParamError{"whole-line mode needs a lookup scan"};
+    n_slices_ = 1;
+    early_glob_ = false;
+    if (!wl_) wl_ = std::make_unique<WholeLines>();
+    WholeLines& q = *wl_;
+    Work& w = work_[0];
+    w.ensure(rq.len);
+    const size_t want = std::max<size_t>(std::max<size_t>(4096, (size_t)rq.len / 8), grown_list(hint_.n_cand));
+    if (w.cands.n < want) w.cands.alloc(want);
+    if (w.hits.n < w.cands.n / 4) w.hits.alloc(w.cands.n / 4);   // each_list counts the hit list at a quarter of the candidates
+    if (ddb_->view.has_glob && w.glob_work.n < w.cands.n) w.glob_work.alloc(w.cands.n);   // string queries reach the glob pass unwalked
+    ensure_final(std::max(w.hits.n, w.cands.n), w.ids.n);
+    const uint32_t cap = (uint32_t)std::min<size_t>(w.cands.n, 0x7FFFFFFFu);
+    const uint32_t tiles = line_tiles(rq.len), chunks = line_chunks(tiles);
+    if (q.counts.n < tiles || !q.prefix.p) { q.counts.alloc((size_t)tiles + tiles / 4 + 1024); q.prefix.alloc(q.counts.n + 1); }
+    if (q.chunks.n < chunks) q.chunks.alloc((size_t)chunks + 64);
+    if (q.ends.n < cap) { q.ends.alloc(cap); q.invalid.alloc(cap); }
+    if (!q.ctr.p) { q.ctr.alloc(1); q.host.alloc(1); }
+    mirror_used_ = false;
+    if (rq.host_mirror) {
+        static const uint32_t mirror0 = getenv("MATCHY_AMD_MIRROR_RECS") ? (uint32_t)atoi(getenv("MATCHY_AMD_MIRROR_RECS")) : (1u << 20);
+        ensure_mirror(std::max(mirror0, 16u), std::max(mirror0 / 16, 16u));
+        if (compact_) mirror_c4_.ensure(std::max(mirror0, 16u));
+        mirror_used_ = true;
+    }
+    if (compact_ && c4_.n < final_.n) c4_.alloc(final_.n);
+    slice_params(0, rq, 0, rq.len + 1, launch_[0]);   // the lookup parameters; the extraction kernels' are not used
+    if (!counters_clean_) { MXY_HIP(hipMemsetAsync(counters_.p, 0, sizeof(ScanCounters) * MAX_SLICES, stream)); dom_preset_ = 0; }
+    counters_clean_ = false;
+    if (dom_preset_) MXY_HIP(hipMemsetD32Async((hipDeviceptr_t)&counters_.p->n_dom, 0, 1, stream));
+    dom_preset_ = 0; dom_want_ = 0;
+    WholeLineParams p{};
+    p.data = rq.ptr; p.len = rq.len; p.prefix = q.prefix.p; p.ends = q.ends.p; p.invalid = q.invalid.p;
+    p.cands = w.cands.p; p.cap = cap; p.wl = q.ctr.p; p.counters = counters_.p; p.pk = launch_[0].lp.pk;
+    MXY_HIP(hipMemsetAsync(q.invalid.p, 0, std::min<size_t>(cap, (size_t)rq.len + 1), stream));   // a batch has at most len lines
+    MXY_HIP(hipMemsetAsync(q.ctr.p, 0, sizeof(WholeLineCounters), stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_[0], stream));
+    MXY_HIP(line_index_build(rq.ptr, rq.len, q.counts.p, q.chunks.p, q.prefix.p, n_cu_, stream, nullptr));
+    if (profile_) MXY_HIP(hipEventRecord(ev_[1], stream));
+    launch_whole_lines_scatter(p, n_cu_, stream);
+    launch_whole_lines_classify(p, ddb_->view, n_cu_, stream);
+    if (profile_) { MXY_HIP(hipEventRecord(ev_[2], stream)); MXY_HIP(hipEventRecord(ev_[3], stream)); }
+    launch_lookup(launch_[0].lp, ddb_->view, n_cu_ * launch_[0].gm[2], stream);
+    MXY_HIP(hipMemcpyAsync(q.host.p, q.ctr.p, sizeof(WholeLineCounters), hipMemcpyDeviceToHost, stream));
+    if (profile_) MXY_HIP(hipEventRecord(ev_[4], stream));
+}
+
+void Scanner::arm_whole_lines(ScanRequest& rq, bool gz) {
+    rq.whole_lines = false;
+    if (!whole_lines_ || !rq.lookup) return;
+    const char* other = gz ? "gz scans" : (segments_ && segments_->pending()) ? "segments" : hit_lines_on_ ? "hit lines" : render_pending_ ? "rendered records" : nullptr;
+    if (other) {
+        set_segments(nullptr, 0);
+        set_render(nullptr);
+        throw ParamError{std::string("whole-line mode and ") + other + " cannot be combined"};
+    }
+    rq.whole_lines = true;
+}
+
 size_t sort_hits_temp_bytes(uint32_t n);
 hipError_t sort_hits(const FinalHit* fin, uint32_t n, unsigned long long* keys, uint32_t* vals, void* temp, size_t temp_bytes, FinalHit* out,
                      hipStream_t stream);
 
 namespace {
-size_t grown(uint32_t n) { return (size_t)n + n / 4 + 1024; }
+size_t grown(uint32_t n) { return grown_list(n); }
 }  // namespace
 
 // Every work list of slice `w` with the counter of its entries in `s`: f(name, capacity, count, grow), grow() reallocates the list for
@@ -1237,6 +1303,12 @@ void Scanner::report_counters(ScanOutput& out, bool trace) {
         }
         MXY_HIP(hipEventElapsedTime(&timing_.total_ms, ev_[0], ev_[4]));
         timing_.slices = ns;
+    }
+    if (last_.whole_lines && wl_) {   // the mode's counters came back behind the lookups; its intervals are the stream's
+        const WholeLineCounters& h = *wl_->host.p;
+        wl_->last[0] = h.queries; wl_->last[1] = h.address(); wl_->last[2] = h.string(); wl_->last[3] = h.invalid_utf8;
+        out.n_cand = h.address() + h.string();   // the queries that were looked up
+        if (profile_) { wl_->ms[0] = timing_.anchor_ms; wl_->ms[1] = timing_.validate_ms; wl_->ms[2] = timing_.lookup_ms; }
     }
 }
 
@@ -1558,6 +1630,11 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
     if (cand_bases) cand_bases->clear();
     if (fin) { fin->clear(); fin_ids->clear(); fin_offs->clear(); }
     if (fin_lines) fin_lines->clear();
+    // whole-line mode: the pieces are cut at newlines, which is the cut the mode needs; its counters add up over them
+    ScanRequest mode;
+    mode.lookup = lookup;
+    arm_whole_lines(mode);
+    uint64_t wl_sum[4] = {0, 0, 0, 0};
     // segmented scan: every piece gets the starts that intersect it, clamped and shifted; a piece ends at a line end, so the per-segment
     // figures of the pieces add up, and the indices go back into the caller's table
     std::vector<uint32_t> seg_all;
@@ -1624,6 +1701,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         ScanRequest rq;
         rq.ptr = staging_.p; rq.len = (uint32_t)n; rq.lookup = lookup; rq.lines = (line_ctx_ || hit_lines_on_) && lookup;
         rq.hit_lines = hit_lines_on_ && lookup && fin;
+        rq.whole_lines = mode.whole_lines;
         size_t seg_first = 0, seg_last = 0;
         if (!seg_all.empty()) {
             // the last segment that starts at or in front of the piece .. the last that starts inside it (the last piece: the last of all)
@@ -1686,12 +1764,14 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             if (part.seg_of_fin) for (size_t i = 0; i < part.n_fin; ++i) out.seg_of_own.push_back(part.seg_of_fin[i] + (uint32_t)seg_first);
         }
         out.lines += part.lines; out.n_cand += part.n_cand; out.n_hits += part.n_hits;
+        if (mode.whole_lines) for (int k = 0; k < 4; ++k) wl_sum[k] += wl_->last[k];
         for (int t = 0; t < IT_COUNT; ++t) out.by_type[t] += part.by_type[t];
         if (fin && part.n_fin) append_shifted(part.fin, part.n_fin, part.fin_ids, part.fin_offs, part.n_fin_ids, (uint32_t)pos, *fin, *fin_ids, *fin_offs);
         for (const Candidate& c : part.cands) { all_cands.push_back(c); if (cand_bases) cand_bases->push_back(pos); }
         pos += n;
     } while (pos < len);
     out.cands.swap(all_cands);
+    if (mode.whole_lines) for (int k = 0; k < 4; ++k) wl_->last[k] = wl_sum[k];
     if (out.has_hit_lines) {
         HitLinesView& v = out.hit_lines;
         v.text = out.hl_text_own.empty() ? nullptr : out.hl_text_own.data(); v.text_len = out.hl_text_own.size();

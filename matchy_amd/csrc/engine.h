@@ -16,6 +16,7 @@
 #include "result_layout.h"
 #include "scan_types.h"
 #include "segments.h"
+#include "whole_lines.h"
 
 namespace mxy {
 
@@ -173,6 +174,9 @@ struct ScanRequest {
     bool lines = false;        // line context: fetch() resolves every final record to its line (line_index.hip); needs `lookup`
     bool hit_lines = false;    // fetch() packs the distinct lines with a hit into one block (hit_lines.hip); needs `lines`
     bool render = false;       // fetch() renders the records as NDJSON on the device (render.hip); set by Scanner::arm_render
+    // every line of the batch is one query (whole_lines.hip) in place of extraction; needs `lookup`; set by Scanner::arm_whole_lines.
+    // The scan runs on ONE stream: `fork` and `slices` are ignored in this mode.
+    bool whole_lines = false;
 };
 
 // Moves the line records of a piece that starts `base` bytes and `line_base` lines into the whole (append_shifted for the line array).
@@ -255,6 +259,19 @@ public:
     GzInflate::Result gz_finish();
     // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
     void gz_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (gz_) gz_->timing(out_ms); }
+    // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
+    // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.
+    // scan_host reads the setting itself; the other entries of a lookup scan call arm_whole_lines in front of arm_segments, which sets
+    // rq.whole_lines and throws ParamError for a combination the mode does not have (segments, hit lines, rendered records; `gz`: the
+    // caller is a gz scan) — pending segment tables and render parameters are dropped then. Never set, nothing of it is allocated,
+    // launched or copied.
+    void set_whole_lines(bool on) { whole_lines_ = on; }
+    bool whole_lines() const { return whole_lines_; }
+    void arm_whole_lines(ScanRequest& rq, bool gz = false);
+    // queries, address queries, string queries and queries that are not valid UTF-8 of the last scan in the mode (scan_host: summed over its pieces)
+    void whole_lines_counters(uint64_t out[4]) const { for (int k = 0; k < 4; ++k) out[k] = wl_ ? wl_->last[k] : 0; }
+    // with set_profile: milliseconds of count + prefix, of scatter + classify, and of the lookups of the last scan in the mode
+    void whole_lines_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = wl_ ? wl_->ms[k] : 0; }
     // Distinct candidate texts (distinct.hip), for extractor handles: while on, a fetch with want_cands returns only the candidates whose
     // text this scanner has not returned since it was created or reset — the set lives in device memory across scans and pieces, and only
     // the survivors are copied back. Off (the default), nothing of it is allocated, launched or copied.
@@ -329,6 +346,7 @@ private:
     void launch_sliced(int ns, hipStream_t stream);
     void launch_forked(hipStream_t stream);
     void launch_one_stream(hipStream_t stream);
+    void launch_whole_lines(const ScanRequest& rq, hipStream_t stream);   // the schedule of a scan in whole-line mode
     void ensure_dom_stream();       // the fourth stream and its events, created at first use
     bool rare_possible() const { return (flags_ & (EX_HASHES | EX_BITCOIN | EX_ETHEREUM | EX_MONERO)) != 0; }
     // the steps of fetch(), in its order
@@ -388,6 +406,17 @@ private:
     std::unique_ptr<RenderParams> render_pending_;   // set_render, until arm_render takes it
     std::unique_ptr<NdjsonRender> render_;     // created by the first arm_render that arms a scan
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
+    // whole-line queries: the buffers of the front end (grown with the candidate list, reused between scans), created by the first scan in the mode
+    struct WholeLines {
+        DevBuf<uint32_t> counts, chunks, prefix, ends;
+        DevBuf<uint8_t> invalid;
+        DevBuf<WholeLineCounters> ctr;
+        PinnedBuf<WholeLineCounters> host;
+        uint64_t last[4] = {0, 0, 0, 0};
+        float ms[3] = {0, 0, 0};
+    };
+    bool whole_lines_ = false;
+    std::unique_ptr<WholeLines> wl_;
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
     bool tally_on_ = false;

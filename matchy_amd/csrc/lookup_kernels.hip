@@ -19,25 +19,8 @@
 namespace mxy {
 
 // ------------------------------------------------------------------------------------------------ stage B: lookups
-// SearchTree::lookup_v4 (tree:46-90): trie_v4 in device_shared.h (k_anchor uses it too). lookup_v6 (tree:92-125):
-__device__ bool trie_v6(const DevDb& db, const uint16_t seg[8], uint32_t& data_off, uint32_t& prefix) {
-    uint32_t node = 0;
-    for (int bi = 0; bi < 128; ++bi) {
-        uint2 nd = db.ip_nodes[node];
-        uint32_t bit = (seg[bi >> 4] >> (15 - (bi & 15))) & 1;
-        uint32_t rec = bit ? nd.y : nd.x;
-        if (rec == db.node_count) return false;
-        if (rec < db.node_count) node = rec;
-        else {
-            uint32_t off = rec - db.node_count;
-            if (off < 16) return false;
-            data_off = off - 16;
-            prefix = (uint32_t)bi + 1;
-            return true;
-        }
-    }
-    return false;
-}
+// SearchTree::lookup_v4 (tree:46-90) and lookup_v6 (tree:92-125): trie_v4 and trie_v6 in device_shared.h (k_anchor and the whole-line
+// front end use them too).
 
 // ---- case-insensitive databases: Rust str::to_lowercase on the device (texts with non-ASCII characters only; pure ASCII is
 // folded inline). The character data comes from matchy_amd/data/lowercase.bin (DevDb::lc_*).
@@ -503,68 +486,7 @@ __device__ __forceinline__ bool ac_touches_output(const DevDb& db, const DfaView
     return (any >> 31) != 0;
 }
 
-// One lane's hit -> dense FinalHit record (+ its pattern ids and data offsets), device copy and pinned host mirror: the body of
-// k_pack, also called straight from k_lookup for bulk scans (LookupParams::direct), where it overlaps the PCIe writes of
-// the records with the lookups instead of running as a kernel of its own afterwards. Wave-uniform call; `valid` marks the
-// lanes that hold a hit. Glob ids come from `globs` (k_lookup's own result list) or, when that is null, from pp.ids.
-// Pattern results follow Database::lookup_string_uncached (database.rs:911-981): the literal id counts only if it has a data
-// mapping, then the glob ids in ascending order; a literal without mapping and no glob is NotFound.
-__device__ __forceinline__ void pack_record(const PackParams& pp, bool valid, const Hit& h, const uint32_t* globs) {
-    const uint32_t lane = lane_id();
-    uint32_t nid = 0, lit_off = 0xFFFFFFFFu;
-    if (valid && h.kind == 3) {
-        if (h.a != 0xFFFFFFFFu && h.a < pp.n_lit) lit_off = pp.lit_offsets[h.a];
-        nid = (lit_off != 0xFFFFFFFFu ? 1u : 0u) + h.n_globs;
-        if (nid == 0) valid = false;
-    }
-    // dense slot for the record: one atomic per wave
-    const uint64_t vm = __ballot(valid);
-    if (vm == 0) return;
-    uint32_t slot0 = 0;
-    if (lane == 0) slot0 = atomicAdd(&pp.counters->n_final, (uint32_t)__popcll(vm));
-    slot0 = __builtin_amdgcn_readfirstlane(slot0);
-    const uint32_t slot = slot0 + (uint32_t)__popcll(vm & lanemask_lt());
-    // side-array space for pattern ids: wave exclusive scan of nid, one atomic per wave
-    uint32_t scan = valid ? nid : 0u;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)scan, off);
-        if ((int)lane >= off) scan += t;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)scan, 63);
-    uint32_t ids0 = 0;
-    if (total) {
-        if (lane == 0) ids0 = atomicAdd(&pp.counters->n_final_ids, total);
-        ids0 = __builtin_amdgcn_readfirstlane(ids0);
-    }
-    if (valid) {
-        const uint32_t my_ids = ids0 + scan - nid;
-        FinalHit f{};
-        f.start = h.start;
-        f.len_type = h.len_type;
-        f.kind = h.kind;
-        f.prefix_len = h.prefix_len;
-        if (h.kind == 2) f.value = h.a;
-        else {
-            f.n_ids = (uint16_t)nid;
-            f.value = my_ids;
-            uint32_t w = my_ids;
-            if (lit_off != 0xFFFFFFFFu) {
-                if (w < pp.out_ids_cap) { pp.out_ids[w] = h.a; pp.out_offs[w] = (long long)lit_off; }
-                if (w < pp.host_ids_cap) { pp.host_ids[w] = h.a; pp.host_offs[w] = (long long)lit_off; }
-                ++w;
-            }
-            for (uint32_t k = 0; k < h.n_globs; ++k, ++w) {
-                const uint32_t pid = globs ? globs[k] : ((h.ids_off + k < pp.ids_cap) ? pp.ids[h.ids_off + k] : 0u);
-                const long long go = pid < pp.n_glob ? (long long)pp.glob_offsets[pid] : -1ll;
-                if (w < pp.out_ids_cap) { pp.out_ids[w] = pid; pp.out_offs[w] = go; }
-                if (w < pp.host_ids_cap) { pp.host_ids[w] = pid; pp.host_offs[w] = go; }
-            }
-        }
-        if (slot < pp.out_cap) pp.out[slot] = f;
-        if (slot < pp.host_cap) pp.host_out[slot] = f;
-    }
-}
+// pack_record (one lane's hit -> its dense FinalHit record) is in device_shared.h: the whole-line front end writes records with it too.
 
 // Records without glob ids (IP hits, literal hits) collect in a per-lane LDS buffer and leave PEND_RECS per lane at a time:
 // the dense slots of the record array come from ONE returning atomic per flush instead of one per loop iteration. With a

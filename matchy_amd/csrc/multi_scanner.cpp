@@ -66,6 +66,7 @@ struct MultiScanner {
     bool line_ctx = false;   // matchy_multi_scanner_set_line_context: every worker sets its scanner to it before a scan
     bool hit_lines = false;  // matchy_multi_scanner_set_hit_lines: likewise
     bool tally = false, tally_ever = false;   // matchy_multi_scanner_set_tally: likewise
+    bool whole_lines = false;   // matchy_multi_scanner_set_whole_lines: likewise
     std::shared_ptr<const RenderSpec> render_next;   // matchy_multi_scanner_set_render: goes with the next batch submitted
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
@@ -85,7 +86,7 @@ struct MultiScanner {
         }
         for (;;) {
             MultiJob j;
-            bool want_lines = false, want_hit_lines = false, want_tally = false, touch_tally = false;
+            bool want_lines = false, want_hit_lines = false, want_tally = false, touch_tally = false, want_whole_lines = false;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return closing || !q.empty(); });
@@ -99,11 +100,13 @@ struct MultiScanner {
                 cv_space.notify_one();
                 want_lines = line_ctx; want_hit_lines = hit_lines;
                 want_tally = tally; touch_tally = tally_ever;
+                want_whole_lines = whole_lines;
             }
             MultiDone d;
             d.data = j.data; d.len = j.len; d.tag = j.tag; d.worker = w;
             if (!scanners[w]) scanners[w] = matchy_scanner_create(db, flags, devices[w]);
             std::string err;
+            if (scanners[w]) matchy_scanner_set_whole_lines(scanners[w], want_whole_lines);
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
             else if (!j.gz.empty()) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
                 // an armed pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
@@ -230,6 +233,16 @@ int32_t matchy_multi_scanner_set_tally(matchy_multi_scanner_t* h, bool enabled) 
     std::lock_guard<std::mutex> lk(ms->mu);
     ms->tally = enabled;
     if (enabled) ms->tally_ever = true;
+    return MATCHY_SUCCESS;
+}
+// Whole-line queries: the workers switch their scanners before a scan; the batches in flight keep the mode they were submitted
+// under only if nothing is pending when it changes, so the call needs the workers idle.
+int32_t matchy_multi_scanner_set_whole_lines(matchy_multi_scanner_t* h, bool enabled) {
+    if (!h) return MATCHY_ERROR_INVALID_PARAM;
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    if (ms->taken != ms->submitted) { set_error("matchy_multi_scanner_set_whole_lines: batches are still pending"); return MATCHY_ERROR_INVALID_PARAM; }
+    ms->whole_lines = enabled;
     return MATCHY_SUCCESS;
 }
 int32_t matchy_multi_scanner_tally_top(matchy_multi_scanner_t* h, size_t limit, matchy_tally_t* out) {

@@ -59,6 +59,7 @@ public:
     // bytes of the scan: starts[0] == 0, non-decreasing, every start <= len.
     void arm(size_t len);
     bool active() const { return active_; }
+    bool pending() const { return !pending_.empty(); }   // set() left a table that no scan has armed yet
     void off() { active_ = false; index_base_ = 0; }
     // The armed table goes to the device on `stream`, in front of the scan's kernels: the copy of a pageable vector is staged by the
     // runtime, and behind the scan it would sit on the critical path of the fetch.
