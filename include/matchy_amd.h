@@ -385,7 +385,7 @@ typedef struct matchy_render_params_t {
   uint64_t line_base;            /* lines in front of the buffer; or, with sources, */
   const uint64_t *line_bases;    /* one per segment (NULL = zeros) */
 } matchy_render_params_t;
-/* Arms the scanner's NEXT scan through matchy_scanner_scan, _scan_device, _submit_device or _scan_gz (the parameters are copied at the
+/* Arms the scanner's NEXT scan through matchy_scanner_scan, _scan_device, _submit_device, _scan_gz or _scan_gz_files (the parameters are copied at the
  * call; NULL disarms), and that scan consumes them whether it succeeds or not. A scan armed with parameters that do not fit it — line flags without
  * line context, `sources` for a scan without segments, n_sources other than the segment count — fails with MATCHY_ERROR_INVALID_PARAM
  * and a message; the scanner stays usable. matchy_scanner_scan renders piece by piece and hands out the blocks end to end. */
@@ -479,8 +479,29 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t *scanner, const uint8_t *packed,
  * MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
 int32_t matchy_scan_result_gz(const matchy_scan_result_t *result, const int32_t **status, size_t *n_members, const uint8_t **text,
                               size_t *text_len);
-/* With matchy_scanner_set_profile: milliseconds of the inflate kernel (the CRC is computed inside it), 0, and the seal kernel of the last gz scan. */
+/* With matchy_scanner_set_profile: milliseconds of the inflate kernel (the CRC is computed inside it), 0, and the seal kernel (of a scan
+ * of files: the verdict and seal kernels) of the last gz scan. */
 void matchy_scanner_get_gz_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* ---- gz scans of multi-member files (opt-in, beside matchy_scanner_scan_gz, which stays as it is): a gzip file may hold many members
+ * (RFC 1952: `cat a.gz b.gz`, `pigz -i`, appended chunks, BGZF), each an independent DEFLATE stream, so a file of k members is inflated
+ * by k waves. The table names whole FILES; the library finds the members of each on the host (a BGZF header names its member's length;
+ * otherwise the next 1f 8b 08 with no reserved FLG bit, XFL 0 / 2 / 4 and a header that parses, at least 10 bytes behind the body's
+ * start; FNAME and FCOMMENT of a later member count up to 256 bytes each, so the search is linear in the file's length whatever it
+ * holds). A cut is a guess the device verifies: a member must end exactly 8 bytes before its piece's end, and its CRC-32 and ISIZE must
+ * match — a false cut cannot yield pieces that are all OK. A file is OK when all its members are; otherwise it takes the status of its
+ * first member in stream order that is not, its whole region is overwritten with '\n', and the caller falls back (gzread) for it.
+ * Layout of the batch: segment i is FILE i. The members of a file lie end to end with nothing between them (a line may span two
+ * members); one '\n' — the separator — follows every file whose inflated length is not 0. Every capacity is the member's own ISIZE.
+ * `lines` and `bytes` count the OK files' own text. Fetch modes, line context, hit lines, rendered records, the tally, the refusal of
+ * whole-line queries and the errors are those of matchy_scanner_scan_gz; a file of 4 GiB or more is refused as well. */
+typedef struct matchy_gz_file_t { uint64_t offset; uint64_t len; } matchy_gz_file_t;
+int32_t matchy_scanner_scan_gz_files(matchy_scanner_t *scanner, const uint8_t *packed, size_t packed_len, const matchy_gz_file_t *files,
+                                     size_t n_files, uint32_t fetch_mode, bool want_text, matchy_scan_result_t *result);
+/* file_status: n_files values MATCHY_GZ_*; first_member: n_files + 1 values, the members of file f are [first_member[f],
+ * first_member[f + 1]) of what matchy_scan_result_gz hands out (per-member statuses, and the text as for any gz scan). Owned by the
+ * result. MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_gz_files(const matchy_scan_result_t *result, const int32_t **file_status, size_t *n_files,
+                                    const uint32_t **first_member);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -591,6 +612,10 @@ int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t *ms, const u
  * length — NULL and the length without want_text. */
 int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_member_t *members,
                                        size_t n, bool want_text, void *tag);
+/* The same for a pack of n_files gzip files of one member or many (matchy_scanner_scan_gz_files: `files` is copied). The batch from
+ * _next answers matchy_scan_result_gz_files as well. */
+int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_file_t *files,
+                                             size_t n_files, bool want_text, void *tag);
 /* NUMA node of a worker's GPU (-1 = unknown) and the number of CPUs its thread bound itself to (0 = not bound); valid once the
  * worker thread has started (after the first _next at the latest). */
 int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t *ms, size_t worker, int32_t *node, int32_t *cpus_bound);
@@ -612,7 +637,7 @@ void matchy_multi_scanner_set_line_context(matchy_multi_scanner_t *ms, bool enab
  * matchy_scan_result_hit_lines (and _lines), owned by the result, and render with text == NULL — a gz batch submitted without want_text
  * included, whose `data` is NULL. The merged results of matchy_multi_scanner_scan / _scan_file do not carry the block. */
 void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t *ms, bool enabled);
-/* Rendered records (matchy_scanner_set_render) on the multi-device scanner: arms the NEXT batch submitted (matchy_multi_scanner_submit / _submit_near / _submit_segments / _submit_gz;
+/* Rendered records (matchy_scanner_set_render) on the multi-device scanner: arms the NEXT batch submitted (matchy_multi_scanner_submit / _submit_near / _submit_segments / _submit_gz / _submit_gz_files;
  * copied at the call, NULL disarms). The worker that takes the batch arms its scanner; the batch's result owns the block. An armed gz
  * batch submitted without want_text is scanned with line context whatever matchy_multi_scanner_set_line_context says: its result carries
  * the lines with matches per segment, which nobody could count from a text that does not come back. A batch whose

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_set_segments", "matchy_scan_result_segments", "matchy_scan_result_to_ndjson_segments",
     "matchy_multi_scanner_submit_segments", "matchy_scanner_get_segment_timing",
     "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
+    "matchy_scanner_scan_gz_files", "matchy_scan_result_gz_files", "matchy_multi_scanner_submit_gz_files",
     "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
     "matchy_multi_scanner_set_hit_lines",
     "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
@@ -165,6 +166,11 @@ class _ScanSegment(C.Structure):
 class _GzMember(C.Structure):
     # matchy_gz_member_t (16 bytes)
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint32), ("out_len", C.c_uint32)]
+
+
+class _GzFile(C.Structure):
+    # matchy_gz_file_t (16 bytes)
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64)]
 
 
 class _TallyEntry(C.Structure):
@@ -313,6 +319,9 @@ def lib():
         "matchy_scan_result_gz": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_gz_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_multi_scanner_submit_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_bool, vp]),
+        "matchy_scanner_scan_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_gz_files": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
+        "matchy_multi_scanner_submit_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_bool, vp]),
         "matchy_scanner_set_whole_lines": (None, [vp, C.c_bool]),
         "matchy_scanner_whole_lines": (C.c_bool, [vp]),
         "matchy_scanner_get_whole_lines_counters": (None, [vp, C.POINTER(C.c_uint64)]),
@@ -709,6 +718,32 @@ class ScanResult:
         ga = self._gz_arrays()
         return None if ga is None else ga[3]
 
+    def _gz_file_arrays(self):
+        """(file status pointer, n_files, first_member pointer) of a gz scan of files, else None"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        st, n, fm = C.c_void_p(), C.c_size_t(), C.c_void_p()
+        if lib().matchy_scan_result_gz_files(C.byref(self._raw), C.byref(st), C.byref(n), C.byref(fm)) != 0:
+            return None
+        return st.value or 0, int(n.value), fm.value or 0
+
+    def gz_file_status(self):
+        """one GZ_* verdict per file of a gz scan of files (Scanner.scan_gz_files): OK, or the status of the file's first member in
+        stream order that is not; None for any other scan"""
+        ga = self._gz_file_arrays()
+        if ga is None:
+            return None
+        arr = C.cast(ga[0], C.POINTER(C.c_int32))
+        return [arr[i] for i in range(ga[1])]
+
+    def gz_first_member(self):
+        """n_files + 1 indices into gz_status(): the members of file f are [first[f], first[f + 1]); None for any other scan"""
+        ga = self._gz_file_arrays()
+        if ga is None:
+            return None
+        arr = C.cast(ga[2], C.POINTER(C.c_uint32))
+        return [arr[i] for i in range(ga[1] + 1)]
+
     def hit_lines(self):
         """the block of the distinct lines with a hit (Scanner.set_hit_lines; matchy_scan_result_hit_lines) as a dict: text (bytes),
         text_len, n_lines and the uint32 numpy arrays line_off (n_lines + 1), line_no, line_of_hit, line_of_ip4_hit (None where the
@@ -1024,6 +1059,17 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_scan_gz failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def scan_gz_files(self, blobs, want_text=False, fetch_mode=1) -> ScanResult:
+        """inflate the gzip files `blobs` (bytes each, of one member or many) on the GPU, one wave per member, and scan them as one batch
+        of len(blobs) segments (matchy_scanner_scan_gz_files). The result has .segments / .segment_of like a segmented scan,
+        gz_file_status() / gz_first_member(), and gz_status() / gz_text() per member."""
+        packed, table = _gz_pack_files(blobs)
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_gz_files(self._h, packed, len(packed), table, len(table), fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_gz_files failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
     def gz_timing_ms(self):
         out = (C.c_float * 3)()
         lib().matchy_scanner_get_gz_timing(self._h, out)
@@ -1074,6 +1120,16 @@ def _gz_pack(blobs, out_lens=None):
     for i, b in enumerate(blobs):
         table[i].offset, table[i].len = pos, len(b)
         table[i].out_len = int(out_lens[i]) if out_lens is not None and out_lens[i] else 0
+        pos += len(b)
+    return b"".join(bytes(b) for b in blobs), table
+
+
+def _gz_pack_files(blobs):
+    """the files end to end as one bytes object, and their matchy_gz_file_t table"""
+    table = (_GzFile * len(blobs))()
+    pos = 0
+    for i, b in enumerate(blobs):
+        table[i].offset, table[i].len = pos, len(b)
         pos += len(b)
     return b"".join(bytes(b) for b in blobs), table
 
@@ -1166,6 +1222,16 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_gz failed ({rc}): " + last_error())
 
+    def submit_gz_files_ptr(self, host_ptr: int, nbytes: int, files, want_text=False, tag: int = 0):
+        """queue a pack of gzip files of one member or many that lives at a host address: files = [(offset, len)]
+        (matchy_multi_scanner_submit_gz_files). next() then carries gz_file_status and gz_first_member as well"""
+        table = (_GzFile * len(files))()
+        for i, (off, ln) in enumerate(files):
+            table[i].offset, table[i].len = off, ln
+        rc = lib().matchy_multi_scanner_submit_gz_files(self._h, host_ptr, nbytes, table, len(files), bool(want_text), tag)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_gz_files failed ({rc}): " + last_error())
+
     def pending(self) -> int:
         return lib().matchy_multi_scanner_pending(self._h)
 
@@ -1213,6 +1279,8 @@ class MultiScanner:
         if gz is not None:   # a gz batch: data / len are the inflated text (NULL without want_text) and its length
             out["gz_status"] = gz
             out["text"] = C.string_at(b.data, b.len) if b.data else None
+            if r.gz_file_status() is not None:
+                out["gz_file_status"], out["gz_first_member"] = r.gz_file_status(), r.gz_first_member()
         r.close()
         return out
 

@@ -1181,15 +1181,15 @@ static_assert(MATCHY_GZ_OK == gz::GZ_OK && MATCHY_GZ_BAD_HEADER == gz::GZ_BAD_HE
                   MATCHY_GZ_BAD_CODES == gz::GZ_BAD_CODES && MATCHY_GZ_BAD_SYMBOL == gz::GZ_BAD_SYMBOL && MATCHY_GZ_BAD_DISTANCE == gz::GZ_BAD_DISTANCE &&
                   MATCHY_GZ_OVERFLOW == gz::GZ_OVERFLOW && MATCHY_GZ_SIZE_MISMATCH == gz::GZ_SIZE_MISMATCH && MATCHY_GZ_CRC_MISMATCH == gz::GZ_CRC_MISMATCH &&
                   MATCHY_GZ_TRAILING_DATA == gz::GZ_TRAILING_DATA, "k_gz_inflate writes MATCHY_GZ_* values directly");
-int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, uint32_t fetch_mode,
-                               bool want_text, matchy_scan_result_t* out) {
-    if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;
-    memset(out, 0, sizeof(*out));
-    if (!members || n == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
-    ScannerH* h = reinterpret_cast<ScannerH*>(s);
+static_assert(sizeof(GzFileIn) == sizeof(matchy_gz_file_t) && offsetof(GzFileIn, len) == offsetof(matchy_gz_file_t, len), "the plan reads matchy_gz_file_t directly");
+// one table is set: `members` (matchy_scanner_scan_gz: one member per file, member i is segment i) or `files` (matchy_scanner_scan_gz_files:
+// files of one member or many, file i is segment i)
+static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, const matchy_gz_file_t* files, size_t n,
+                            uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out) {
     try {
         { ScanRequest mode; mode.lookup = true; h->sc->arm_whole_lines(mode, true); }   // refused in front of the inflate kernels
-        const Scanner::GzBatch b = h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
+        const Scanner::GzBatch b = files ? h->sc->gz_inflate_files(packed, packed_len, reinterpret_cast<const GzFileIn*>(files), n)
+                                         : h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
         rq.ptr = b.text; rq.len = b.len; rq.lookup = true;
@@ -1218,12 +1218,40 @@ int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_
         auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
         in->has_gz = true;
         in->gz_status.assign(g.status, g.status + g.n);
+        if (g.file_status) {
+            in->has_gz_files = true;
+            in->gz_file_status.assign(g.file_status, g.file_status + g.n_files);
+            in->gz_first_member.assign(g.first_member, g.first_member + g.n_files + 1);
+        }
         in->gz_text = g.text; in->gz_text_len = g.text_len;
         if (sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, uint32_t fetch_mode,
+                               bool want_text, matchy_scan_result_t* out) {
+    if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    if (!members || n == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
+    return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, members, nullptr, n, fetch_mode, want_text, out);
+}
+int32_t matchy_scanner_scan_gz_files(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_file_t* files, size_t n_files, uint32_t fetch_mode,
+                                     bool want_text, matchy_scan_result_t* out) {
+    if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    if (!files || n_files == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz_files: no files"); return MATCHY_ERROR_INVALID_PARAM; }
+    return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, nullptr, files, n_files, fetch_mode, want_text, out);
+}
+int32_t matchy_scan_result_gz_files(const matchy_scan_result_t* r, const int32_t** file_status, size_t* n_files, const uint32_t** first_member) {
+    if (!r) return MATCHY_ERROR_INVALID_PARAM;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_gz_files) { set_error("matchy_scan_result_gz_files: the result was not produced by a gz scan of files"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (file_status) *file_status = in->gz_file_status.data();
+    if (n_files) *n_files = in->gz_file_status.size();
+    if (first_member) *first_member = in->gz_first_member.data();
+    return MATCHY_SUCCESS;
 }
 int32_t matchy_scan_result_gz(const matchy_scan_result_t* r, const int32_t** status, size_t* n_members, const uint8_t** text, size_t* text_len) {
     if (!r) return MATCHY_ERROR_INVALID_PARAM;

@@ -53,6 +53,10 @@ struct ScanResultInternal {
     std::vector<uint8_t> gz_text_own;
     const uint8_t* gz_text = nullptr;
     size_t gz_text_len = 0;
+    // gz scan of files (matchy_scan_result_gz_files): one verdict per file and the members of file f, [first_member[f], first_member[f + 1]); owned
+    bool has_gz_files = false;
+    std::vector<int32_t> gz_file_status;
+    std::vector<uint32_t> gz_first_member;
 };
 
 // hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top

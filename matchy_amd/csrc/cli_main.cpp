@@ -19,6 +19,8 @@
 // --gz-on-gpu sends runs of consecutive small .gz inputs to the GPU compressed (matchy_multi_scanner_submit_gz, inflate.hip): one wave
 // per file inflates them into the segments of one batch. A file the GPU does not accept (a second member, a damaged stream) is read the
 // old way right behind its pack, so it is scanned or reported exactly as without the flag; only its place in the output moves.
+// --gz-members (with --gz-on-gpu) extends the packs to .gz files of many small members that fit one batch
+// (matchy_multi_scanner_submit_gz_files): one wave per member, the file is one segment, the verdict is per file.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -67,6 +69,7 @@ int usage() {
             "                                0 = all; counted on the GPU; with --format summary nothing else is printed; not with --follow)\n"
             "               [--pack-inputs]   (consecutive small files share a batch and are told apart on the GPU; same output; not with --follow)\n"
             "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
+            "               [--gz-members]   (with --gz-on-gpu: a .gz file of many small members that fits one batch is inflated by one wave per member)\n"
             "               [--gather-lines]   (the lines with a match are gathered on the GPU and records are rendered from them: with --gz-on-gpu no inflated\n"
             "                                   text crosses the bus; same output; gains nothing where nearly every line matches)\n"
             "               [--render-on-gpu]   (with --format json: batches whose line numbers are known when they are submitted leave the GPU as\n"
@@ -305,7 +308,8 @@ struct Totals {
 
 // --gz-on-gpu: one file of a gz pack, and the statuses of a pack's members (MATCHY_GZ_*) on their way from the worker that scanned the
 // pack to the reader, which reads the members that failed the old way before it submits anything else
-struct GzFile { size_t input; uint64_t offset; uint32_t len, isize; };
+// --gz-members: isize is the sum over the file's members, of which there are `members`
+struct GzFile { size_t input; uint64_t offset; uint32_t len, isize; uint32_t members = 1; };
 struct GzVerdict {
     std::mutex mu;
     std::condition_variable cv;
@@ -369,6 +373,8 @@ struct MatchPipeline {
     // --gather-lines: the scanners run with hit lines. Every result carries the lines of its matches, the renderers read those (the
     // text of a gz pack stays on the device), and "Lines with matches" is the device's count as with line context.
     bool gather = false;
+    // --gz-members: gz packs hold files of one member or many (matchy_multi_scanner_submit_gz_files); the verdicts are per file
+    bool gz_members = false;
     // --render-on-gpu: a batch whose line bases are known when it is submitted leaves the device as finished NDJSON
     // (matchy_multi_scanner_set_render): every batch without line numbers; with them the packs (every segment is a whole file: base 0)
     // and an input's first batch. Any other batch, and a batch whose render status is not OK, goes through the host renderer as before.
@@ -434,9 +440,15 @@ struct MatchPipeline {
         int32_t rc;
         arm(*hb);
         if (!hb->gz.empty()) {   // the text comes back only where something is rendered from it
-            std::vector<matchy_gz_member_t> table;
-            for (const GzFile& g : hb->gz) table.push_back(matchy_gz_member_t{g.offset, g.len, 0});
-            rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather && !hb->armed, hb);
+            if (gz_members) {
+                std::vector<matchy_gz_file_t> table;
+                for (const GzFile& g : hb->gz) table.push_back(matchy_gz_file_t{g.offset, g.len});
+                rc = matchy_multi_scanner_submit_gz_files(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather && !hb->armed, hb);
+            } else {
+                std::vector<matchy_gz_member_t> table;
+                for (const GzFile& g : hb->gz) table.push_back(matchy_gz_member_t{g.offset, g.len, 0});
+                rc = matchy_multi_scanner_submit_gz(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather && !hb->armed, hb);
+            }
             if (rc != MATCHY_SUCCESS) { matchy_multi_scanner_set_render(ms, nullptr); hb->verdict->set(nullptr, 0); delete hb; return seq; }   // every member goes the old way
         }
         else if (hb->pack.empty()) rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg);
@@ -490,7 +502,8 @@ struct MatchPipeline {
             t.lines += r.lines; t.candidates += r.candidates; t.bytes += r.bytes; t.matches += r.n_hits;
             const int32_t* st = nullptr;
             size_t n_st = 0;
-            if (matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr) != MATCHY_SUCCESS) { st = nullptr; n_st = 0; d.ok = false; }
+            const int32_t got = gz_members ? matchy_scan_result_gz_files(&r, &st, &n_st, nullptr) : matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr);   // per file either way
+            if (got != MATCHY_SUCCESS) { st = nullptr; n_st = 0; d.ok = false; }
             b.verdict->set(st, n_st);
             if (!d.ok) { fprintf(stderr, "[ERROR] no gz statuses in the scan result of a gz pack: %s\n", matchy_amd_last_error()); return; }
         } else {
@@ -777,31 +790,59 @@ struct GzPacker {
     std::vector<GzFile> pending_files;
     size_t on_gpu = 0, packs = 0, on_host = 0;
     unsigned long long packed_bytes = 0, text_bytes = 0;
+    // --gz-members: a .gz input of many members is eligible when every member's compressed length and ISIZE are at most max_member and the
+    // file, compressed and inflated (the sum of its ISIZEs plus 1), fits one pack; the verdict on the pack is then per file
+    bool members = false;
+    std::vector<uint64_t> cuts;
+    size_t multi_files = 0, multi_members = 0;   // of the files the GPU accepted: those of more than one member, and their members
 
     GzPacker(MatchPipeline& p, const std::vector<std::string>& ps, std::vector<char>& rf, size_t bb) : pl(p), paths(ps), read_failed(rf) {
         batch_bytes = std::min<size_t>(bb, ((size_t)1 << 31) - ((size_t)1 << 20));   // a batch stays below 2^31 bytes
         max_member = batch_bytes / 4;
         if (const char* e = getenv("MATCHY_AMD_GZ_MAX_MEMBER")) max_member = std::min<size_t>(max_member, strtoull(e, nullptr, 10));
     }
+    // --gz-members: the members of the file p[0, size), whose first header parses. False: a member's compressed length or ISIZE above
+    // max_member, a piece with no room for its trailer, or more text than one pack holds — the file keeps the host path.
+    bool members_fit(const uint8_t* p, size_t size, uint32_t& n_members, uint32_t& isize) {
+        gz_split_members(p, size, cuts);
+        uint64_t sum = 0;
+        for (size_t k = 0; k < cuts.size(); ++k) {
+            const uint64_t at = cuts[k], len = (k + 1 < cuts.size() ? cuts[k + 1] : (uint64_t)size) - at;
+            uint64_t body = 0;
+            if (len > max_member || gz_parse_header(p + at, len, body) != GZ_PLAN_OK || len - body < 8) return false;
+            const uint8_t* t = p + at + len - 4;
+            const uint32_t is = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            if (is > max_member) return false;
+            sum += is;
+            if (sum + 1 > batch_bytes) return false;
+        }
+        n_members = (uint32_t)cuts.size(); isize = (uint32_t)sum;
+        return true;
+    }
     bool take(size_t i) {
         const std::string& path = paths[i];
         struct stat sb;
-        if (!pack_ends_with_gz(path) || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18 || (size_t)sb.st_size > max_member) return false;
+        // with --gz-members a file may be as large as a pack: its members are what must be small
+        if (!pack_ends_with_gz(path) || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18 || (size_t)sb.st_size > (members ? batch_bytes : max_member)) return false;
         const size_t size = (size_t)sb.st_size, at = buf.size();
         buf.resize(at + size);
         uint64_t body = 0;
         const bool whole = pack_read_file(path, buf.data() + at, size) == (long long)size;
         const bool parses = whole && gz_parse_header(buf.data() + at, size, body) == GZ_PLAN_OK && size - body >= 8;
         const uint8_t* t = buf.data() + at + size - 4;
-        const uint32_t isize = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-        if (!parses || isize > max_member) { buf.resize(at); return false; }
-        if (!files.empty() && text + isize + 1 > batch_bytes) {   // the file opens the next pack
+        uint32_t isize = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24, n_members = 1;
+        if (parses && members && !members_fit(buf.data() + at, size, n_members, isize)) { buf.resize(at); return false; }
+        // a file of one member is treated as it is without --gz-members
+        if (!parses || (n_members == 1 && (size > max_member || isize > max_member))) { buf.resize(at); return false; }
+        // the file opens the next pack: its text does not fit, or (--gz-members, where a file of many empty members may be as large as a
+        // pack and vouch for no text) its compressed bytes do not
+        if (!files.empty() && (text + isize + 1 > batch_bytes || (members && at + size > batch_bytes))) {
             const std::vector<uint8_t> file(buf.begin() + (long)at, buf.end());
             buf.resize(at);
             flush();
             buf = file;
         }
-        files.push_back(GzFile{i, buf.size() - size, (uint32_t)size, isize});
+        files.push_back(GzFile{i, buf.size() - size, (uint32_t)size, isize, n_members});
         text += (uint64_t)isize + 1;
         return true;
     }
@@ -811,7 +852,11 @@ struct GzPacker {
         pending->wait();
         for (size_t k = 0; k < pending_files.size(); ++k) {
             const GzFile& g = pending_files[k];
-            if (k < pending->status.size() && pending->status[k] == MATCHY_GZ_OK) { ++on_gpu; packed_bytes += g.len; text_bytes += g.isize; continue; }
+            if (k < pending->status.size() && pending->status[k] == MATCHY_GZ_OK) {
+                ++on_gpu; packed_bytes += g.len; text_bytes += g.isize;
+                if (g.members > 1) { ++multi_files; multi_members += g.members; }
+                continue;
+            }
             ++on_host;
             if (!read_input(pl, g.input, paths[g.input], batch_bytes)) read_failed[g.input] = 1;
         }
@@ -841,7 +886,7 @@ struct GzPacker {
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gather_lines = false, render_gpu = false, whole_lines = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -872,6 +917,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--input-line") input_line = true;
         else if (a == "--pack-inputs") pack = true;
         else if (a == "--gz-on-gpu") gz_gpu = true;
+        else if (a == "--gz-members") gz_members = true;
         else if (a == "--gather-lines") gather_lines = true;
         else if (a == "--render-on-gpu") render_gpu = true;
         else if (a == "--whole-lines") whole_lines = true;
@@ -886,6 +932,7 @@ int cmd_match(int argc, char** argv) {
     }
     if (pos.size() < 2) return usage();
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
+    if (gz_members && !gz_gpu) { fprintf(stderr, "Error: --gz-members needs --gz-on-gpu (it extends the gz packs to files of many members)\n"); return 1; }
     if (whole_lines) {
         // the mode has no extraction to configure, and the library refuses it together with segments, gz scans, hit lines and rendered records
         const char* other = !extractors.empty() ? "--extractors" : pack ? "--pack-inputs" : gz_gpu ? "--gz-on-gpu" : gather_lines ? "--gather-lines" : render_gpu ? "--render-on-gpu" : nullptr;
@@ -979,6 +1026,7 @@ int cmd_match(int argc, char** argv) {
     pl.line_ctx = line_numbers || input_line || (gz_gpu && format != "json");
     pl.input_line = input_line;
     pl.gather = gather_lines;
+    pl.gz_members = gz_members;
     pl.render_gpu = render_gpu;   // takes effect with --format json only (MatchPipeline::arm)
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
     if (pl.gather) matchy_multi_scanner_set_hit_lines(ms, true);
@@ -1004,6 +1052,7 @@ int cmd_match(int argc, char** argv) {
     pl.consumed.assign(paths.size(), -1);
     PackStats packed;
     GzPacker gzp(pl, paths, read_failed, batch_bytes);
+    gzp.members = gz_members;
     // an input that is not part of a plain pack: into the gz pack in hand, or, behind that pack and its verdict, the way it is read without the flags
     auto single = [&](size_t i) {
         if (gz_gpu && gzp.take(i)) return;
@@ -1099,6 +1148,7 @@ int cmd_match(int argc, char** argv) {
         if (pack) fprintf(stderr, "[INFO] Packed %zu inputs into %zu batches (%llu bytes of input in all)\n", packed.inputs, packed.packs, t.bytes);
         if (gz_gpu) fprintf(stderr, "[INFO] Inflated %zu .gz inputs on the GPU in %zu batches (%llu -> %llu bytes), %zu read on the host\n", gzp.on_gpu, gzp.packs,
                             gzp.packed_bytes, gzp.text_bytes, gzp.on_host);
+        if (gz_members) fprintf(stderr, "[INFO] gz members on the GPU: %zu in %zu multi-member files\n", gzp.multi_members, gzp.multi_files);
     }
     matchy_multi_scanner_free(ms);
     matchy_close(db);

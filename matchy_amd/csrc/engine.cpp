@@ -1550,13 +1550,20 @@ void Scanner::arm_segments(size_t len, hipStream_t stream, bool upload) {
 }
 
 // gz scans (inflate.h). The pass and the scan behind it share this scanner's own stream, so nothing waits on the host in between.
-Scanner::GzBatch Scanner::gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n) {
+template <class Launch>
+Scanner::GzBatch Scanner::gz_pass(Launch&& launch) {
     MXY_HIP(hipSetDevice(ddb_->device));
     host_stream_.create(hipStreamNonBlocking);
     if (!gz_) gz_ = std::make_unique<GzInflate>();
-    gz_->launch(packed, packed_len, members, n, n_cu_, profile_, host_stream_);
+    launch(*gz_);
     set_segments(gz_->starts().data(), gz_->starts().size());
     return GzBatch{gz_->device_text(), gz_->text_len(), host_stream_};
+}
+Scanner::GzBatch Scanner::gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n) {
+    return gz_pass([&](GzInflate& g) { g.launch(packed, packed_len, members, n, n_cu_, profile_, host_stream_); });
+}
+Scanner::GzBatch Scanner::gz_inflate_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files) {
+    return gz_pass([&](GzInflate& g) { g.launch_files(packed, packed_len, files, n_files, n_cu_, profile_, host_stream_); });
 }
 void Scanner::gz_queue_results(bool want_text) { gz_->queue_results(want_text, host_stream_); }
 GzInflate::Result Scanner::gz_finish() { return gz_->finish(); }

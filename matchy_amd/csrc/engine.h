@@ -255,6 +255,8 @@ public:
     // kernels, gz_finish behind the fetch. Never called, nothing of it is allocated, launched or copied.
     struct GzBatch { const uint8_t* text; uint32_t len; hipStream_t stream; };
     GzBatch gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n);
+    // the same for files of one member or many (GzInflate::launch_files): FILE i is segment i
+    GzBatch gz_inflate_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files);
     void gz_queue_results(bool want_text);
     GzInflate::Result gz_finish();
     // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
@@ -406,6 +408,8 @@ private:
     std::unique_ptr<RenderParams> render_pending_;   // set_render, until arm_render takes it
     std::unique_ptr<NdjsonRender> render_;     // created by the first arm_render that arms a scan
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
+    // what gz_inflate and gz_inflate_files share: device, stream, the pass; launch(GzInflate&) plans and queues; then the segment table
+    template <class Launch> GzBatch gz_pass(Launch&& launch);   // engine.cpp only
     // whole-line queries: the buffers of the front end (grown with the candidate list, reused between scans), created by the first scan in the mode
     struct WholeLines {
         DevBuf<uint32_t> counts, chunks, prefix, ends;

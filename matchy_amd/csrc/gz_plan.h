@@ -5,10 +5,14 @@
 // Layout: the members lie end to end in table order, one '\n' — the separator, not the input's — behind every non-empty member:
 // start[0] = 0, start[i + 1] = start[i] + cap[i] + 1 for cap[i] != 0 and start[i] otherwise. Segment i of the scan is member i; a member
 // whose header does not parse has capacity 0 and keeps its index.
+//
+// Multi-member files (gz_split_members, gz_plan_files, below): the members of a file are found on the host, laid out as ONE segment and
+// inflated by one wave each.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -33,8 +37,9 @@ struct GzPlan {
 };
 
 // RFC 1952 header of the file p[0, len): magic, CM = 8, no reserved FLG bit; FEXTRA, FNAME, FCOMMENT and FHCRC are skipped. Positions are
-// 64-bit throughout, so no field of the file can wrap one. `body` = offset of the first DEFLATE byte.
-inline int32_t gz_parse_header(const uint8_t* p, uint64_t len, uint64_t& body) {
+// 64-bit throughout, so no field of the file can wrap one. `body` = offset of the first DEFLATE byte. max_str: the most bytes FNAME and
+// FCOMMENT may have each, the NUL included; a longer one does not parse (the member split bounds what one candidate header can cost).
+inline int32_t gz_parse_header(const uint8_t* p, uint64_t len, uint64_t& body, uint64_t max_str = ~0ull) {
     body = 0;
     if (len < 10 || p[0] != 0x1F || p[1] != 0x8B || p[2] != 8) return GZ_PLAN_BAD_HEADER;
     const uint8_t flg = p[3];
@@ -49,9 +54,10 @@ inline int32_t gz_parse_header(const uint8_t* p, uint64_t len, uint64_t& body) {
     }
     for (const uint8_t bit : {(uint8_t)8, (uint8_t)16}) {   // FNAME, FCOMMENT: zero-terminated
         if (!(flg & bit)) continue;
-        while (pos < len && p[pos] != 0) ++pos;
-        if (pos >= len) return GZ_PLAN_BAD_HEADER;
-        ++pos;
+        const uint64_t room = std::min(len - pos, max_str);
+        const void* nul = room ? memchr(p + pos, 0, room) : nullptr;
+        if (!nul) return GZ_PLAN_BAD_HEADER;
+        pos = (uint64_t)((const uint8_t*)nul - p) + 1;
     }
     if (flg & 2) {   // FHCRC
         if (len - pos < 2) return GZ_PLAN_BAD_HEADER;
@@ -92,6 +98,128 @@ inline bool gz_plan(const uint8_t* packed, uint64_t packed_len, const GzMemberIn
     }
     plan.total = start;
     for (size_t i = 0; i < n; ++i) if (plan.members[i].status == GZ_PLAN_OK) plan.order.push_back((uint32_t)i);
+    std::stable_sort(plan.order.begin(), plan.order.end(), [&](uint32_t a, uint32_t b) { return plan.members[a].cap > plan.members[b].cap; });
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ multi-member files
+// A gzip file is a sequence of members (RFC 1952), each an independent DEFLATE stream: a file of k members can be inflated by k waves.
+// The host only GUESSES where the members start; the device verifies every guess with the rules it already has: a member must end
+// exactly 8 bytes before its piece's end (otherwise TRUNCATED or TRAILING_DATA) and its CRC-32 and ISIZE must match. If every piece of a
+// file is OK the pieces tile the file with complete valid members, which is what gzread would parse; a false cut cannot give all-OK pieces.
+
+// bit-identical to matchy_gz_file_t: a whole gzip file, of one member or many, at packed[offset, offset + len)
+struct GzFileIn { uint64_t offset, len; };
+
+// BSIZE of a BGZF member (FEXTRA subfield 'B','C' with SLEN 2: the member's length - 1) whose header p[0, len) has parsed; false: none
+inline bool gz_bgzf_bsize(const uint8_t* p, uint64_t len, uint32_t& bsize) {
+    if (len < 12 || !(p[3] & 4)) return false;
+    const uint64_t xlen = (uint64_t)p[10] | (uint64_t)p[11] << 8;
+    if (len - 12 < xlen) return false;
+    for (uint64_t at = 12, end = 12 + xlen; end - at >= 4;) {   // SI1 SI2 SLEN data
+        const uint64_t slen = (uint64_t)p[at + 2] | (uint64_t)p[at + 3] << 8;
+        if (end - at - 4 < slen) return false;
+        if (p[at] == 'B' && p[at + 1] == 'C' && slen == 2) { bsize = (uint32_t)p[at + 4] | (uint32_t)p[at + 5] << 8; return true; }
+        at += 4 + slen;
+    }
+    return false;
+}
+
+// Offsets where the members of the file p[0, len) start; the first is always 0. From one member to the next:
+//   BGZF member    BSIZE gives the length: the next member starts at pos + BSIZE + 1 — a cut only if that leaves room for the smallest
+//                  member in front of it, lies inside the file and a header parses there; otherwise this member keeps the rest.
+//   any other      the next position from body + 10 on (the smallest stream is 2 bytes, the trailer 8) with 1f 8b 08, no reserved FLG
+//                  bit, XFL 0, 2 or 4, and a header that parses.
+// A header the split looks for — every one but the file's first — may have at most GZ_SPLIT_MAX_STR bytes of FNAME and of FCOMMENT each,
+// the NUL included (a file name has at most 255): a candidate then costs a bounded number of bytes, and a hostile file of header patterns
+// with the FNAME bit and no NUL behind them costs time linear in its length. A real member with a longer string is not found, its
+// predecessor reports TRAILING_DATA and the file falls back, like one with an unusual XFL.
+// Every cut lies at least 20 bytes behind the one in front of it, so there are at most len / 18 of them; every read is inside p[0, len).
+constexpr uint64_t GZ_SPLIT_MAX_STR = 256;
+inline void gz_split_members(const uint8_t* p, uint64_t len, std::vector<uint64_t>& cuts) {
+    cuts.clear();
+    cuts.push_back(0);
+    static const uint8_t magic[3] = {0x1F, 0x8B, 8};
+    uint64_t pos = 0, body = 0;   // the member in hand and the length of its header
+    if (gz_parse_header(p, len, body) != GZ_PLAN_OK) return;
+    for (;;) {
+        uint32_t bsize = 0;
+        uint64_t next = 0, nb = 0;
+        if (gz_bgzf_bsize(p + pos, len - pos, bsize)) {
+            next = pos + bsize + 1;
+            if ((uint64_t)bsize + 1 < body + 10 || next >= len || gz_parse_header(p + next, len - next, nb, GZ_SPLIT_MAX_STR) != GZ_PLAN_OK) return;
+        } else {
+            for (uint64_t q = pos + body + 10;; ++q) {
+                const void* hit = q < len ? memmem(p + q, len - q, magic, 3) : nullptr;
+                if (!hit) return;
+                q = (uint64_t)((const uint8_t*)hit - p);
+                if (len - q < 10) return;   // no later position has room for a header either
+                if (!(p[q + 3] & 0xE0) && (p[q + 8] == 0 || p[q + 8] == 2 || p[q + 8] == 4) && gz_parse_header(p + q, len - q, nb, GZ_SPLIT_MAX_STR) == GZ_PLAN_OK) { next = q; break; }
+            }
+        }
+        cuts.push_back(next);
+        pos = next; body = nb;
+    }
+}
+
+// The plan of a pack of files. The members of a file lie end to end with NOTHING between them — a line may span two members, BGZF cuts
+// at arbitrary bytes — and one separator '\n' follows every file whose members' capacities sum to more than 0. Segment i of the scan is
+// FILE i: starts[i] is where its first member's text goes. Every capacity is the member's own ISIZE.
+struct GzFilesPlan {
+    std::vector<GzPlanned> members;        // of all files, in file order and stream order
+    std::vector<uint32_t> member_file;     // one per member: its file
+    std::vector<uint32_t> first_member;    // n_files + 1: the members of file f are [first_member[f], first_member[f + 1])
+    std::vector<uint32_t> starts, caps;    // one per file: the segment table of the scan, and the sum of its members' capacities
+    std::vector<uint32_t> order;           // as GzPlan::order, over the members of all files
+    uint64_t total = 0, packed_bytes = 0;
+};
+
+// False with `err` set: nothing to scan, a file outside packed[0, packed_len) or of 4 GiB or more, or a batch of 2^31 bytes or more.
+inline bool gz_plan_files(const uint8_t* packed, uint64_t packed_len, const GzFileIn* files, size_t n_files, GzFilesPlan& plan, std::string& err) {
+    plan = GzFilesPlan();
+    if (!files || n_files == 0) { err = "gz plan: no files"; return false; }
+    if (n_files > 0x7FFFFFFFull) { err = "gz plan: too many files"; return false; }
+    plan.starts.resize(n_files);
+    plan.caps.resize(n_files);
+    plan.first_member.resize(n_files + 1);
+    std::vector<uint64_t> cuts;
+    uint64_t start = 0;   // of the file; sums are 64-bit and tested after every member, so an ISIZE of 0xFFFFFFFF is refused, not wrapped
+    for (size_t f = 0; f < n_files; ++f) {
+        const GzFileIn& in = files[f];
+        if (in.offset > packed_len || in.len > packed_len - in.offset) { err = "gz plan: file " + std::to_string(f) + " lies outside the buffer"; return false; }
+        if (in.len > 0xFFFFFFFFull) { err = "gz plan: file " + std::to_string(f) + " has 4 GiB or more"; return false; }
+        const uint8_t* p = packed + in.offset;
+        gz_split_members(p, in.len, cuts);
+        if (plan.members.size() + cuts.size() > 0x7FFFFFFFull) { err = "gz plan: too many members"; return false; }
+        plan.first_member[f] = (uint32_t)plan.members.size();
+        plan.starts[f] = (uint32_t)start;
+        uint64_t cap_sum = 0;
+        for (size_t k = 0; k < cuts.size(); ++k) {
+            const uint64_t at = cuts[k], mlen = (k + 1 < cuts.size() ? cuts[k + 1] : in.len) - at;
+            GzPlanned g;
+            uint64_t body = 0;
+            g.status = gz_parse_header(p + at, mlen, body);
+            if (g.status == GZ_PLAN_OK && mlen - body < 8) g.status = GZ_PLAN_TRUNCATED;   // no room for the trailer
+            g.body = in.offset + at + body;
+            g.body_len = g.status == GZ_PLAN_OK ? (uint32_t)(mlen - body) : 0u;
+            g.cap = 0;
+            if (g.status == GZ_PLAN_OK) {
+                const uint8_t* t = p + at + mlen - 4;
+                g.cap = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            }
+            if (start + cap_sum + g.cap + 1 >= (1ull << 31)) { err = "gz plan: the inflated batch reaches 2^31 bytes in file " + std::to_string(f); return false; }
+            g.start = (uint32_t)(start + cap_sum);
+            cap_sum += g.cap;
+            plan.members.push_back(g);
+            plan.member_file.push_back((uint32_t)f);
+        }
+        plan.caps[f] = (uint32_t)cap_sum;
+        if (cap_sum) start += cap_sum + 1;
+        plan.packed_bytes += in.len;
+    }
+    plan.first_member[n_files] = (uint32_t)plan.members.size();
+    plan.total = start;
+    for (size_t i = 0; i < plan.members.size(); ++i) if (plan.members[i].status == GZ_PLAN_OK) plan.order.push_back((uint32_t)i);
     std::stable_sort(plan.order.begin(), plan.order.end(), [&](uint32_t a, uint32_t b) { return plan.members[a].cap > plan.members[b].cap; });
     return true;
 }

@@ -12,6 +12,7 @@
 namespace mxy {
 
 // One member as the kernels see it (GzPlanned without the host's status): body / body_len in the compressed buffer, start / cap in the batch.
+// reserved[0]: the member's file in a scan of multi-member files (gz_plan_files), 0 otherwise.
 struct GzMemberDev { uint64_t body; uint32_t body_len, start, cap, reserved[3]; };
 static_assert(sizeof(GzMemberDev) == 32, "one member per 32-byte sector");
 
@@ -25,6 +26,14 @@ hipError_t gz_inflate_launch(const uint8_t* packed, uint64_t packed_len, const G
                              uint32_t* counter, uint8_t* text, uint32_t text_len, int32_t* status, int grid, hipStream_t stream);
 // One wave per member: the separator '\n' behind an OK member, the whole region of a failed one (separator included) set to '\n'.
 hipError_t gz_seal_launch(const GzMemberDev* members, uint32_t n_members, const int32_t* status, uint8_t* text, uint32_t text_len, hipStream_t stream);
+// Multi-member files, behind k_gz_inflate in place of the seal. The members of file f are [first_member[f], first_member[f + 1]) and
+// carry f in reserved[0].
+// One wave per file: file_status[f] = OK if all its members are OK, otherwise the status of its first member in stream order that is not.
+hipError_t gz_file_verdict_launch(const uint32_t* first_member, uint32_t n_files, const int32_t* status, uint32_t n_members, int32_t* file_status, hipStream_t stream);
+// One wave per member, behind the verdict on the same stream: the region of a member of a failed file is set to '\n'; the last member of
+// a file whose capacity is not 0 writes the separator '\n' behind the file, in both outcomes.
+hipError_t gz_seal_files_launch(const GzMemberDev* members, uint32_t n_members, const uint32_t* first_member, uint32_t n_files, const int32_t* file_status,
+                                uint8_t* text, uint32_t text_len, hipStream_t stream);
 
 // The gz pass of a scanner (Scanner::gz_inflate): the plan of the pack in flight and the buffers of the pass, grown on demand and reused
 // between scans. A scan runs as launch() in front of the scan's kernels, queue_results() behind them on the same stream and finish()
@@ -33,6 +42,9 @@ class GzInflate {
 public:
     // Plans the pack (gz_plan.h), queues the copies of the compressed bytes and the tables, k_gz_inflate and k_gz_seal on `stream`.
     void launch(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n, int n_cu, bool profile, hipStream_t stream);
+    // The same for a pack of files of one member or many (gz_plan_files): k_gz_inflate over the members of all files, then
+    // k_gz_file_verdict and k_gz_seal_files. starts() are then the FILES' starts: file i is segment i.
+    void launch_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files, int n_cu, bool profile, hipStream_t stream);
     const uint8_t* device_text() const { return text_.p; }
     uint32_t text_len() const { return (uint32_t)plan_.total; }
     const std::vector<uint32_t>& starts() const { return plan_.starts; }
@@ -41,13 +53,23 @@ public:
     // Behind the wait for `stream`. status / text are BORROWED from the pinned blocks and valid until the next launch(); text is null
     // without want_text (text_len is the length of the batch either way). ok_bytes: inflated bytes of the OK members; not_input_nl: the '\n' bytes of the batch that are not the input's
     // (separators and the regions of failed members).
-    struct Result { const int32_t* status = nullptr; size_t n = 0; const uint8_t* text = nullptr; size_t text_len = 0; uint64_t ok_bytes = 0, not_input_nl = 0; };
+    // Behind launch_files() the accounting is per file (a file is OK when all its members are), and file_status (n_files values),
+    // first_member (n_files + 1) are set: borrowed like status.
+    struct Result { const int32_t* status = nullptr; size_t n = 0; const uint8_t* text = nullptr; size_t text_len = 0; uint64_t ok_bytes = 0, not_input_nl = 0;
+                    const int32_t* file_status = nullptr; size_t n_files = 0; const uint32_t* first_member = nullptr; };
     Result finish();
-    // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal of the last profiled launch()
+    // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal (k_gz_file_verdict + k_gz_seal_files
+    // behind launch_files) of the last profiled launch
     void timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = ms_[k]; }
 
 private:
-    GzPlan plan_;
+    void upload_and_inflate(const uint8_t* packed, size_t packed_len, int n_cu, bool profile, hipStream_t stream);
+    GzPlan plan_;                 // behind launch_files: members and order of all files, starts of the files
+    bool files_ = false;          // the launch in flight was launch_files
+    std::vector<uint32_t> first_member_host_, file_caps_;
+    DevBuf<uint32_t> first_member_;
+    DevBuf<int32_t> file_status_;
+    PinnedBuf<int32_t> file_status_pinned_;
     std::vector<GzMemberDev> members_host_;
     std::vector<int32_t> status_host_;
     DevBuf<uint8_t> packed_, text_;
