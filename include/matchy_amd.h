@@ -502,6 +502,38 @@ int32_t matchy_scanner_scan_gz_files(matchy_scanner_t *scanner, const uint8_t *p
  * result. MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
 int32_t matchy_scan_result_gz_files(const matchy_scan_result_t *result, const int32_t **file_status, size_t *n_files,
                                     const uint32_t **first_member);
+/* ---- gz windows (opt-in, beside the calls above, which stay as they are): a multi-member file that is LARGER than one batch is scanned
+ * as a chain of windows. A window is a run of consecutive whole members of ONE file; the caller cuts the file (it only needs member
+ * boundaries: BGZF names them, csrc/gz_plan.h gz_next_window walks them) so that the window's text plus the carry fits a batch, and
+ * scans the windows one after another. packed[0, packed_len) holds the window's whole members; the library splits it into members
+ * itself, as matchy_scanner_scan_gz_files does for a file, and the device verifies every cut. Layout of the batch:
+ *   [carry][member 0 text] ... [member m-1 text][one '\n' separator, only with MATCHY_WINDOW_LAST and carry + text > 0]
+ * Behind the inflate, verdict and seal kernels, k_gz_window_tail finds the window's last '\n', copies the partial line behind it — the
+ * carry, at most carry_cap bytes — out and overwrites it with '\n'; the caller hands that carry to the NEXT window, so every line lies
+ * whole in exactly one batch. The window is ONE segment that starts at 0. `bytes` is carry_len + inflated length - the new carry's length
+ * and `lines` the '\n' bytes of that range, so over the windows of a file they sum to the file's inflated length and line count.
+ * Outcomes:  members not all OK (matchy_scan_result_gz_files: one file): the whole batch, carry included, is '\n': no hit, bytes 0, an
+ *            empty carry; the caller falls back (gzread) from the bytes the windows in front consumed.
+ *            MATCHY_WINDOW_NO_LINE_END: more than carry_cap bytes lie behind the window's last '\n' (or the window is longer than
+ *            carry_cap and has none): the same — all '\n', no hit, bytes 0, empty carry.
+ *            MATCHY_WINDOW_LAST: nothing is cut; the last partial line is scanned, the carry is empty.
+ * The result also answers matchy_scan_result_gz_files (one file), matchy_scan_result_gz (member statuses; the text, carry included) and
+ * matchy_scan_result_segments (one segment). Windows of one file are serial: each needs the carry of the one in front. Fetch modes, line
+ * context, hit lines, rendered records, the tally and the refusal of whole-line queries are those of matchy_scanner_scan_gz.
+ * MATCHY_ERROR_INVALID_PARAM with a message, and a scanner that stays usable: NULL handles, packed_len == 0, carry_len > carry_cap,
+ * carry == NULL with carry_len > 0, a batch that reaches 2^31 bytes (the carry counted), unknown flag bits. */
+#define MATCHY_WINDOW_LAST 1u          /* flags: the file ends with this window */
+#define MATCHY_WINDOW_OK 0
+#define MATCHY_WINDOW_NO_LINE_END 1    /* more than carry_cap bytes behind the window's last '\n' (or none at all in a window longer than carry_cap) */
+typedef struct matchy_gz_window_t { const uint8_t *carry; uint32_t carry_len, carry_cap, flags; } matchy_gz_window_t;
+int32_t matchy_scanner_scan_gz_window(matchy_scanner_t *scanner, const uint8_t *packed, size_t packed_len, const matchy_gz_window_t *window,
+                                      uint32_t fetch_mode, bool want_text, matchy_scan_result_t *result);
+/* window_status: MATCHY_WINDOW_*; carry / carry_len: the bytes behind the window's last '\n', owned by the result (valid until it is
+ * freed). MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_gz_window(const matchy_scan_result_t *result, int32_t *window_status, const uint8_t **carry, size_t *carry_len);
+/* matchy_scanner_get_gz_timing behind a window scan (out_ms[2] then includes k_gz_window_tail), and that kernel's own milliseconds as
+ * out_ms[3]. */
+void matchy_scanner_get_gz_window_timing(const matchy_scanner_t *scanner, float out_ms[4]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -616,6 +648,11 @@ int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t *ms, const uint8_t
  * _next answers matchy_scan_result_gz_files as well. */
 int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_file_t *files,
                                              size_t n_files, bool want_text, void *tag);
+/* The same for one window of a large multi-member file (matchy_scanner_scan_gz_window: the carry is copied at the call, the packed
+ * bytes stay the caller's). The batch from _next answers matchy_scan_result_gz_window as well. The windows of one file are serial: the
+ * caller takes a window's batch, and with it the carry, before it submits the next. */
+int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_window_t *window,
+                                              bool want_text, void *tag);
 /* NUMA node of a worker's GPU (-1 = unknown) and the number of CPUs its thread bound itself to (0 = not bound); valid once the
  * worker thread has started (after the first _next at the latest). */
 int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t *ms, size_t worker, int32_t *node, int32_t *cpus_bound);

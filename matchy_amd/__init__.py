@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_submit_segments", "matchy_scanner_get_segment_timing",
     "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
     "matchy_scanner_scan_gz_files", "matchy_scan_result_gz_files", "matchy_multi_scanner_submit_gz_files",
+    "matchy_scanner_scan_gz_window", "matchy_scan_result_gz_window", "matchy_multi_scanner_submit_gz_window", "matchy_scanner_get_gz_window_timing",
     "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
     "matchy_multi_scanner_set_hit_lines",
     "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
@@ -166,6 +167,17 @@ class _ScanSegment(C.Structure):
 class _GzMember(C.Structure):
     # matchy_gz_member_t (16 bytes)
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint32), ("out_len", C.c_uint32)]
+
+
+# MATCHY_WINDOW_*: the flag and the statuses of a gz window (Scanner.scan_gz_window, ScanResult.gz_window)
+WINDOW_LAST = 1
+WINDOW_OK, WINDOW_NO_LINE_END = 0, 1
+GZ_WINDOW_TAIL_BLOCK = 4096   # csrc/inflate.h GZ_TAIL_BLOCK: the bytes k_gz_window_tail looks at per turn of its walk
+
+
+class _GzWindow(C.Structure):
+    # matchy_gz_window_t (24 bytes)
+    _fields_ = [("carry", C.c_void_p), ("carry_len", C.c_uint32), ("carry_cap", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class _GzFile(C.Structure):
@@ -322,6 +334,10 @@ def lib():
         "matchy_scanner_scan_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
         "matchy_scan_result_gz_files": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
         "matchy_multi_scanner_submit_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_bool, vp]),
+        "matchy_scanner_scan_gz_window": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzWindow), C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_gz_window": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_multi_scanner_submit_gz_window": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzWindow), C.c_bool, vp]),
+        "matchy_scanner_get_gz_window_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_scanner_set_whole_lines": (None, [vp, C.c_bool]),
         "matchy_scanner_whole_lines": (C.c_bool, [vp]),
         "matchy_scanner_get_whole_lines_counters": (None, [vp, C.POINTER(C.c_uint64)]),
@@ -718,6 +734,16 @@ class ScanResult:
         ga = self._gz_arrays()
         return None if ga is None else ga[3]
 
+    def gz_window(self):
+        """(WINDOW_* status, carry bytes) of a gz scan of a window (Scanner.scan_gz_window): the carry is the partial line behind the
+        window's last newline, to be handed to the next window; None for any other scan"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        st, p, n = C.c_int32(0), C.c_void_p(), C.c_size_t(0)
+        if lib().matchy_scan_result_gz_window(C.byref(self._raw), C.byref(st), C.byref(p), C.byref(n)) != 0:
+            return None
+        return st.value, (C.string_at(p.value, n.value) if n.value else b"")
+
     def _gz_file_arrays(self):
         """(file status pointer, n_files, first_member pointer) of a gz scan of files, else None"""
         if self._raw is None:
@@ -1070,6 +1096,23 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_scan_gz_files failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def scan_gz_window(self, blob, carry=b"", carry_cap=1 << 20, last=False, want_text=False, fetch_mode=1) -> ScanResult:
+        """inflate and scan one window of a multi-member gzip file that is larger than a batch (matchy_scanner_scan_gz_window): `blob` are
+        the window's whole members, `carry` the partial line the window in front left behind. The result has gz_window() -> (status,
+        carry for the next window), one segment, gz_file_status() (one file), and gz_status() / gz_text() (the carry included)."""
+        keep = C.create_string_buffer(bytes(carry), len(carry)) if carry else None
+        w = _GzWindow(C.addressof(keep) if keep is not None else None, len(carry), carry_cap, WINDOW_LAST if last else 0)
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_gz_window(self._h, bytes(blob), len(blob), C.byref(w), fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_gz_window failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
+    def gz_window_timing_ms(self):
+        out = (C.c_float * 4)()
+        lib().matchy_scanner_get_gz_window_timing(self._h, out)
+        return dict(inflate=out[0], crc=out[1], seal=out[2], tail=out[3])
+
     def gz_timing_ms(self):
         out = (C.c_float * 3)()
         lib().matchy_scanner_get_gz_timing(self._h, out)
@@ -1232,6 +1275,15 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_gz_files failed ({rc}): " + last_error())
 
+    def submit_gz_window_ptr(self, host_ptr: int, nbytes: int, carry=b"", carry_cap=1 << 20, last=False, want_text=False, tag: int = 0):
+        """queue one window of a large multi-member gzip file whose members live at a host address (matchy_multi_scanner_submit_gz_window;
+        the carry is copied). next() then carries window_status and carry as well"""
+        keep = C.create_string_buffer(bytes(carry), len(carry)) if carry else None
+        w = _GzWindow(C.addressof(keep) if keep is not None else None, len(carry), carry_cap, WINDOW_LAST if last else 0)
+        rc = lib().matchy_multi_scanner_submit_gz_window(self._h, host_ptr, nbytes, C.byref(w), bool(want_text), tag)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_gz_window failed ({rc}): " + last_error())
+
     def pending(self) -> int:
         return lib().matchy_multi_scanner_pending(self._h)
 
@@ -1281,6 +1333,8 @@ class MultiScanner:
             out["text"] = C.string_at(b.data, b.len) if b.data else None
             if r.gz_file_status() is not None:
                 out["gz_file_status"], out["gz_first_member"] = r.gz_file_status(), r.gz_first_member()
+            if r.gz_window() is not None:
+                out["window_status"], out["carry"] = r.gz_window()
         r.close()
         return out
 

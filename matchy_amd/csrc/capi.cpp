@@ -369,6 +369,15 @@ void attach_segments(Scanner& sc, const ScanOutput& so, bool device, bool owned,
 }  // namespace
 
 int mxy::capi::default_device_of(const matchy_t* db) { return reinterpret_cast<const Db*>(db)->default_device; }
+const char* mxy::capi::gz_window_refusal(const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* w) {
+    if (!packed || packed_len == 0) return "no members (packed_len is 0)";
+    if (!w) return "no window";
+    if (w->flags & ~MATCHY_WINDOW_LAST) return "unknown flag bits";
+    if (w->carry_len > w->carry_cap) return "carry_len is above carry_cap";
+    if (!w->carry && w->carry_len) return "carry is NULL with a carry_len above 0";
+    if (w->carry_cap >= (1u << 31) || packed_len > 0xFFFFFFFFull) return "the batch reaches 2^31 bytes";
+    return nullptr;
+}
 
 // hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
 namespace {
@@ -1183,13 +1192,15 @@ static_assert(MATCHY_GZ_OK == gz::GZ_OK && MATCHY_GZ_BAD_HEADER == gz::GZ_BAD_HE
                   MATCHY_GZ_TRAILING_DATA == gz::GZ_TRAILING_DATA, "k_gz_inflate writes MATCHY_GZ_* values directly");
 static_assert(sizeof(GzFileIn) == sizeof(matchy_gz_file_t) && offsetof(GzFileIn, len) == offsetof(matchy_gz_file_t, len), "the plan reads matchy_gz_file_t directly");
 // one table is set: `members` (matchy_scanner_scan_gz: one member per file, member i is segment i) or `files` (matchy_scanner_scan_gz_files:
-// files of one member or many, file i is segment i)
+// files of one member or many, file i is segment i), or `window` (matchy_scanner_scan_gz_window: packed[0, packed_len) are the whole members of
+// one window, which is segment 0)
 static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, const matchy_gz_file_t* files, size_t n,
-                            uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out) {
+                            uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out, const matchy_gz_window_t* window = nullptr) {
     try {
         { ScanRequest mode; mode.lookup = true; h->sc->arm_whole_lines(mode, true); }   // refused in front of the inflate kernels
-        const Scanner::GzBatch b = files ? h->sc->gz_inflate_files(packed, packed_len, reinterpret_cast<const GzFileIn*>(files), n)
-                                         : h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
+        const Scanner::GzBatch b = window ? h->sc->gz_inflate_window(packed, packed_len, window->carry, window->carry_len, window->carry_cap, (window->flags & MATCHY_WINDOW_LAST) != 0)
+                                   : files ? h->sc->gz_inflate_files(packed, packed_len, reinterpret_cast<const GzFileIn*>(files), n)
+                                           : h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
         const bool sorted = (fetch_mode & 2) != 0;
         ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
         rq.ptr = b.text; rq.len = b.len; rq.lookup = true;
@@ -1225,6 +1236,11 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
         }
         in->gz_text = g.text; in->gz_text_len = g.text_len;
         if (sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
+        if (g.window) {   // the carry is the next window's input while this result may already be freed by then: always owned
+            in->has_gz_window = true;
+            in->gz_window_status = g.window_status;
+            in->gz_carry.assign(g.carry, g.carry + g.carry_len);
+        }
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1243,6 +1259,26 @@ int32_t matchy_scanner_scan_gz_files(matchy_scanner_t* s, const uint8_t* packed,
     memset(out, 0, sizeof(*out));
     if (!files || n_files == 0 || (!packed && packed_len)) { set_error("matchy_scanner_scan_gz_files: no files"); return MATCHY_ERROR_INVALID_PARAM; }
     return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, nullptr, files, n_files, fetch_mode, want_text, out);
+}
+static_assert(MATCHY_WINDOW_OK == GZ_WINDOW_OK && MATCHY_WINDOW_NO_LINE_END == GZ_WINDOW_NO_LINE_END, "k_gz_window_tail writes MATCHY_WINDOW_* values directly");
+int32_t matchy_scanner_scan_gz_window(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window, uint32_t fetch_mode, bool want_text,
+                                      matchy_scan_result_t* out) {
+    if (!s || !out) { set_error("matchy_scanner_scan_gz_window: no scanner or no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    memset(out, 0, sizeof(*out));
+    if (const char* why = gz_window_refusal(packed, packed_len, window)) { set_error(std::string("matchy_scanner_scan_gz_window: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, nullptr, nullptr, 1, fetch_mode, want_text, out, window);
+}
+int32_t matchy_scan_result_gz_window(const matchy_scan_result_t* r, int32_t* window_status, const uint8_t** carry, size_t* carry_len) {
+    if (!r) { set_error("matchy_scan_result_gz_window: no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_gz_window) { set_error("matchy_scan_result_gz_window: the result was not produced by a gz scan of a window"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (window_status) *window_status = in->gz_window_status;
+    if (carry) *carry = in->gz_carry.data();
+    if (carry_len) *carry_len = in->gz_carry.size();
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_gz_window_timing(const matchy_scanner_t* s, float out[4]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_window_timing(out);
 }
 int32_t matchy_scan_result_gz_files(const matchy_scan_result_t* r, const int32_t** file_status, size_t* n_files, const uint32_t** first_member) {
     if (!r) return MATCHY_ERROR_INVALID_PARAM;

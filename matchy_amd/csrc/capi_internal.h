@@ -13,6 +13,8 @@ namespace capi {
 
 void set_error(const std::string& e);           // the calling thread's matchy_amd_last_error()
 int default_device_of(const matchy_t* db);      // the HIP device a handle's scanners use when none is named
+// why matchy_scanner_scan_gz_window / matchy_multi_scanner_submit_gz_window refuse these arguments; nullptr: they do not
+const char* gz_window_refusal(const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window);
 
 struct ScanResultInternal {
     std::vector<matchy_scan_hit_t> hits;
@@ -57,6 +59,10 @@ struct ScanResultInternal {
     bool has_gz_files = false;
     std::vector<int32_t> gz_file_status;
     std::vector<uint32_t> gz_first_member;
+    // gz scan of a window (matchy_scan_result_gz_window): MATCHY_WINDOW_* and the partial line behind the window's last '\n'; owned
+    bool has_gz_window = false;
+    int32_t gz_window_status = 0;
+    std::vector<uint8_t> gz_carry;
 };
 
 // hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top

@@ -21,6 +21,8 @@
 // old way right behind its pack, so it is scanned or reported exactly as without the flag; only its place in the output moves.
 // --gz-members (with --gz-on-gpu) extends the packs to .gz files of many small members that fit one batch
 // (matchy_multi_scanner_submit_gz_files): one wave per member, the file is one segment, the verdict is per file.
+// --gz-windows (with both) extends that to multi-member .gz files LARGER than a batch: the mapped file goes out as a chain of windows of
+// whole members (matchy_multi_scanner_submit_gz_window), one at a time; every window hands the partial line behind its last '\n' to the next.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -70,6 +72,7 @@ int usage() {
             "               [--pack-inputs]   (consecutive small files share a batch and are told apart on the GPU; same output; not with --follow)\n"
             "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
             "               [--gz-members]   (with --gz-on-gpu: a .gz file of many small members that fits one batch is inflated by one wave per member)\n"
+            "               [--gz-windows]   (with --gz-on-gpu --gz-members: a multi-member .gz file larger than a batch is scanned as a chain of windows of whole members)\n"
             "               [--gather-lines]   (the lines with a match are gathered on the GPU and records are rendered from them: with --gz-on-gpu no inflated\n"
             "                                   text crosses the bus; same output; gains nothing where nearly every line matches)\n"
             "               [--render-on-gpu]   (with --format json: batches whose line numbers are known when they are submitted leave the GPU as\n"
@@ -315,6 +318,10 @@ struct GzVerdict {
     std::condition_variable cv;
     bool done = false;
     std::vector<int32_t> status;   // empty with done set: the pack was not scanned at all, every member is read the old way
+    // --gz-windows: MATCHY_WINDOW_*, the carry for the next window and the bytes of the file this window consumed; written before set()
+    int32_t window_status = MATCHY_WINDOW_OK;
+    std::vector<uint8_t> carry;
+    uint64_t bytes = 0;
     void set(const int32_t* st, size_t n) {
         { std::lock_guard<std::mutex> lk(mu); if (done) return; status.assign(st, st + n); done = true; }
         cv.notify_all();
@@ -337,6 +344,9 @@ struct Batch { size_t input = 0; Bytes own; const uint8_t* ptr = nullptr; size_t
                // --gz-on-gpu: the gzip files of a gz pack (`ptr` holds them compressed, end to end), one segment each, and where the
                // reader waits for the verdict on them
                std::vector<GzFile> gz; std::shared_ptr<GzVerdict> verdict;
+               // --gz-windows: the batch is one window of the file gz[0] (`ptr` holds its whole members, in the file's mapping) behind `carry`;
+               // it is ONE segment like a pack of one file, but its lines count on from those of the windows in front
+               bool window = false, window_last = false; std::vector<uint8_t> carry; uint32_t carry_cap = 0;
                bool armed = false; };   // --render-on-gpu: the batch was submitted with matchy_multi_scanner_set_render
 // what a batch contributes to the output: `text` / `text_len` is the buffer matchy_scan_result_to_ndjson returned (written to stdout as
 // it is and released by the printer: 200 bytes per match are not copied again on the way), `out` what --follow builds from it
@@ -396,12 +406,12 @@ struct MatchPipeline {
         if (!render_gpu || !json) return;
         const bool segmented = !b.pack.empty() || !b.gz.empty();
         bool first = true;
-        if (!segmented) {
+        if (!segmented || b.window) {   // a window is a batch of its input like a stream batch: only the first has line base 0
             if (input_started.size() <= b.input) input_started.resize(b.input + 1, 0);
             first = !input_started[b.input];
             input_started[b.input] = 1;
         }
-        if (line_ctx && !segmented && !first) return;
+        if (line_ctx && (!segmented || b.window) && !first) return;
         matchy_render_params_t p;
         memset(&p, 0, sizeof(p));
         p.flags = line_ctx ? (MATCHY_RENDER_LINE_NUMBERS | (input_line ? MATCHY_RENDER_INPUT_LINE : 0u)) : 0u;
@@ -440,7 +450,10 @@ struct MatchPipeline {
         int32_t rc;
         arm(*hb);
         if (!hb->gz.empty()) {   // the text comes back only where something is rendered from it
-            if (gz_members) {
+            if (hb->window) {
+                const matchy_gz_window_t w{hb->carry.data(), (uint32_t)hb->carry.size(), hb->carry_cap, hb->window_last ? MATCHY_WINDOW_LAST : 0u};
+                rc = matchy_multi_scanner_submit_gz_window(ms, hb->ptr, hb->len, &w, json && !gather && !hb->armed, hb);
+            } else if (gz_members) {
                 std::vector<matchy_gz_file_t> table;
                 for (const GzFile& g : hb->gz) table.push_back(matchy_gz_file_t{g.offset, g.len});
                 rc = matchy_multi_scanner_submit_gz_files(ms, hb->ptr, hb->len, table.data(), table.size(), json && !gather && !hb->armed, hb);
@@ -504,6 +517,12 @@ struct MatchPipeline {
             size_t n_st = 0;
             const int32_t got = gz_members ? matchy_scan_result_gz_files(&r, &st, &n_st, nullptr) : matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr);   // per file either way
             if (got != MATCHY_SUCCESS) { st = nullptr; n_st = 0; d.ok = false; }
+            if (b.window && got == MATCHY_SUCCESS) {
+                const uint8_t* carry = nullptr;
+                size_t n_carry = 0;
+                if (matchy_scan_result_gz_window(&r, &b.verdict->window_status, &carry, &n_carry) == MATCHY_SUCCESS) { b.verdict->carry.assign(carry, carry + n_carry); b.verdict->bytes = r.bytes; }
+                else { st = nullptr; n_st = 0; d.ok = false; }
+            }
             b.verdict->set(st, n_st);
             if (!d.ok) { fprintf(stderr, "[ERROR] no gz statuses in the scan result of a gz pack: %s\n", matchy_amd_last_error()); return; }
         } else {
@@ -563,7 +582,7 @@ struct MatchPipeline {
         if (b.pack.empty() && b.gz.empty()) rc = matchy_scan_result_to_ndjson_lines(sc, &r, data, sources[b.input].c_str(), base, input_line, &text, &n);
         else {
             const std::vector<const char*> src = pack_sources(b);
-            const std::vector<uint64_t> bases(src.size(), 0);
+            const std::vector<uint64_t> bases(src.size(), b.window ? base : 0);   // a window goes on where the windows in front ended
             rc = matchy_scan_result_to_ndjson_segments(sc, &r, data, src.data(), bases.data(), input_line, &text, &n);
         }
         if (rc == MATCHY_SUCCESS) { d.text = text; d.text_len = n; }
@@ -617,7 +636,7 @@ struct MatchPipeline {
             } else if (d) {
                 if (line_ctx) {   // the worker's scanner renders here: with line context its hook renders nothing, so one thread at a time uses it
                     render_numbered(matchy_multi_scanner_worker_scanner(ms, b.worker), b.result, b.data, *hb, line_base[hb->input], *d);
-                    if (hb->pack.empty() && hb->gz.empty()) line_base[hb->input] += b.result.lines;
+                    if ((hb->pack.empty() && hb->gz.empty()) || hb->window) line_base[hb->input] += b.result.lines;
                 }
                 if (!d->ok) each_input(*hb, [&](size_t i) { input_failed[i] = 1; });   // rendering failed: the batch's matches are missing, exit status says so
                 if (d->text_len) write_all_stdout(d->text, d->text_len);
@@ -636,8 +655,10 @@ struct MatchPipeline {
 // (crates/matchy/src/file_reader.rs:45-75, by extension); "-" is stdin. Regular files are mapped and their batches are
 // views of the mapping (no copy on the host; this thread pre-faults and pins each batch's pages ahead of its scan;
 // MATCHY_AMD_NO_MMAP=1 reads them like a stream instead). Returns false when the input could not be read. Mappings are
-// released by the printer as their files complete.
-bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t batch_bytes) {
+// released by the printer as their files complete. skip (inputs that are read): the first `skip` bytes of the stream — what the gz windows
+// in front have reported already (--gz-windows), which ends behind a '\n' — are read and cut into batches like the rest, so the cuts
+// are those of the whole stream, but not submitted; 0 is the whole input.
+bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t batch_bytes, uint64_t skip = 0) {
     const bool gz = ends_with_ci(path, ".gz");
     int fd = path == "-" ? 0 : open(path.c_str(), O_RDONLY);
     if (fd < 0) { fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), strerror(errno)); return false; }
@@ -677,11 +698,13 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
             return r;
         },
         batch_bytes,
-        [&](Bytes&& data, size_t len, uint64_t) {
-            Batch b;
-            b.input = input; b.ptr = data.get(); b.len = len; b.own = std::move(data);
-            pl.submit(std::move(b));
+        [&](Bytes&& data, size_t len, uint64_t off) {
             total_read += len;
+            if (off + len <= skip) return true;   // reported already
+            const size_t drop = off < skip ? (size_t)(skip - off) : 0;   // skip lies behind a '\n': what is left starts a line
+            Batch b;
+            b.input = input; b.ptr = data.get() + drop; b.len = len - drop; b.own = std::move(data);
+            pl.submit(std::move(b));
             return true;
         });
     const bool ok = e == StreamEnd::DONE;
@@ -796,10 +819,70 @@ struct GzPacker {
     std::vector<uint64_t> cuts;
     size_t multi_files = 0, multi_members = 0;   // of the files the GPU accepted: those of more than one member, and their members
 
+    // --gz-windows: a multi-member .gz input that take() leaves (larger than a batch, or more text than a pack holds) is mapped and goes
+    // out as a chain of windows of whole members: up to batch_bytes - carry_cap of text and batch_bytes compressed each. carry_cap is
+    // min(1 MiB, max_member); MATCHY_AMD_GZ_MAX_CARRY lowers it.
+    bool windows = false;
+    size_t carry_cap = 0;
+    size_t win_windows = 0, win_files = 0, win_host = 0;   // windows the GPU accepted, files that went out as windows, of those finished on the host
+
     GzPacker(MatchPipeline& p, const std::vector<std::string>& ps, std::vector<char>& rf, size_t bb) : pl(p), paths(ps), read_failed(rf) {
         batch_bytes = std::min<size_t>(bb, ((size_t)1 << 31) - ((size_t)1 << 20));   // a batch stays below 2^31 bytes
         max_member = batch_bytes / 4;
         if (const char* e = getenv("MATCHY_AMD_GZ_MAX_MEMBER")) max_member = std::min<size_t>(max_member, strtoull(e, nullptr, 10));
+        carry_cap = std::min<size_t>((size_t)1 << 20, max_member);
+        if (const char* e = getenv("MATCHY_AMD_GZ_MAX_CARRY")) carry_cap = std::min<size_t>(carry_cap, strtoull(e, nullptr, 10));
+    }
+    // --gz-windows, behind barrier(): input i as a chain of windows. False: not eligible (no regular .gz file, a first header that does
+    // not parse, a first member that alone breaks a bound), nothing was submitted and the input is read the way it is without the flag.
+    // The windows go out one at a time: the reader waits for a window's verdict, and with it the carry, before it submits the next —
+    // and faults the next window's pages in meanwhile. A window the GPU does not accept (a member that fails, NO_LINE_END, a scan that
+    // failed) or a member the walker cannot take ends the chain: everything reported so far is right — verified members, complete
+    // lines only — and the host reads the file the way it does without the flag and reports what lies behind the bytes the accepted
+    // windows consumed. A file whose decoder fails loses the batch the host was filling, as it does without the flag: the records are
+    // those of the run without the flag, plus — where the windows had got further than the host's last batch cut — the complete lines
+    // in between.
+    bool take_windows(size_t i) {
+        const std::string& path = paths[i];
+        struct stat sb;
+        if (!windows || !pack_ends_with_gz(path)) return false;
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18) { close(fd); return false; }
+        const size_t size = (size_t)sb.st_size;
+        void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        close(fd);
+        if (m == MAP_FAILED) return false;
+        const uint8_t* p = (const uint8_t*)m;
+        const uint64_t max_text = batch_bytes - carry_cap;   // carry_cap <= max_member = batch_bytes / 4
+        GzWindow cur, nxt;
+        if (!gz_next_window(p, size, 0, batch_bytes, max_text, max_member, cur)) { munmap(m, size); return false; }
+        ++win_files;
+        std::vector<uint8_t> carry;
+        uint64_t from = 0, consumed = 0;
+        size_t last_seq = 0;
+        bool ok = false;
+        for (;;) {
+            Batch b;
+            b.input = i; b.ptr = p + from; b.len = (size_t)(cur.end - from); b.mapped = true;
+            b.window = true; b.window_last = cur.end == size; b.carry = carry; b.carry_cap = (uint32_t)carry_cap;
+            b.gz.push_back(GzFile{i, 0, (uint32_t)b.len, (uint32_t)cur.text, cur.members});
+            b.verdict = std::make_shared<GzVerdict>();
+            const std::shared_ptr<GzVerdict> v = b.verdict;
+            last_seq = pl.submit(std::move(b));
+            const bool have_next = cur.end < size && gz_next_window(p, size, cur.end, batch_bytes, max_text, max_member, nxt);
+            if (have_next) { volatile uint8_t sink = 0; for (uint64_t q = cur.end; q < nxt.end; q += 4096) sink = sink + p[q]; }
+            v->wait();
+            if (v->status.size() != 1 || v->status[0] != MATCHY_GZ_OK || v->window_status != MATCHY_WINDOW_OK) break;
+            ++win_windows; consumed += v->bytes;
+            carry = std::move(v->carry);
+            if (cur.end == size) { ok = true; break; }
+            if (!have_next) break;   // the next member alone breaks a bound
+            from = cur.end; cur = nxt;
+        }
+        pl.add_mapping(m, size, last_seq);
+        if (!ok) { ++win_host; if (!read_input(pl, i, path, batch_bytes, consumed)) read_failed[i] = 1; }
+        return true;
     }
     // --gz-members: the members of the file p[0, size), whose first header parses. False: a member's compressed length or ISIZE above
     // max_member, a piece with no room for its trailer, or more text than one pack holds — the file keeps the host path.
@@ -886,7 +969,7 @@ struct GzPacker {
 int cmd_match(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gather_lines = false, render_gpu = false, whole_lines = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gz_windows = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
@@ -918,6 +1001,7 @@ int cmd_match(int argc, char** argv) {
         else if (a == "--pack-inputs") pack = true;
         else if (a == "--gz-on-gpu") gz_gpu = true;
         else if (a == "--gz-members") gz_members = true;
+        else if (a == "--gz-windows") gz_windows = true;
         else if (a == "--gather-lines") gather_lines = true;
         else if (a == "--render-on-gpu") render_gpu = true;
         else if (a == "--whole-lines") whole_lines = true;
@@ -932,6 +1016,7 @@ int cmd_match(int argc, char** argv) {
     }
     if (pos.size() < 2) return usage();
     if (format != "json" && format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", format.c_str()); return 1; }
+    if (gz_windows && !(gz_gpu && gz_members)) { fprintf(stderr, "Error: --gz-windows needs --gz-on-gpu --gz-members (it extends them to multi-member files larger than a batch)\n"); return 1; }
     if (gz_members && !gz_gpu) { fprintf(stderr, "Error: --gz-members needs --gz-on-gpu (it extends the gz packs to files of many members)\n"); return 1; }
     if (whole_lines) {
         // the mode has no extraction to configure, and the library refuses it together with segments, gz scans, hit lines and rendered records
@@ -1053,10 +1138,12 @@ int cmd_match(int argc, char** argv) {
     PackStats packed;
     GzPacker gzp(pl, paths, read_failed, batch_bytes);
     gzp.members = gz_members;
+    gzp.windows = gz_windows;
     // an input that is not part of a plain pack: into the gz pack in hand, or, behind that pack and its verdict, the way it is read without the flags
     auto single = [&](size_t i) {
         if (gz_gpu && gzp.take(i)) return;
         if (gz_gpu) gzp.barrier();
+        if (gz_windows && gzp.take_windows(i)) return;
         if (!read_input(pl, i, paths[i], batch_bytes)) read_failed[i] = 1;
     };
     if (pack) {
@@ -1149,6 +1236,7 @@ int cmd_match(int argc, char** argv) {
         if (gz_gpu) fprintf(stderr, "[INFO] Inflated %zu .gz inputs on the GPU in %zu batches (%llu -> %llu bytes), %zu read on the host\n", gzp.on_gpu, gzp.packs,
                             gzp.packed_bytes, gzp.text_bytes, gzp.on_host);
         if (gz_members) fprintf(stderr, "[INFO] gz members on the GPU: %zu in %zu multi-member files\n", gzp.multi_members, gzp.multi_files);
+        if (gz_windows) fprintf(stderr, "[INFO] gz windows on the GPU: %zu windows of %zu files, %zu finished on the host\n", gzp.win_windows, gzp.win_files, gzp.win_host);
     }
     matchy_multi_scanner_free(ms);
     matchy_close(db);

@@ -257,10 +257,14 @@ public:
     GzBatch gz_inflate(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n);
     // the same for files of one member or many (GzInflate::launch_files): FILE i is segment i
     GzBatch gz_inflate_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files);
+    // one window of a file that is larger than a batch (GzInflate::launch_window): the window is segment 0, its carry lies in front
+    GzBatch gz_inflate_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last);
     void gz_queue_results(bool want_text);
     GzInflate::Result gz_finish();
     // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
     void gz_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (gz_) gz_->timing(out_ms); }
+    // the same behind a window scan (the third value then includes k_gz_window_tail), and that kernel's own time as a fourth
+    void gz_window_timing(float out_ms[4]) const { gz_timing(out_ms); out_ms[3] = gz_ ? gz_->tail_ms() : 0; }
     // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
     // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.
     // scan_host reads the setting itself; the other entries of a lookup scan call arm_whole_lines in front of arm_segments, which sets

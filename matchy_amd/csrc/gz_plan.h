@@ -8,6 +8,9 @@
 //
 // Multi-member files (gz_split_members, gz_plan_files, below): the members of a file are found on the host, laid out as ONE segment and
 // inflated by one wave each.
+//
+// Windows (gz_next_window, gz_plan_window, below): a file larger than a batch is walked window by window — runs of whole members — and
+// every window is planned like a file, with the carry of the window in front laid in front of its text.
 #pragma once
 
 #include <algorithm>
@@ -136,30 +139,61 @@ inline bool gz_bgzf_bsize(const uint8_t* p, uint64_t len, uint32_t& bsize) {
 // predecessor reports TRAILING_DATA and the file falls back, like one with an unusual XFL.
 // Every cut lies at least 20 bytes behind the one in front of it, so there are at most len / 18 of them; every read is inside p[0, len).
 constexpr uint64_t GZ_SPLIT_MAX_STR = 256;
+// The ONE copy of the cut rule above: the member at `pos` of the file p[0, len), whose header of `body` bytes has parsed. True with
+// the next member's position and the length of its header; false: this member keeps the rest of the file.
+inline bool gz_next_member(const uint8_t* p, uint64_t len, uint64_t pos, uint64_t body, uint64_t& next, uint64_t& next_body) {
+    static const uint8_t magic[3] = {0x1F, 0x8B, 8};
+    uint32_t bsize = 0;
+    if (gz_bgzf_bsize(p + pos, len - pos, bsize)) {
+        next = pos + bsize + 1;
+        return !((uint64_t)bsize + 1 < body + 10 || next >= len || gz_parse_header(p + next, len - next, next_body, GZ_SPLIT_MAX_STR) != GZ_PLAN_OK);
+    }
+    for (uint64_t q = pos + body + 10;; ++q) {
+        const void* hit = q < len ? memmem(p + q, len - q, magic, 3) : nullptr;
+        if (!hit) return false;
+        q = (uint64_t)((const uint8_t*)hit - p);
+        if (len - q < 10) return false;   // no later position has room for a header either
+        if (!(p[q + 3] & 0xE0) && (p[q + 8] == 0 || p[q + 8] == 2 || p[q + 8] == 4) && gz_parse_header(p + q, len - q, next_body, GZ_SPLIT_MAX_STR) == GZ_PLAN_OK) { next = q; return true; }
+    }
+}
 inline void gz_split_members(const uint8_t* p, uint64_t len, std::vector<uint64_t>& cuts) {
     cuts.clear();
     cuts.push_back(0);
-    static const uint8_t magic[3] = {0x1F, 0x8B, 8};
     uint64_t pos = 0, body = 0;   // the member in hand and the length of its header
     if (gz_parse_header(p, len, body) != GZ_PLAN_OK) return;
+    for (uint64_t next = 0, nb = 0; gz_next_member(p, len, pos, body, next, nb); pos = next, body = nb) cuts.push_back(next);
+}
+
+// Windows (gz_plan_window, below): a file too large for one batch is scanned as runs of consecutive whole members. The walker finds the
+// next run without walking the whole file first: from `from` — 0, or the end of the window in front — it steps from member to member by
+// gz_next_member, so the cuts it yields over a file are exactly those of gz_split_members, and stops in front of the member that would
+// push the window past max_text inflated bytes (the sum of the ISIZE fields) or max_comp compressed bytes. False — no window: nothing
+// is left (from >= len), or the next member alone breaks a bound: its header does not parse, it has no room for a trailer, or its
+// compressed length or its ISIZE is above max_member, max_comp or max_text. All sums are 64-bit; every read is inside p[0, len). The
+// member that ends a window is stepped over once more by the next call, so a file costs at most twice the walk of gz_split_members.
+// cuts: where the window's members start, appended (nullptr: not wanted).
+struct GzWindow { uint64_t end = 0, text = 0; uint32_t members = 0; };
+inline bool gz_next_window(const uint8_t* p, uint64_t len, uint64_t from, uint64_t max_comp, uint64_t max_text, uint64_t max_member, GzWindow& out,
+                           std::vector<uint64_t>* cuts = nullptr) {
+    out = GzWindow();
+    out.end = from;
+    if (from >= len) return false;
+    uint64_t pos = from, body = 0;
+    if (gz_parse_header(p + pos, len - pos, body, from ? GZ_SPLIT_MAX_STR : ~0ull) != GZ_PLAN_OK) return false;
     for (;;) {
-        uint32_t bsize = 0;
         uint64_t next = 0, nb = 0;
-        if (gz_bgzf_bsize(p + pos, len - pos, bsize)) {
-            next = pos + bsize + 1;
-            if ((uint64_t)bsize + 1 < body + 10 || next >= len || gz_parse_header(p + next, len - next, nb, GZ_SPLIT_MAX_STR) != GZ_PLAN_OK) return;
-        } else {
-            for (uint64_t q = pos + body + 10;; ++q) {
-                const void* hit = q < len ? memmem(p + q, len - q, magic, 3) : nullptr;
-                if (!hit) return;
-                q = (uint64_t)((const uint8_t*)hit - p);
-                if (len - q < 10) return;   // no later position has room for a header either
-                if (!(p[q + 3] & 0xE0) && (p[q + 8] == 0 || p[q + 8] == 2 || p[q + 8] == 4) && gz_parse_header(p + q, len - q, nb, GZ_SPLIT_MAX_STR) == GZ_PLAN_OK) { next = q; break; }
-            }
-        }
-        cuts.push_back(next);
+        const bool more = gz_next_member(p, len, pos, body, next, nb);
+        const uint64_t end = more ? next : len, mlen = end - pos;
+        if (mlen - body < 8 || mlen > max_member) break;   // no room for the trailer; too long for one wave
+        const uint8_t* t = p + end - 4;
+        const uint64_t isize = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+        if (isize > max_member || out.text + isize > max_text || end - from > max_comp || out.members == 0x7FFFFFFFu) break;
+        if (cuts) cuts->push_back(pos);
+        out.end = end; out.text += isize; ++out.members;
+        if (!more) break;
         pos = next; body = nb;
     }
+    return out.members != 0;
 }
 
 // The plan of a pack of files. The members of a file lie end to end with NOTHING between them — a line may span two members, BGZF cuts
@@ -221,6 +255,21 @@ inline bool gz_plan_files(const uint8_t* packed, uint64_t packed_len, const GzFi
     plan.total = start;
     for (size_t i = 0; i < plan.members.size(); ++i) if (plan.members[i].status == GZ_PLAN_OK) plan.order.push_back((uint32_t)i);
     std::stable_sort(plan.order.begin(), plan.order.end(), [&](uint32_t a, uint32_t b) { return plan.members[a].cap > plan.members[b].cap; });
+    return true;
+}
+
+// The plan of one window: packed[0, packed_len) holds the window's whole members (split here once more, like a file of gz_plan_files),
+// carry_len bytes — the partial line the window in front left behind — lie in front of their text:
+//   [carry][member 0 text] ... [member m - 1 text][one '\n', only if the window is the file's LAST and carry + capacities > 0]
+// The members' starts are shifted by carry_len; the window is segment 0 of the scan and starts at 0; caps[0] is the sum of the
+// members' capacities, without the carry. Refused like a file: a batch that reaches 2^31 bytes, the carry counted in.
+inline bool gz_plan_window(const uint8_t* packed, uint64_t packed_len, uint32_t carry_len, bool last, GzFilesPlan& plan, std::string& err) {
+    const GzFileIn file{0, packed_len};
+    if (!gz_plan_files(packed, packed_len, &file, 1, plan, err)) return false;
+    const uint64_t text = (uint64_t)carry_len + plan.caps[0];
+    if (text + 1 >= (1ull << 31)) { err = "gz plan: the inflated batch reaches 2^31 bytes with the carry of " + std::to_string(carry_len) + " bytes in front of the window"; return false; }
+    for (GzPlanned& g : plan.members) g.start += carry_len;
+    plan.total = text + (last && text ? 1 : 0);
     return true;
 }
 

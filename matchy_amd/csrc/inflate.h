@@ -35,6 +35,18 @@ hipError_t gz_file_verdict_launch(const uint32_t* first_member, uint32_t n_files
 hipError_t gz_seal_files_launch(const GzMemberDev* members, uint32_t n_members, const uint32_t* first_member, uint32_t n_files, const int32_t* file_status,
                                 uint8_t* text, uint32_t text_len, hipStream_t stream);
 
+// Windows (gz_plan_window): behind k_gz_seal_files on the same stream, one workgroup of GZ_TAIL_THREADS for the one window of the batch,
+// whose text is text[0, seg_end) with carry_len bytes of carry in front. It finds the window's last '\n' within the last carry_cap + 1
+// bytes, walking back in blocks of GZ_TAIL_BLOCK bytes, copies the partial line behind it (the tail, at most carry_cap bytes) to
+// carry_out and overwrites it with '\n'; result[0] = the tail's length, result[1] = GZ_WINDOW_OK or GZ_WINDOW_NO_LINE_END (the whole
+// window is then '\n'). A window whose file_status[0] is not OK gets its carry region set to '\n' as well, and `last` (the file ends
+// here) cuts nothing and writes the separator at text[seg_end]. Nothing is loaded or stored outside text[0, text_len) and
+// carry_out[0, carry_cap).
+constexpr uint32_t GZ_TAIL_THREADS = 256, GZ_TAIL_BLOCK = 4096;
+constexpr int32_t GZ_WINDOW_OK = 0, GZ_WINDOW_NO_LINE_END = 1;
+hipError_t gz_window_tail_launch(uint8_t* text, uint32_t text_len, uint32_t seg_end, uint32_t carry_len, const int32_t* file_status, uint32_t carry_cap, bool last,
+                                 uint8_t* carry_out, uint32_t* result, hipStream_t stream);
+
 // The gz pass of a scanner (Scanner::gz_inflate): the plan of the pack in flight and the buffers of the pass, grown on demand and reused
 // between scans. A scan runs as launch() in front of the scan's kernels, queue_results() behind them on the same stream and finish()
 // behind the wait. Not thread-safe, like the scanner. Throws mxy::HipError and, for a table that breaks its rules, mxy::ParamError.
@@ -45,6 +57,12 @@ public:
     // The same for a pack of files of one member or many (gz_plan_files): k_gz_inflate over the members of all files, then
     // k_gz_file_verdict and k_gz_seal_files. starts() are then the FILES' starts: file i is segment i.
     void launch_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files, int n_cu, bool profile, hipStream_t stream);
+    // One window of a file that is larger than a batch: packed[0, packed_len) are its whole members (gz_plan_window), carry[0, carry_len)
+    // the partial line the window in front left behind, staged through a pinned block of the pass and copied to text[0, carry_len).
+    // k_gz_inflate over the members, k_gz_file_verdict and k_gz_seal_files for the one file, then k_gz_window_tail. The window is
+    // segment 0 of the scan.
+    void launch_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last, int n_cu, bool profile,
+                       hipStream_t stream);
     const uint8_t* device_text() const { return text_.p; }
     uint32_t text_len() const { return (uint32_t)plan_.total; }
     const std::vector<uint32_t>& starts() const { return plan_.starts; }
@@ -56,13 +74,19 @@ public:
     // Behind launch_files() the accounting is per file (a file is OK when all its members are), and file_status (n_files values),
     // first_member (n_files + 1) are set: borrowed like status.
     struct Result { const int32_t* status = nullptr; size_t n = 0; const uint8_t* text = nullptr; size_t text_len = 0; uint64_t ok_bytes = 0, not_input_nl = 0;
-                    const int32_t* file_status = nullptr; size_t n_files = 0; const uint32_t* first_member = nullptr; };
+                    const int32_t* file_status = nullptr; size_t n_files = 0; const uint32_t* first_member = nullptr;
+                    // behind launch_window(): the window's status (GZ_WINDOW_*) and its carry, borrowed like status. ok_bytes is then
+                    // carry_len + capacities - carry_len of the result (0 for a failed window or NO_LINE_END), not_input_nl the rest of the batch
+                    bool window = false; int32_t window_status = 0; const uint8_t* carry = nullptr; uint32_t carry_len = 0; };
     Result finish();
     // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal (k_gz_file_verdict + k_gz_seal_files
     // behind launch_files) of the last profiled launch
     void timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = ms_[k]; }
+    // behind launch_window() the third value includes k_gz_window_tail; this is that kernel's own time (0 behind any other launch)
+    float tail_ms() const { return tail_ms_; }
 
 private:
+    void inflate_files(GzFilesPlan& fp, const uint8_t* packed, size_t packed_len, int n_cu, bool profile, hipStream_t stream);
     void upload_and_inflate(const uint8_t* packed, size_t packed_len, int n_cu, bool profile, hipStream_t stream);
     GzPlan plan_;                 // behind launch_files: members and order of all files, starts of the files
     bool files_ = false;          // the launch in flight was launch_files
@@ -79,6 +103,15 @@ private:
     PinnedBuf<int32_t> status_pinned_;
     PinnedBuf<uint8_t> text_pinned_;
     Event ev_[3];                 // created by the first profiled launch()
+    // windows: set by launch_window, never allocated without it
+    bool window_ = false, window_last_ = false;
+    uint32_t carry_len_ = 0, carry_cap_ = 0;
+    DevBuf<uint8_t> carry_out_;
+    DevBuf<uint32_t> window_result_;
+    PinnedBuf<uint8_t> carry_in_pinned_, carry_out_pinned_;
+    PinnedBuf<uint32_t> window_result_pinned_;
+    Event ev_tail_;
+    float tail_ms_ = 0;
     float ms_[3] = {0, 0, 0};
     bool timed_ = false, with_text_ = false;
     int waves_per_cu_ = 0;

@@ -45,7 +45,7 @@ struct RenderSpec {
         (void)matchy_scanner_set_render(sc, &p);   // copies
     }
 };
-struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; std::shared_ptr<const RenderSpec> render; std::vector<matchy_gz_file_t> gz_files; };   // node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz); gz_files: of files of one member or many (matchy_multi_scanner_submit_gz_files)
+struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; std::shared_ptr<const RenderSpec> render; std::vector<matchy_gz_file_t> gz_files; bool gz_window = false; std::vector<uint8_t> carry; uint32_t carry_cap = 0, window_flags = 0; };   // gz_window: the batch is one window of a large file (matchy_multi_scanner_submit_gz_window), carry its copied carry; node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz); gz_files: of files of one member or many (matchy_multi_scanner_submit_gz_files)
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
     const matchy_t* db = nullptr;
@@ -108,14 +108,16 @@ struct MultiScanner {
             std::string err;
             if (scanners[w]) matchy_scanner_set_whole_lines(scanners[w], want_whole_lines);
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
-            else if (!j.gz.empty() || !j.gz_files.empty()) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
+            else if (!j.gz.empty() || !j.gz_files.empty() || j.gz_window) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
                 // an armed pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
                 // (lines with matches per segment) whatever the setting is
                 matchy_scanner_set_line_context(scanners[w], want_lines || (j.render && !j.gz_text));
                 matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
                 if (j.render) j.render->arm(scanners[w]);
-                d.status = !j.gz_files.empty() ? matchy_scanner_scan_gz_files(scanners[w], j.data, j.len, j.gz_files.data(), j.gz_files.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res)
+                const matchy_gz_window_t window{j.carry.data(), (uint32_t)j.carry.size(), j.carry_cap, j.window_flags};
+                d.status = j.gz_window ? matchy_scanner_scan_gz_window(scanners[w], j.data, j.len, &window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res)
+                         : !j.gz_files.empty() ? matchy_scanner_scan_gz_files(scanners[w], j.data, j.len, j.gz_files.data(), j.gz_files.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res)
                                                : matchy_scanner_scan_gz(scanners[w], j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res);
                 d.data = nullptr; d.len = 0;
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
@@ -339,6 +341,22 @@ int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t* h, const ui
     std::unique_lock<std::mutex> lk(ms->mu);
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
     ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, {}, want_text, std::move(ms->render_next), std::move(table)});
+    ms->cv_work.notify_one();
+    return MATCHY_SUCCESS;
+}
+int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window, bool want_text,
+                                              void* tag) {
+    if (!h) { set_error("matchy_multi_scanner_submit_gz_window: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (const char* why = gz_window_refusal(packed, packed_len, window)) { set_error(std::string("matchy_multi_scanner_submit_gz_window: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    MultiJob j{0, packed, packed_len, tag, nullptr, -1, {}, {}, want_text, nullptr, {}};
+    j.gz_window = true; j.carry_cap = window->carry_cap; j.window_flags = window->flags;
+    if (window->carry_len) j.carry.assign(window->carry, window->carry + window->carry_len);   // copied in front of the lock
+    std::unique_lock<std::mutex> lk(ms->mu);
+    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
+    j.seq = ms->submitted++;
+    j.render = std::move(ms->render_next);
+    ms->q.push_back(std::move(j));
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
 }
