@@ -11,6 +11,8 @@ LIB = LIBDIR / "libmatchy_amd.so"
 BINDIR = PKG / "bin"
 CLI = BINDIR / "matchy"
 SOURCES = ["k_anchor.hip", "validate_kernels.hip", "lookup_kernels.hip", "sort_hits.hip", "line_index.hip", "hit_lines.hip", "render.hip", "text_table.hip", "distinct.hip", "tally.hip", "segments.hip", "inflate.hip", "whole_lines.hip", "ip_tables.hip", "engine.cpp", "db_image.cpp", "db_builder.cpp", "data_codec.cpp", "unicode_lower.cpp", "host_topology.cpp", "host_lookup.cpp", "capi.cpp", "multi_scanner.cpp"]
+# the `matchy` command line, built with g++ on top of the library: main and the small commands, `matchy match`
+CLI_SOURCES = ["cli_main.cpp", "cli_match.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # lookup_kernels.hip: keep the dynamically indexed private arrays of the glob matcher (result list, star stack: 80 dwords,
 # touched a few times per text) in scratch instead of in vector registers — 96 VGPRs instead of 512 for k_lookup<true>.
@@ -55,9 +57,8 @@ def build(force=False, verbose=False):
         raise RuntimeError("hipcc compilation failed")
     link = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *objs, "-ldl", "-lpthread"]
     subprocess.run(link, check=True)
-    # the `matchy` command line (build / match) on top of the library
     BINDIR.mkdir(exist_ok=True)
-    cli = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", str(CSRC / "cli_main.cpp"), "-o", str(CLI),
+    cli = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", *(str(CSRC / s) for s in CLI_SOURCES), "-o", str(CLI),
            f"-L{LIBDIR}", "-lmatchy_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN/../lib"]
     subprocess.run(cli, check=True)
     return LIB

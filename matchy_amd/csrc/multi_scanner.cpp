@@ -45,7 +45,26 @@ struct RenderSpec {
         (void)matchy_scanner_set_render(sc, &p);   // copies
     }
 };
-struct MultiJob { size_t seq; const uint8_t* data; size_t len; void* tag; const void* pinned; int32_t node; std::vector<uint32_t> starts; std::vector<matchy_gz_member_t> gz; bool gz_text; std::shared_ptr<const RenderSpec> render; std::vector<matchy_gz_file_t> gz_files; bool gz_window = false; std::vector<uint8_t> carry; uint32_t carry_cap = 0, window_flags = 0; };   // gz_window: the batch is one window of a large file (matchy_multi_scanner_submit_gz_window), carry its copied carry; node: NUMA node the bytes live on, -1 = anywhere; starts: segments of the batch (matchy_multi_scanner_submit_segments); gz: the batch is a pack of gzip files (matchy_multi_scanner_submit_gz); gz_files: of files of one member or many (matchy_multi_scanner_submit_gz_files)
+// what a batch is: set by the submit call that queued it (matchy_multi_scanner_submit / _submit_near, _submit_segments, _submit_gz,
+// _submit_gz_files, _submit_gz_window, in this order), read by the worker that scans it
+enum class JobKind { PLAIN, SEGMENTS, GZ_MEMBERS, GZ_FILES, GZ_WINDOW };
+struct MultiJob {
+    JobKind kind;
+    const uint8_t* data;                      // the caller's bytes: text, or (gz kinds) the compressed pack
+    size_t len;
+    void* tag;
+    size_t seq = 0;                           // given out when the job is queued
+    const void* pinned = nullptr;             // PLAIN, SEGMENTS: page range the caller pinned; the worker unpins it
+    int32_t node = -1;                        // NUMA node the bytes live on, -1 = anywhere
+    std::vector<uint32_t> starts;             // SEGMENTS: the segments of the batch
+    std::vector<matchy_gz_member_t> gz;       // GZ_MEMBERS: a pack of gzip files of one member each
+    std::vector<matchy_gz_file_t> gz_files;   // GZ_FILES: of files of one member or many
+    std::vector<uint8_t> carry;               // GZ_WINDOW: the batch is one window of a large file behind this carry, copied at the submit
+    uint32_t carry_cap = 0, window_flags = 0; // GZ_WINDOW
+    bool gz_text = false;                     // gz kinds: the inflated text comes back with the result
+    std::shared_ptr<const RenderSpec> render; // matchy_multi_scanner_set_render, taken by the submit that followed it
+    bool is_gz() const { return kind == JobKind::GZ_MEMBERS || kind == JobKind::GZ_FILES || kind == JobKind::GZ_WINDOW; }
+};
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
     const matchy_t* db = nullptr;
@@ -85,7 +104,7 @@ struct MultiScanner {
             worker_node[w] = node; worker_cpus[w] = cpus;
         }
         for (;;) {
-            MultiJob j;
+            MultiJob j{};
             bool want_lines = false, want_hit_lines = false, want_tally = false, touch_tally = false, want_whole_lines = false;
             {
                 std::unique_lock<std::mutex> lk(mu);
@@ -108,28 +127,26 @@ struct MultiScanner {
             std::string err;
             if (scanners[w]) matchy_scanner_set_whole_lines(scanners[w], want_whole_lines);
             if (!scanners[w]) { d.status = MATCHY_ERROR_IO; err = std::string("multi scanner: no scanner on device ") + std::to_string(devices[w]) + ": " + matchy_amd_last_error(); }
-            else if (!j.gz.empty() || !j.gz_files.empty() || j.gz_window) {   // a pack of gzip files: the batch's data / len become the inflated text, which the result owns
-                // an armed pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
+            else if (j.len || j.kind != JobKind::PLAIN) {   // an empty batch with a table is scanned too: its result carries the table
+                matchy_scanner_t* sc = scanners[w];
+                // an armed gz pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
                 // (lines with matches per segment) whatever the setting is
-                matchy_scanner_set_line_context(scanners[w], want_lines || (j.render && !j.gz_text));
-                matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
-                if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
-                if (j.render) j.render->arm(scanners[w]);
+                matchy_scanner_set_line_context(sc, want_lines || (j.is_gz() && j.render && !j.gz_text));
+                matchy_scanner_set_hit_lines(sc, want_hit_lines);
+                if (touch_tally) matchy_scanner_set_tally(sc, want_tally);
+                if (j.kind == JobKind::SEGMENTS) d.status = matchy_scanner_set_segments(sc, j.starts.data(), j.starts.size());
+                if (j.render) j.render->arm(sc);
                 const matchy_gz_window_t window{j.carry.data(), (uint32_t)j.carry.size(), j.carry_cap, j.window_flags};
-                d.status = j.gz_window ? matchy_scanner_scan_gz_window(scanners[w], j.data, j.len, &window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res)
-                         : !j.gz_files.empty() ? matchy_scanner_scan_gz_files(scanners[w], j.data, j.len, j.gz_files.data(), j.gz_files.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res)
-                                               : matchy_scanner_scan_gz(scanners[w], j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res);
-                d.data = nullptr; d.len = 0;
-                if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
-                else (void)matchy_scan_result_gz(&d.res, nullptr, nullptr, &d.data, &d.len);
-            }
-            else if (j.len || !j.starts.empty()) {   // an empty batch with a table is scanned too: its result carries the table
-                matchy_scanner_set_line_context(scanners[w], want_lines);
-                matchy_scanner_set_hit_lines(scanners[w], want_hit_lines);
-                if (touch_tally) matchy_scanner_set_tally(scanners[w], want_tally);
-                if (!j.starts.empty()) d.status = matchy_scanner_set_segments(scanners[w], j.starts.data(), j.starts.size());
-                if (j.render) j.render->arm(scanners[w]);
-                if (d.status == MATCHY_SUCCESS) d.status = matchy_scanner_scan(scanners[w], j.data, j.len, &d.res);
+                if (d.status == MATCHY_SUCCESS) switch (j.kind) {
+                    case JobKind::PLAIN: case JobKind::SEGMENTS: d.status = matchy_scanner_scan(sc, j.data, j.len, &d.res); break;
+                    case JobKind::GZ_MEMBERS: d.status = matchy_scanner_scan_gz(sc, j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
+                    case JobKind::GZ_FILES: d.status = matchy_scanner_scan_gz_files(sc, j.data, j.len, j.gz_files.data(), j.gz_files.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
+                    case JobKind::GZ_WINDOW: d.status = matchy_scanner_scan_gz_window(sc, j.data, j.len, &window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
+                }
+                if (j.is_gz()) {   // the batch's data / len become the inflated text, which the result owns
+                    d.data = nullptr; d.len = 0;
+                    if (d.status == MATCHY_SUCCESS) (void)matchy_scan_result_gz(&d.res, nullptr, nullptr, &d.data, &d.len);
+                }
                 if (d.status != MATCHY_SUCCESS) err = matchy_amd_last_error();
             }
             if (d.status == MATCHY_SUCCESS && hook) d.payload = hook(hook_user, w, scanners[w], &d.res, d.data, d.len, j.tag);
@@ -300,58 +317,10 @@ int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t* h, size_t
     if (cpus_bound) *cpus_bound = ms->worker_cpus[worker];
     return MATCHY_SUCCESS;
 }
-int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, void* tag, const void* pinned_range, int32_t numa_node) {
-    if (!h || (!data && len) || len > 0xFFFFFFFFull) return MATCHY_ERROR_INVALID_PARAM;
-    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
-    std::unique_lock<std::mutex> lk(ms->mu);
-    // blocks while the job queue is full OR max_inflight batches are out (someone has to call matchy_multi_scanner_next: a caller that
-    // submits and gathers on ONE thread interleaves the two — matchy_multi_scanner_pending() tells it when a next() is due)
-    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, numa_node, {}, {}, false, std::move(ms->render_next)});
-    ms->cv_work.notify_one();
-    return MATCHY_SUCCESS;
-}
-int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, const uint32_t* starts, size_t n, void* tag,
-                                             const void* pinned_range) {
-    if (!h || (!data && len) || len > 0xFFFFFFFFull || (!starts && n)) return MATCHY_ERROR_INVALID_PARAM;
-    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
-    std::vector<uint32_t> table(starts, starts + n);   // copied in front of the lock
-    std::unique_lock<std::mutex> lk(ms->mu);
-    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, data, len, tag, pinned_range, -1, std::move(table), {}, false, std::move(ms->render_next)});
-    ms->cv_work.notify_one();
-    return MATCHY_SUCCESS;
-}
-int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, bool want_text,
-                                       void* tag) {
-    if (!h || (!packed && packed_len) || !members || n == 0) { set_error("matchy_multi_scanner_submit_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
-    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
-    std::vector<matchy_gz_member_t> table(members, members + n);   // copied in front of the lock
-    std::unique_lock<std::mutex> lk(ms->mu);
-    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, std::move(table), want_text, std::move(ms->render_next)});
-    ms->cv_work.notify_one();
-    return MATCHY_SUCCESS;
-}
-int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_file_t* files, size_t n_files,
-                                             bool want_text, void* tag) {
-    if (!h || (!packed && packed_len) || !files || n_files == 0) { set_error("matchy_multi_scanner_submit_gz_files: no files"); return MATCHY_ERROR_INVALID_PARAM; }
-    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
-    std::vector<matchy_gz_file_t> table(files, files + n_files);   // copied in front of the lock
-    std::unique_lock<std::mutex> lk(ms->mu);
-    ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
-    ms->q.push_back(MultiJob{ms->submitted++, packed, packed_len, tag, nullptr, -1, {}, {}, want_text, std::move(ms->render_next), std::move(table)});
-    ms->cv_work.notify_one();
-    return MATCHY_SUCCESS;
-}
-int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window, bool want_text,
-                                              void* tag) {
-    if (!h) { set_error("matchy_multi_scanner_submit_gz_window: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
-    if (const char* why = gz_window_refusal(packed, packed_len, window)) { set_error(std::string("matchy_multi_scanner_submit_gz_window: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
-    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
-    MultiJob j{0, packed, packed_len, tag, nullptr, -1, {}, {}, want_text, nullptr, {}};
-    j.gz_window = true; j.carry_cap = window->carry_cap; j.window_flags = window->flags;
-    if (window->carry_len) j.carry.assign(window->carry, window->carry + window->carry_len);   // copied in front of the lock
+// The one way into the queue; the job's tables were copied in front of the lock. Blocks while the job queue is full OR max_inflight
+// batches are out (someone has to call matchy_multi_scanner_next: a caller that submits and gathers on ONE thread interleaves the two —
+// matchy_multi_scanner_pending() tells it when a next() is due).
+static int32_t enqueue(MultiScanner* ms, MultiJob&& j) {
     std::unique_lock<std::mutex> lk(ms->mu);
     ms->cv_space.wait(lk, [&] { return ms->q.size() < ms->max_q && ms->submitted - ms->taken < ms->max_inflight; });
     j.seq = ms->submitted++;
@@ -359,6 +328,42 @@ int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t* h, const u
     ms->q.push_back(std::move(j));
     ms->cv_work.notify_one();
     return MATCHY_SUCCESS;
+}
+int32_t matchy_multi_scanner_submit_near(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, void* tag, const void* pinned_range, int32_t numa_node) {
+    if (!h || (!data && len) || len > 0xFFFFFFFFull) return MATCHY_ERROR_INVALID_PARAM;
+    MultiJob j{JobKind::PLAIN, data, len, tag};
+    j.pinned = pinned_range; j.node = numa_node;
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_segments(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, const uint32_t* starts, size_t n, void* tag,
+                                             const void* pinned_range) {
+    if (!h || (!data && len) || len > 0xFFFFFFFFull || (!starts && n)) return MATCHY_ERROR_INVALID_PARAM;
+    MultiJob j{n ? JobKind::SEGMENTS : JobKind::PLAIN, data, len, tag};   // no table: a plain batch
+    j.pinned = pinned_range; j.starts.assign(starts, starts + n);
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_gz(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, bool want_text,
+                                       void* tag) {
+    if (!h || (!packed && packed_len) || !members || n == 0) { set_error("matchy_multi_scanner_submit_gz: no members"); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiJob j{JobKind::GZ_MEMBERS, packed, packed_len, tag};
+    j.gz_text = want_text; j.gz.assign(members, members + n);
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_file_t* files, size_t n_files,
+                                             bool want_text, void* tag) {
+    if (!h || (!packed && packed_len) || !files || n_files == 0) { set_error("matchy_multi_scanner_submit_gz_files: no files"); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiJob j{JobKind::GZ_FILES, packed, packed_len, tag};
+    j.gz_text = want_text; j.gz_files.assign(files, files + n_files);
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window, bool want_text,
+                                              void* tag) {
+    if (!h) { set_error("matchy_multi_scanner_submit_gz_window: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (const char* why = gz_window_refusal(packed, packed_len, window)) { set_error(std::string("matchy_multi_scanner_submit_gz_window: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiJob j{JobKind::GZ_WINDOW, packed, packed_len, tag};
+    j.gz_text = want_text; j.carry_cap = window->carry_cap; j.window_flags = window->flags;
+    if (window->carry_len) j.carry.assign(window->carry, window->carry + window->carry_len);
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
 }
 size_t matchy_multi_scanner_pending(const matchy_multi_scanner_t* h) {
     if (!h) return 0;

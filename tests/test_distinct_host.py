@@ -31,7 +31,8 @@ def test_header_export_list_and_library_carry_the_unique_calls():
 
 
 def test_command_line_keeps_no_host_set():
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    import matchy_amd.build as B
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "seen_sorted" not in src and "seen_new" not in src
     assert "matchy_amd_extractor_set_unique" in src
 

@@ -206,7 +206,8 @@ def test_sources():
     hip = (ROOT / "matchy_amd" / "csrc" / "inflate.hip").read_text()
     for k in ("k_gz_inflate", "k_gz_seal", "k_gz_file_verdict", "k_gz_seal_files"):
         assert re.search(r"__global__[^;{]*\b%s\b" % k, hip), k
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    import matchy_amd.build as B
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--gz-members" in src and "matchy_multi_scanner_submit_gz_files" in src
     assert "hip/" not in (ROOT / "matchy_amd" / "csrc" / "gz_plan.h").read_text()
     assert struct.calcsize("<QQ") == 16

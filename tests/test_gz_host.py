@@ -65,7 +65,7 @@ def test_sources_and_build_list():
     hip = (ROOT / "matchy_amd" / "csrc" / "inflate.hip").read_text()
     for k in ("k_gz_inflate", "k_gz_seal"):
         assert re.search(r"__global__[^;{]*\b%s\b" % k, hip), k
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--gz-on-gpu" in src and "matchy_multi_scanner_submit_gz" in src and "MATCHY_AMD_GZ_MAX_MEMBER" in src
     for host_only in ("gz_plan.h",):
         assert "hip/" not in (ROOT / "matchy_amd" / "csrc" / host_only).read_text()

@@ -237,5 +237,6 @@ def test_sources():
         assert re.search(r"__global__[^;{]*\b%s\b" % k, hip), k
     plan_h = (ROOT / "matchy_amd" / "csrc" / "gz_plan.h").read_text()
     assert "hip/" not in plan_h and plan_h.count("memmem(") == 1   # one copy of the cut rule
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    import matchy_amd.build as B
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--gz-windows" in src and "matchy_multi_scanner_submit_gz_window" in src

@@ -61,7 +61,7 @@ def test_header_export_list_library_and_mirror_carry_the_segment_calls():
 def test_sources_build_list_and_command_line():
     import matchy_amd.build as B
     assert "segments.hip" in B.SOURCES
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--pack-inputs" in src and "matchy_multi_scanner_submit_segments" in src and "matchy_scan_result_to_ndjson_segments" in src
     hip = (ROOT / "matchy_amd" / "csrc" / "segments.hip").read_text()
     for k in ("k_seg_build", "k_seg_records", "k_seg_lines"):

@@ -50,7 +50,7 @@ def test_header_export_list_library_and_mirror_carry_the_tally_calls():
 def test_sources_build_list_and_command_line():
     import matchy_amd.build as B
     assert "tally.hip" in B.SOURCES
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--tally" in src and "matchy_multi_scanner_tally_top" in src
     hip = (ROOT / "matchy_amd" / "csrc" / "tally.hip").read_text()
     for k in ("k_tally_claim", "k_tally_publish", "k_tally_export", "k_tally_gather"):

@@ -51,7 +51,7 @@ def test_header_export_list_library_and_mirror_carry_the_whole_line_calls():
 def test_sources_build_list_and_command_line():
     import matchy_amd.build as B
     assert "whole_lines.hip" in B.SOURCES
-    src = (ROOT / "matchy_amd" / "csrc" / "cli_main.cpp").read_text()
+    src = "".join((ROOT / "matchy_amd" / "csrc" / name).read_text() for name in [*B.CLI_SOURCES, "gz_packer.h"])   # the command line
     assert "--whole-lines" in src and "matchy_multi_scanner_set_whole_lines" in src
     hip = (ROOT / "matchy_amd" / "csrc" / "whole_lines.hip").read_text()
     for k in ("k_wl_scatter", "k_wl_classify"):

@@ -1,4 +1,4 @@
-// The host-side "lines with matches" loop of `matchy match` (MatchPipeline::render in cli_main.cpp) as a function, for
+// The host-side "lines with matches" loop of `matchy match` (MatchPipeline::render in cli_match.cpp) as a function, for
 // tools/line_context_timing.py: hit starts sorted by offset; a new line starts when a '\n' lies between two hit starts.
 #include <cstddef>
 #include <cstdint>
