@@ -444,7 +444,8 @@ void matchy_scanner_get_segment_timing(const matchy_scanner_t *scanner, float ou
  * The caller hands over one host buffer that holds whole gzip files (RFC 1952, one member each) and a table of them. The compressed
  * bytes cross the bus, one wave per file inflates it on the GPU into its segment of one batch in device memory, CRC-32 and ISIZE are
  * verified there, and the scan runs over that batch as a segmented scan: segment i is member i. DEFLATE is sequential within a
- * stream: the parallelism is across the files, and a single large file gains nothing.
+ * stream: the parallelism is across the files, and a single large file gains nothing without pieces
+ * (matchy_scanner_set_gz_pieces, below) — and with them still nothing where its stream has no dynamic block at which a piece can start.
  * Layout of the batch: the members' texts end to end in table order, one '\n' — the separator, which is not the input's — behind every
  * non-empty member, whether or not its text ends in one: start[0] = 0, start[i + 1] = start[i] + out_len[i] + 1 for a non-empty
  * member and start[i] for an empty one. Line numbers inside a member do not change: the extra empty line is its last.
@@ -534,6 +535,40 @@ int32_t matchy_scan_result_gz_window(const matchy_scan_result_t *result, int32_t
 /* matchy_scanner_get_gz_timing behind a window scan (out_ms[2] then includes k_gz_window_tail), and that kernel's own milliseconds as
  * out_ms[3]. */
 void matchy_scanner_get_gz_window_timing(const matchy_scanner_t *scanner, float out_ms[4]);
+/* ---- pieces of one stream (opt-in, beside the calls above: with piece_bytes 0, the default, every kernel launch, status and output
+ * byte is what it is without this call). A large member is cut into pieces of piece_bytes compressed bytes. Every piece but the first
+ * looks for the first bit position inside it where a dynamic DEFLATE block header parses, and all pieces are decoded at once from there
+ * into 16-bit symbols, a back-reference into the unknown 32 KiB in front becoming a marker; a piece stops at the block end that is the
+ * start of a later piece. The pieces reached from piece 0 this way form a chain that is the sequential parse of the stream; markers are
+ * then resolved down the chain, and CRC-32 and ISIZE are verified as ever. A member whose chain does not reach the stream's end, or
+ * that fails any test on the way, is inflated afterwards in the same scan by the one-wave path, whose status it gets: there is no new
+ * status value, and output, statuses and their precedence are those of the scan with pieces off.
+ * piece_bytes: 0 = off; a power of two from 512 to 1 MiB = on for every member of at least 2 * piece_bytes compressed bytes; anything
+ * else is MATCHY_ERROR_INVALID_PARAM and the setting (and the scanner) stays as it was. It applies to matchy_scanner_scan_gz,
+ * matchy_scanner_scan_gz_files and matchy_scanner_scan_gz_window, whose members go through the same inflate stage.
+ * Limits. Stored and fixed blocks have no findable start: the piece in front decodes through them, so a stream of such blocks alone
+ * (gzip -1 on some builds, zlib Z_FIXED) is decoded by piece 0 at one wave's pace and costs the find on top. A member that is handed
+ * over costs what it costs with pieces off, plus the passes that ran. The symbol scratch is 2 bytes per inflated byte of the split
+ * members (at most 4 GiB, which a batch below 2^31 bytes never reaches). What a batch cannot hold stays outside
+ * this call: a member larger than a batch, and a single-stream file larger than a batch — windows need member boundaries. */
+typedef struct matchy_gz_piece_t {
+    uint64_t start_bit, end_bit;  /* in the member's DEFLATE body; end_bit: where its decoder stopped. 0 without MATCHY_PIECE_HAS_START */
+    uint32_t member;              /* index into the statuses of matchy_scan_result_gz */
+    uint32_t produced, out_pos;   /* bytes it decoded; where they begin in the member's text (0 unless live) */
+    uint32_t flags;               /* MATCHY_PIECE_* */
+} matchy_gz_piece_t;
+#define MATCHY_PIECE_HAS_START 1u    /* a block start was found in it (piece 0 of a member: always) */
+#define MATCHY_PIECE_LIVE 2u         /* on the chain from piece 0 */
+#define MATCHY_PIECE_HANDED_OVER 4u  /* its member was inflated by the one-wave path after all */
+int32_t matchy_scanner_set_gz_pieces(matchy_scanner_t *scanner, uint32_t piece_bytes);
+uint32_t matchy_scanner_get_gz_pieces(const matchy_scanner_t *scanner);
+/* The piece table of a gz scan, owned by the result: n pieces, laid out member by member; first_piece: n_members + 1 values, the pieces
+ * of member i are [first_piece[i], first_piece[i + 1]) — none for a member that was not split. With pieces off n is 0 and first_piece
+ * NULL. MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_gz_pieces(const matchy_scan_result_t *result, const matchy_gz_piece_t **pieces, size_t *n, const uint32_t **first_piece);
+/* With matchy_scanner_set_profile: milliseconds of the find, count, chain and symbols kernels, of windows + resolve + verdict, and of the
+ * handover inflate of the last gz scan (all part of out_ms[0] of matchy_scanner_get_gz_timing); zeros where no member was split. */
+void matchy_scanner_get_gz_pieces_timing(const matchy_scanner_t *scanner, float out_ms[6]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -653,6 +688,8 @@ int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t *ms, const u
  * caller takes a window's batch, and with it the carry, before it submits the next. */
 int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_window_t *window,
                                               bool want_text, void *tag);
+/* matchy_scanner_set_gz_pieces for every worker: each sets its scanner to the value in front of a gz batch it takes. */
+int32_t matchy_multi_scanner_set_gz_pieces(matchy_multi_scanner_t *ms, uint32_t piece_bytes);
 /* NUMA node of a worker's GPU (-1 = unknown) and the number of CPUs its thread bound itself to (0 = not bound); valid once the
  * worker thread has started (after the first _next at the latest). */
 int32_t matchy_multi_scanner_worker_numa(const matchy_multi_scanner_t *ms, size_t worker, int32_t *node, int32_t *cpus_bound);

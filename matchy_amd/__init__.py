@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_scan_gz", "matchy_scan_result_gz", "matchy_scanner_get_gz_timing", "matchy_multi_scanner_submit_gz",
     "matchy_scanner_scan_gz_files", "matchy_scan_result_gz_files", "matchy_multi_scanner_submit_gz_files",
     "matchy_scanner_scan_gz_window", "matchy_scan_result_gz_window", "matchy_multi_scanner_submit_gz_window", "matchy_scanner_get_gz_window_timing",
+    "matchy_scanner_set_gz_pieces", "matchy_scanner_get_gz_pieces", "matchy_scan_result_gz_pieces", "matchy_scanner_get_gz_pieces_timing",
+    "matchy_multi_scanner_set_gz_pieces",
     "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
     "matchy_multi_scanner_set_hit_lines",
     "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
@@ -178,6 +180,16 @@ GZ_WINDOW_TAIL_BLOCK = 4096   # csrc/inflate.h GZ_TAIL_BLOCK: the bytes k_gz_win
 class _GzWindow(C.Structure):
     # matchy_gz_window_t (24 bytes)
     _fields_ = [("carry", C.c_void_p), ("carry_len", C.c_uint32), ("carry_cap", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _GzPiece(C.Structure):
+    # matchy_gz_piece_t (32 bytes)
+    _fields_ = [("start_bit", C.c_uint64), ("end_bit", C.c_uint64), ("member", C.c_uint32), ("produced", C.c_uint32), ("out_pos", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+# MATCHY_PIECE_*: flags of a piece (ScanResult.gz_pieces)
+GZ_PIECE_HAS_START, GZ_PIECE_LIVE, GZ_PIECE_HANDED_OVER = 1, 2, 4
 
 
 class _GzFile(C.Structure):
@@ -338,6 +350,11 @@ def lib():
         "matchy_scan_result_gz_window": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_multi_scanner_submit_gz_window": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzWindow), C.c_bool, vp]),
         "matchy_scanner_get_gz_window_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_set_gz_pieces": (C.c_int32, [vp, C.c_uint32]),
+        "matchy_scanner_get_gz_pieces": (C.c_uint32, [vp]),
+        "matchy_scan_result_gz_pieces": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.POINTER(_GzPiece)), C.POINTER(C.c_size_t), C.POINTER(vp)]),
+        "matchy_scanner_get_gz_pieces_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_multi_scanner_set_gz_pieces": (C.c_int32, [vp, C.c_uint32]),
         "matchy_scanner_set_whole_lines": (None, [vp, C.c_bool]),
         "matchy_scanner_whole_lines": (C.c_bool, [vp]),
         "matchy_scanner_get_whole_lines_counters": (None, [vp, C.POINTER(C.c_uint64)]),
@@ -770,6 +787,22 @@ class ScanResult:
         arr = C.cast(ga[2], C.POINTER(C.c_uint32))
         return [arr[i] for i in range(ga[1] + 1)]
 
+    def gz_pieces(self):
+        """(pieces, first_piece) of a gz scan with pieces on (Scanner.set_gz_pieces; matchy_scan_result_gz_pieces): pieces is a list of
+        tuples (start_bit, end_bit, member, produced, out_pos, flags), the pieces of member i are pieces[first_piece[i]:first_piece[i + 1]].
+        ([], None) with pieces off; None for any other scan"""
+        ga = self._gz_arrays()
+        if ga is None:
+            return None
+        p, n, fp = C.POINTER(_GzPiece)(), C.c_size_t(), C.c_void_p()
+        if lib().matchy_scan_result_gz_pieces(C.byref(self._raw), C.byref(p), C.byref(n), C.byref(fp)) != 0:
+            return None
+        pieces = [(p[i].start_bit, p[i].end_bit, p[i].member, p[i].produced, p[i].out_pos, p[i].flags) for i in range(n.value)]
+        if not fp.value:
+            return pieces, None
+        arr = C.cast(fp, C.POINTER(C.c_uint32))
+        return pieces, [arr[i] for i in range(ga[1] + 1)]
+
     def hit_lines(self):
         """the block of the distinct lines with a hit (Scanner.set_hit_lines; matchy_scan_result_hit_lines) as a dict: text (bytes),
         text_len, n_lines and the uint32 numpy arrays line_off (n_lines + 1), line_no, line_of_hit, line_of_ip4_hit (None where the
@@ -1108,6 +1141,20 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_scan_gz_window failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def set_gz_pieces(self, piece_bytes=0):
+        """pieces of one stream for the next gz scans (matchy_scanner_set_gz_pieces): every member of at least 2 * piece_bytes compressed
+        bytes is inflated by one wave per piece. 0 = off (the default); otherwise a power of two from 512 to 1 MiB, else ValueError"""
+        if lib().matchy_scanner_set_gz_pieces(self._h, piece_bytes) != 0:
+            raise ValueError(f"matchy_scanner_set_gz_pieces failed: {last_error()}")
+
+    def gz_pieces(self) -> int:
+        return int(lib().matchy_scanner_get_gz_pieces(self._h))
+
+    def gz_pieces_timing_ms(self):
+        out = (C.c_float * 6)()
+        lib().matchy_scanner_get_gz_pieces_timing(self._h, out)
+        return dict(find=out[0], count=out[1], chain=out[2], symbols=out[3], resolve=out[4], handover=out[5])
+
     def gz_window_timing_ms(self):
         out = (C.c_float * 4)()
         lib().matchy_scanner_get_gz_window_timing(self._h, out)
@@ -1212,6 +1259,11 @@ class MultiScanner:
     def set_hit_lines(self, on: bool):
         """hit lines for every worker's scanner, from the next batch on: batches from next() answer hit_lines() and render without text"""
         lib().matchy_multi_scanner_set_hit_lines(self._h, bool(on))
+
+    def set_gz_pieces(self, piece_bytes=0):
+        """Scanner.set_gz_pieces on every worker's scanner, from the next gz batch on"""
+        if lib().matchy_multi_scanner_set_gz_pieces(self._h, piece_bytes) != 0:
+            raise ValueError(f"matchy_multi_scanner_set_gz_pieces failed: {last_error()}")
 
     def set_render(self, flags=0, source=None, sources=None, line_base=0, line_bases=None):
         """arms the NEXT batch submitted (submit_ptr / submit_segments_ptr / submit_gz_ptr) like Scanner.set_render: next() then carries

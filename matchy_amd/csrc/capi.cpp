@@ -1236,6 +1236,12 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
         }
         in->gz_text = g.text; in->gz_text_len = g.text_len;
         if (sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
+        if (g.first_piece) {   // pieces are on: the table may still be empty
+            in->has_gz_pieces = true;
+            in->gz_first_piece.assign(g.first_piece, g.first_piece + g.n + 1);
+            in->gz_pieces.resize(g.n_pieces);
+            for (size_t k = 0; k < g.n_pieces; ++k) memcpy(&in->gz_pieces[k], &g.pieces[k], sizeof(matchy_gz_piece_t));
+        }
         if (g.window) {   // the carry is the next window's input while this result may already be freed by then: always owned
             in->has_gz_window = true;
             in->gz_window_status = g.window_status;
@@ -1298,6 +1304,28 @@ int32_t matchy_scan_result_gz(const matchy_scan_result_t* r, const int32_t** sta
     if (text) *text = in->gz_text;
     if (text_len) *text_len = in->gz_text_len;
     return MATCHY_SUCCESS;
+}
+static_assert(sizeof(matchy_gz_piece_t) == 32 && offsetof(matchy_gz_piece_t, flags) == offsetof(gz::Piece, flags) && offsetof(matchy_gz_piece_t, member) == offsetof(gz::Piece, member),
+              "matchy_gz_piece_t is the first 32 bytes of gz::Piece");
+static_assert(MATCHY_PIECE_HAS_START == gz::PIECE_HAS_START && MATCHY_PIECE_LIVE == gz::PIECE_LIVE && MATCHY_PIECE_HANDED_OVER == gz::PIECE_HANDED, "the kernels write MATCHY_PIECE_* flags directly");
+int32_t matchy_scanner_set_gz_pieces(matchy_scanner_t* s, uint32_t piece_bytes) {
+    if (!s) { set_error("matchy_scanner_set_gz_pieces: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (piece_bytes && !gz_piece_bytes_valid(piece_bytes)) { set_error("matchy_scanner_set_gz_pieces: piece_bytes is 0 or a power of two from 512 to 1 MiB"); return MATCHY_ERROR_INVALID_PARAM; }
+    reinterpret_cast<ScannerH*>(s)->sc->set_gz_pieces(piece_bytes);
+    return MATCHY_SUCCESS;
+}
+uint32_t matchy_scanner_get_gz_pieces(const matchy_scanner_t* s) { return s ? reinterpret_cast<const ScannerH*>(s)->sc->gz_pieces() : 0; }
+int32_t matchy_scan_result_gz_pieces(const matchy_scan_result_t* r, const matchy_gz_piece_t** pieces, size_t* n, const uint32_t** first_piece) {
+    if (!r) { set_error("matchy_scan_result_gz_pieces: no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_gz) { set_error("matchy_scan_result_gz_pieces: the result was not produced by a gz scan"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (pieces) *pieces = in->gz_pieces.data();
+    if (n) *n = in->gz_pieces.size();
+    if (first_piece) *first_piece = in->has_gz_pieces ? in->gz_first_piece.data() : nullptr;
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_gz_pieces_timing(const matchy_scanner_t* s, float out[6]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_pieces_timing(out);
 }
 void matchy_scanner_get_gz_timing(const matchy_scanner_t* s, float out[3]) {
     if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_timing(out);

@@ -63,6 +63,10 @@ struct ScanResultInternal {
     bool has_gz_window = false;
     int32_t gz_window_status = 0;
     std::vector<uint8_t> gz_carry;
+    // gz scan with pieces on (matchy_scan_result_gz_pieces): the piece table and the pieces of member i, [first[i], first[i + 1]); owned
+    bool has_gz_pieces = false;
+    std::vector<matchy_gz_piece_t> gz_pieces;
+    std::vector<uint32_t> gz_first_piece;
 };
 
 // hit tally (tally.h) behind matchy_scanner_tally_top / matchy_multi_scanner_tally_top

@@ -570,9 +570,10 @@ struct GzReader {
     bool windows = false;
     size_t win_windows = 0, win_files = 0, win_host = 0;   // windows the GPU accepted, files that went out as windows, of those finished on the host
 
-    GzReader(MatchPipeline& p, HostReader& h, bool members, bool win) : pl(p), host(h), windows(win) {
+    GzReader(MatchPipeline& p, HostReader& h, bool members, bool win, bool pieces) : pl(p), host(h), windows(win) {
         auto env = [](const char* name) { const char* e = getenv(name); return e ? std::optional<uint64_t>(strtoull(e, nullptr, 10)) : std::nullopt; };
-        packer.bounds = gz_bounds(h.batch_bytes, env("MATCHY_AMD_GZ_MAX_MEMBER"), env("MATCHY_AMD_GZ_MAX_CARRY"));
+        // --gz-pieces: a member is inflated by many waves, so it may be as large as a pack holds
+        packer.bounds = (pieces ? gz_bounds_pieces : gz_bounds)(h.batch_bytes, env("MATCHY_AMD_GZ_MAX_MEMBER"), env("MATCHY_AMD_GZ_MAX_CARRY"));
         packer.members = members;
         packer.on_pack = [this](const std::vector<uint8_t>& packed, const std::vector<GzFile>& files) { send(packed, files); };
         // behind the pack in hand and its verdict: as a chain of windows, or the way it is read without the flags
@@ -671,6 +672,11 @@ struct MatchOptions {
     std::string format = "json", extractors, devices;
     bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gz_windows = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
+    // --gz-pieces[=BYTES] (with --gz-on-gpu): one large DEFLATE stream is inflated by many waves, in pieces of BYTES compressed bytes; 0 = off.
+    // The default is the best of the sweep of tools/gz_pieces_timing.py: 4, 8 and 16 KiB lie within 3 % of each other on
+    // level 6 log text, whose blocks have about 32 KiB; from 32 KiB on a piece holds more than one block and the time doubles.
+    uint32_t gz_pieces = 0;
+    static constexpr uint32_t GZ_PIECES_DEFAULT = 8192;
     size_t batch_bytes = (size_t)256 << 20;  // GPU batches: large, so that one launch amortises PCIe latency
     int device = 0;
     int jobs = 0;   // -j N|auto (matchy.rs:98-103: worker threads): scanners here; auto = 2 (summary) / 4 (json) per device listed once
@@ -711,6 +717,13 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
             if (n.empty() || n.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "error: --tally=N needs a number, got '%s'\n", n.c_str()); return 2; }
             o.tally = true; o.tally_limit = strtoull(n.c_str(), nullptr, 10);
         }
+        else if (a == "--gz-pieces") o.gz_pieces = M::GZ_PIECES_DEFAULT;
+        else if (a.compare(0, 12, "--gz-pieces=") == 0) {
+            const std::string n = a.substr(12);
+            const unsigned long long b = n.empty() || n.find_first_not_of("0123456789") != std::string::npos ? 0ull : strtoull(n.c_str(), nullptr, 10);
+            if (b > 0xFFFFFFFFull || !gz_piece_bytes_valid((uint32_t)b)) { fprintf(stderr, "error: --gz-pieces=BYTES needs a power of two from 512 to 1048576, got '%s'\n", n.c_str()); return 2; }
+            o.gz_pieces = (uint32_t)b;
+        }
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); return 2; }
         else o.pos.push_back(a);
     }
@@ -719,9 +732,10 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
     if (o.format != "json" && o.format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", o.format.c_str()); return 1; }
     if (o.gz_windows && !(o.gz_gpu && o.gz_members)) return refuse("--gz-windows needs --gz-on-gpu --gz-members (it extends them to multi-member files larger than a batch)");
     if (o.gz_members && !o.gz_gpu) return refuse("--gz-members needs --gz-on-gpu (it extends the gz packs to files of many members)");
+    if (o.gz_pieces && !o.gz_gpu) return refuse("--gz-pieces needs --gz-on-gpu (it inflates one large stream of a gz pack with many waves)");
     if (o.whole_lines) {
         // the mode has no extraction to configure, and the library refuses it together with segments, gz scans, hit lines and rendered records
-        const char* other = !o.extractors.empty() ? "--extractors" : o.pack ? "--pack-inputs" : o.gz_gpu ? "--gz-on-gpu" : o.gather_lines ? "--gather-lines" : o.render_gpu ? "--render-on-gpu" : nullptr;
+        const char* other = !o.extractors.empty() ? "--extractors" : o.pack ? "--pack-inputs" : o.gz_gpu ? "--gz-on-gpu" : o.gz_pieces ? "--gz-pieces" : o.gather_lines ? "--gather-lines" : o.render_gpu ? "--render-on-gpu" : nullptr;
         if (other) { fprintf(stderr, "Error: --whole-lines is not supported with %s\n", other); return 1; }
     }
     if (o.follow && o.tally) return refuse("--tally is not supported with --follow (the report is printed after the last batch)");
@@ -916,6 +930,7 @@ int cmd_match(int argc, char** argv) {
     if (pl.gather) matchy_multi_scanner_set_hit_lines(ms, true);
     if (o.tally) matchy_multi_scanner_set_tally(ms, true);
     if (o.whole_lines) matchy_multi_scanner_set_whole_lines(ms, true);
+    if (o.gz_pieces) (void)matchy_multi_scanner_set_gz_pieces(ms, o.gz_pieces);   // tested by parse_match_options
     matchy_multi_scanner_set_batch_hook(ms, &MatchPipeline::batch_hook, &pl);
     std::vector<std::string> paths;
     bool stdin_seen = false;
@@ -932,7 +947,7 @@ int cmd_match(int argc, char** argv) {
     pl.line_base.assign(paths.size(), 0);
     pl.consumed.assign(paths.size(), -1);
     HostReader host{pl, paths, o.batch_bytes, std::vector<char>(paths.size(), 0)};
-    GzReader gzr(pl, host, o.gz_members, o.gz_windows);
+    GzReader gzr(pl, host, o.gz_members, o.gz_windows, o.gz_pieces != 0);
     PackStats packed;
     run_inputs(o, pl, host, gzr, packed, t, input_failed);
     uint64_t tally_distinct = 0;

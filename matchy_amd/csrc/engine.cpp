@@ -1555,6 +1555,7 @@ Scanner::GzBatch Scanner::gz_pass(Launch&& launch) {
     MXY_HIP(hipSetDevice(ddb_->device));
     host_stream_.create(hipStreamNonBlocking);
     if (!gz_) gz_ = std::make_unique<GzInflate>();
+    gz_->set_pieces(gz_piece_bytes_);
     launch(*gz_);
     set_segments(gz_->starts().data(), gz_->starts().size());
     return GzBatch{gz_->device_text(), gz_->text_len(), host_stream_};

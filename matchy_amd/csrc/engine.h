@@ -264,6 +264,11 @@ public:
     // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
     void gz_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (gz_) gz_->timing(out_ms); }
     // the same behind a window scan (the third value then includes k_gz_window_tail), and that kernel's own time as a fourth
+    // pieces of one stream (inflate_pieces.hip): 0 = off, otherwise a valid piece size (gz_piece_bytes_valid; the C ABI tests it). It
+    // holds for every gz_inflate* from the next one on: members of at least 2 * piece_bytes compressed bytes are inflated by many waves.
+    void set_gz_pieces(uint32_t piece_bytes) { gz_piece_bytes_ = piece_bytes; }
+    uint32_t gz_pieces() const { return gz_piece_bytes_; }
+    void gz_pieces_timing(float out_ms[6]) const { for (int k = 0; k < 6; ++k) out_ms[k] = 0; if (gz_) gz_->pieces_timing(out_ms); }
     void gz_window_timing(float out_ms[4]) const { gz_timing(out_ms); out_ms[3] = gz_ ? gz_->tail_ms() : 0; }
     // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
     // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.
@@ -412,6 +417,7 @@ private:
     std::unique_ptr<RenderParams> render_pending_;   // set_render, until arm_render takes it
     std::unique_ptr<NdjsonRender> render_;     // created by the first arm_render that arms a scan
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
+    uint32_t gz_piece_bytes_ = 0;
     // what gz_inflate and gz_inflate_files share: device, stream, the pass; launch(GzInflate&) plans and queues; then the segment table
     template <class Launch> GzBatch gz_pass(Launch&& launch);   // engine.cpp only
     // whole-line queries: the buffers of the front end (grown with the candidate list, reused between scans), created by the first scan in the mode

@@ -35,6 +35,16 @@ inline GzBounds gz_bounds(size_t batch_bytes, std::optional<uint64_t> max_member
     return b;
 }
 
+// --gz-pieces: a member is inflated by many waves (inflate_pieces.hip), so one wave's pace no longer bounds it and the member bound is
+// what a pack can hold: max_text, and one byte less than a batch for the separator. carry_cap and max_text are those of gz_bounds
+// (with the overrides, which lower the member bound here as well).
+inline GzBounds gz_bounds_pieces(size_t batch_bytes, std::optional<uint64_t> max_member = {}, std::optional<uint64_t> max_carry = {}) {
+    GzBounds b = gz_bounds(batch_bytes, max_member, max_carry);
+    b.max_member = (size_t)std::min<uint64_t>(b.max_text, b.batch_bytes - 1);
+    if (max_member) b.max_member = (size_t)std::min<uint64_t>(b.max_member, *max_member);
+    return b;
+}
+
 // One file of a gz pack: its index among the inputs, where it lies in the pack, compressed, and what it vouches for: isize is the sum
 // of the ISIZE fields of its `members` members.
 struct GzFile { size_t input; uint64_t offset; uint32_t len, isize; uint32_t members = 1; };

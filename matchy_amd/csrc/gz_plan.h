@@ -273,4 +273,54 @@ inline bool gz_plan_window(const uint8_t* packed, uint64_t packed_len, uint32_t 
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------ pieces of one stream
+// One large member inflated by many waves (inflate_pieces.hip). A member is split when pieces are on and its body has at least
+// 2 * piece_bytes bytes: piece i of it are the compressed bytes [i * piece_bytes, (i + 1) * piece_bytes) of the body, the last one
+// shorter. A split member needs 2 bytes of symbol scratch per byte of its capacity. GZ_PIECE_SCRATCH_MAX bounds the scratch of one scan:
+// 4 GiB = 2 * 2^31 bytes. It follows from the batch bound: a batch holds less than 2^31 bytes of text, so a plan that gz_plan accepts
+// never reaches it, and symbol positions fit 32 bits; it is tested here all the same, so that the rule holds for any table a caller of
+// this function builds. (A lower bound was tried first: at 1 GiB the pack of 64 files of 16 MiB split only half of its members, and the
+// other half set the time of the scan.) Members are taken in claim order, largest first; one that would push the scratch past the
+// bound stays unsplit, and so does an empty one.
+constexpr uint32_t GZ_PIECE_BYTES_MIN = 512, GZ_PIECE_BYTES_MAX = 1u << 20;
+constexpr uint64_t GZ_PIECE_SCRATCH_MAX = 1ull << 32;
+inline bool gz_piece_bytes_valid(uint32_t piece_bytes) {
+    return piece_bytes >= GZ_PIECE_BYTES_MIN && piece_bytes <= GZ_PIECE_BYTES_MAX && (piece_bytes & (piece_bytes - 1)) == 0;
+}
+struct GzPiecePlan {
+    std::vector<uint32_t> split;         // the split members, in table order
+    std::vector<uint32_t> first_piece;   // n_members + 1: the pieces of member i are [first_piece[i], first_piece[i + 1])
+    std::vector<uint32_t> sym_base;      // one per member: where its symbols begin in the scratch (16-bit units)
+    uint64_t scratch_syms = 0;
+};
+// `order` (GzPlan::order) loses the members that are split: they are not k_gz_inflate's in the first launch.
+inline void gz_plan_pieces(const std::vector<GzPlanned>& members, std::vector<uint32_t>& order, uint32_t piece_bytes, GzPiecePlan& pp) {
+    const size_t n = members.size();
+    pp = GzPiecePlan();
+    pp.first_piece.assign(n + 1, 0);
+    pp.sym_base.assign(n, 0);
+    if (!gz_piece_bytes_valid(piece_bytes)) return;
+    std::vector<uint8_t> is_split(n, 0);
+    uint64_t bytes = 0, pieces = 0;
+    for (const uint32_t mi : order) {
+        const GzPlanned& g = members[mi];
+        const uint64_t np = ((uint64_t)g.body_len + piece_bytes - 1) / piece_bytes;
+        if (g.status != GZ_PLAN_OK || g.cap == 0 || g.body_len < 2ull * piece_bytes || bytes + 2ull * g.cap > GZ_PIECE_SCRATCH_MAX || pieces + np > 0x7FFFFFFFull) continue;
+        is_split[mi] = 1;
+        bytes += 2ull * g.cap; pieces += np;
+    }
+    uint64_t first = 0, syms = 0;
+    for (size_t i = 0; i < n; ++i) {
+        pp.first_piece[i] = (uint32_t)first;
+        if (!is_split[i]) continue;
+        pp.split.push_back((uint32_t)i);
+        pp.sym_base[i] = (uint32_t)syms;
+        first += ((uint64_t)members[i].body_len + piece_bytes - 1) / piece_bytes;
+        syms += members[i].cap;
+    }
+    pp.first_piece[n] = (uint32_t)first;
+    pp.scratch_syms = syms;
+    order.erase(std::remove_if(order.begin(), order.end(), [&](uint32_t mi) { return is_split[mi] != 0; }), order.end());
+}
+
 }  // namespace mxy

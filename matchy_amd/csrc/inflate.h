@@ -8,11 +8,13 @@
 
 #include "gz_plan.h"
 #include "hip_owners.h"
+#include "inflate_core.h"
 
 namespace mxy {
 
 // One member as the kernels see it (GzPlanned without the host's status): body / body_len in the compressed buffer, start / cap in the batch.
-// reserved[0]: the member's file in a scan of multi-member files (gz_plan_files), 0 otherwise.
+// reserved[0]: the member's file in a scan of multi-member files (gz_plan_files), 0 otherwise. reserved[1], reserved[2]: the first piece
+// and the piece count of a member that is split (inflate_pieces.hip), 0 and 0 otherwise.
 struct GzMemberDev { uint64_t body; uint32_t body_len, start, cap, reserved[3]; };
 static_assert(sizeof(GzMemberDev) == 32, "one member per 32-byte sector");
 
@@ -47,6 +49,30 @@ constexpr int32_t GZ_WINDOW_OK = 0, GZ_WINDOW_NO_LINE_END = 1;
 hipError_t gz_window_tail_launch(uint8_t* text, uint32_t text_len, uint32_t seg_end, uint32_t carry_len, const int32_t* file_status, uint32_t carry_cap, bool last,
                                  uint8_t* carry_out, uint32_t* result, hipStream_t stream);
 
+// Pieces of one stream (inflate_pieces.hip, gz_plan_pieces): what the seven kernels share. pieces / starts have n_pieces entries, laid out
+// member by member (GzMemberDev::reserved[1..2]); split[0, n_split) are the split members; complete / failed / crc have one word per
+// member; scratch[0, scratch_len) are the 16-bit symbols, a member's at gz::Piece::sym_base. The launches run in this order on one
+// stream, behind the copies of packed bytes and tables: find, count, chain, symbols, windows, resolve, verdict. The verdict writes
+// GZ_OK for a member whose pieces gave its text, and for every other split member its index into handover[0, n_split) — filled up with
+// 0xFFFFFFFF — which gz_inflate_launch then takes as its order list. Nothing is loaded outside packed[0, packed_len), nothing stored
+// outside text[0, text_len), scratch[0, scratch_len) and the tables.
+struct GzPieceArgs {
+    const uint8_t* packed; uint64_t packed_len;
+    const GzMemberDev* members; uint32_t n_members;
+    gz::Piece* pieces; uint64_t* starts; uint32_t n_pieces, piece_bytes;
+    const uint32_t* split; uint32_t n_split;
+    uint32_t *complete, *failed, *crc;
+    uint16_t* scratch; uint64_t scratch_len;
+    uint8_t* text; uint32_t text_len;
+};
+hipError_t gz_piece_find_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_count_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_chain_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_symbols_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_windows_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_resolve_launch(const GzPieceArgs& a, hipStream_t stream);
+hipError_t gz_piece_verdict_launch(const GzPieceArgs& a, int32_t* status, uint32_t* handover, hipStream_t stream);
+
 // The gz pass of a scanner (Scanner::gz_inflate): the plan of the pack in flight and the buffers of the pass, grown on demand and reused
 // between scans. A scan runs as launch() in front of the scan's kernels, queue_results() behind them on the same stream and finish()
 // behind the wait. Not thread-safe, like the scanner. Throws mxy::HipError and, for a table that breaks its rules, mxy::ParamError.
@@ -63,6 +89,11 @@ public:
     // segment 0 of the scan.
     void launch_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last, int n_cu, bool profile,
                        hipStream_t stream);
+    // Pieces of one stream: 0 = off (the default), otherwise a power of two in [GZ_PIECE_BYTES_MIN, GZ_PIECE_BYTES_MAX]
+    // (gz_piece_bytes_valid). From the next launch on, every member of at least 2 * piece_bytes compressed bytes is split
+    // (gz_plan_pieces) and inflated by one wave per piece; with 0 no piece kernel is launched and nothing of them is allocated.
+    void set_pieces(uint32_t piece_bytes) { piece_bytes_ = piece_bytes; }
+    uint32_t pieces() const { return piece_bytes_; }
     const uint8_t* device_text() const { return text_.p; }
     uint32_t text_len() const { return (uint32_t)plan_.total; }
     const std::vector<uint32_t>& starts() const { return plan_.starts; }
@@ -77,13 +108,19 @@ public:
                     const int32_t* file_status = nullptr; size_t n_files = 0; const uint32_t* first_member = nullptr;
                     // behind launch_window(): the window's status (GZ_WINDOW_*) and its carry, borrowed like status. ok_bytes is then
                     // carry_len + capacities - carry_len of the result (0 for a failed window or NO_LINE_END), not_input_nl the rest of the batch
-                    bool window = false; int32_t window_status = 0; const uint8_t* carry = nullptr; uint32_t carry_len = 0; };
+                    bool window = false; int32_t window_status = 0; const uint8_t* carry = nullptr; uint32_t carry_len = 0;
+                    // pieces of one stream: the table of the launch (empty with pieces off or no member split), borrowed like status;
+                    // the pieces of member i are [first_piece[i], first_piece[i + 1]), n + 1 entries
+                    const gz::Piece* pieces = nullptr; size_t n_pieces = 0; const uint32_t* first_piece = nullptr; };
     Result finish();
     // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal (k_gz_file_verdict + k_gz_seal_files
     // behind launch_files) of the last profiled launch
     void timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = ms_[k]; }
     // behind launch_window() the third value includes k_gz_window_tail; this is that kernel's own time (0 behind any other launch)
     float tail_ms() const { return tail_ms_; }
+    // pieces: find, count, chain, symbols, windows + resolve + verdict, handover inflate of the last profiled launch; zeros with pieces
+    // off or no member split. (These times are part of timing()'s first value.)
+    void pieces_timing(float out_ms[6]) const { for (int k = 0; k < 6; ++k) out_ms[k] = piece_ms_[k]; }
 
 private:
     void inflate_files(GzFilesPlan& fp, const uint8_t* packed, size_t packed_len, int n_cu, bool profile, hipStream_t stream);
@@ -112,6 +149,19 @@ private:
     PinnedBuf<uint32_t> window_result_pinned_;
     Event ev_tail_;
     float tail_ms_ = 0;
+    // pieces of one stream: nothing below is allocated while piece_bytes_ is 0
+    void inflate_pieces(size_t packed_len, int n_cu, bool profile, hipStream_t stream);
+    uint32_t piece_bytes_ = 0;
+    GzPiecePlan piece_plan_;
+    std::vector<gz::Piece> pieces_host_;
+    DevBuf<gz::Piece> pieces_;
+    DevBuf<uint64_t> piece_starts_;
+    DevBuf<uint32_t> split_, handover_, member_words_, handover_counter_;   // member_words_: complete, failed, crc
+    DevBuf<uint16_t> scratch_;
+    PinnedBuf<gz::Piece> pieces_pinned_;
+    Event ev_piece_[7];
+    bool pieces_timed_ = false;
+    float piece_ms_[6] = {0, 0, 0, 0, 0, 0};
     float ms_[3] = {0, 0, 0};
     bool timed_ = false, with_text_ = false;
     int waves_per_cu_ = 0;

@@ -328,5 +328,246 @@ MXY_HD uint32_t crc_lane_part(const uint32_t* table, const uint8_t* out, uint32_
     return crc_mul(crc_bytes(table, out + begin, len), crc_xpow8(n - begin - len));
 }
 
+// ------------------------------------------------------------------------------------------------ pieces of one stream
+// One large member is cut into pieces of piece_bytes compressed bytes (inflate_pieces.hip). Piece 0 starts at bit 0 of the body; every
+// other piece starts at the first bit position inside it where a dynamic block header parses (piece_probe), if there is one. Every piece
+// is decoded from its start with no knowledge of the 32 KiB in front of it: a back-reference that reaches in front of the piece's first
+// byte becomes a MARKER symbol (256 + k: byte k of those 32 KiB). A piece stops at the first block end that is the start of a later
+// piece; the pieces reached from piece 0 by following these landings are LIVE, and because every live piece starts at the bit where the
+// one in front ended, a chain that reaches the end of the final block is the sequential parse of the stream. A false start is never live.
+//
+// Loop bounds: the probe reads at most 74 bits in front of read_dynamic; a piece decoder consumes at least one input bit per token or
+// block header (the turn bound of its callers is 8 * body_len + 2, as for decode_batch), ends at the member's end or capacity, and —
+// any piece but piece 0 — after it has passed GZ_PIECE_MAX_SKIP candidate starts without landing on one.
+
+// Bit positions are relative to the member's body and 64-bit: a body of 4 GiB has 2^35 of them.
+MXY_HD uint64_t br_bit_pos(const BitReader& b) { return (uint64_t)b.pos * 8u - b.cnt; }
+MXY_HD void br_seek_bit(BitReader& b, uint64_t bit) {
+    const uint64_t byte = bit >> 3;
+    br_seek(b, byte < b.end ? (uint32_t)byte : b.end);
+    const uint32_t drop = (uint32_t)bit & 7u;
+    if (!drop || byte >= b.end) return;
+    br_fill(b);   // at least one byte: cnt >= 8 > drop
+    b.buf >>= drop; b.cnt -= drop;
+}
+
+// n <= 24 bits at bit position `bit` of in[0, end), low bit first; false: the input ends first
+MXY_HD bool peek_bits(const uint8_t* in, uint32_t end, uint64_t bit, uint32_t n, uint32_t& v) {
+    if (bit + n > (uint64_t)end * 8u) return false;
+    const uint32_t at = (uint32_t)(bit >> 3), sh = (uint32_t)bit & 7u;
+    uint32_t w = 0;
+    for (uint32_t k = 0; k < 4u && at + k < end; ++k) w |= (uint32_t)in[at + k] << (8u * k);
+    v = (w >> sh) & ((1u << n) - 1u);
+    return true;
+}
+
+// The cheap test in front of the probe: any BFINAL, BTYPE = 2, HLIT <= 29, HDIST <= 29 and a code-length code whose Kraft sum is exactly
+// 1 (build_code refuses every other one for CODE_LENGTHS). 17 + 3 * (HCLEN + 4) <= 74 bits, nothing stored.
+MXY_HD bool piece_probe_cheap(const uint8_t* in, uint32_t end, uint64_t bit) {
+    uint32_t h;
+    if (!peek_bits(in, end, bit, 17, h)) return false;
+    if (((h >> 1) & 3u) != 2u || ((h >> 3) & 31u) > 29u || ((h >> 8) & 31u) > 29u) return false;
+    const uint32_t hclen = ((h >> 13) & 15u) + 4u;
+    uint32_t kraft = 0;   // in units of 2^-7
+    for (uint32_t i = 0; i < hclen; i += 8u) {   // <= 3 turns of <= 8 lengths
+        const uint32_t n = hclen - i < 8u ? hclen - i : 8u;
+        uint32_t w;
+        if (!peek_bits(in, end, bit + 17u + 3u * i, 3u * n, w)) return false;
+        for (uint32_t k = 0; k < n; ++k) { const uint32_t l = (w >> (3u * k)) & 7u; if (l) kraft += 128u >> l; }
+    }
+    return kraft == 128u;
+}
+// A block start at `bit`: the cheap test, then a dynamic header that read_dynamic accepts. Stored and fixed blocks have no findable
+// start: the piece in front decodes them. t is scratch.
+MXY_HD bool piece_probe(const uint8_t* in, uint32_t end, uint64_t bit, Tables& t) {
+    if (!piece_probe_cheap(in, end, bit)) return false;
+    BitReader b;
+    b.in = in; b.end = end;
+    br_seek_bit(b, bit + 3u);
+    return read_dynamic(b, t) == GZ_OK;
+}
+
+// A piece that is no piece 0 gives up after it has passed this many candidate starts without landing on one. A true start lands on the
+// next true start; between two true starts lie only false candidates, which the probe rarely lets through (none in the 1 MB of
+// compressed log text of the test vectors; the dead candidates of the false-start vector are genuine headers inside a stored
+// payload). 8 passed candidates therefore mean a run of 8 pieces' worth of stored or fixed blocks or of false starts — a false start that
+// happens to decode on is cut off after about 8 pieces of input in place of the member's rest, and a true start that gives up only
+// makes its member take the one-wave path, which is always right.
+constexpr uint32_t GZ_PIECE_MAX_SKIP = 8;
+constexpr uint32_t GZ_PIECE_WINDOW = 32768;
+constexpr uint32_t GZ_PIECE_QUEUE = 64;   // tokens per call of piece_decode_batch, for the kernels and the CPU driver alike
+constexpr uint64_t GZ_PIECE_NO_START = ~0ull;
+constexpr uint32_t GZ_PIECE_END = 0xFFFFFFFFu, GZ_PIECE_NONE = 0xFFFFFFFEu;   // landed on the end of the final block; not landed
+constexpr int32_t GZ_PIECE_NO_LANDING = 11;   // internal to the piece table, never a member's status
+
+// A symbol of the scratch: 0..255 a byte, 256 + k byte k of the GZ_PIECE_WINDOW bytes in front of the piece's first byte.
+constexpr uint32_t GZ_SYM_MARKER = 256;
+// Symbol i of a match at piece position `pos`: the index of the symbol it copies, or (negative) -1 - k for window byte k.
+MXY_HD int32_t piece_match_src(uint32_t pos, uint32_t dist, uint32_t i) {
+    const int64_t src = (int64_t)pos - (int64_t)dist + (int64_t)(i < dist ? i : i % dist);
+    return src >= 0 ? (int32_t)src : (int32_t)(-1 - ((int64_t)GZ_PIECE_WINDOW + src));
+}
+
+// decode_batch for a piece: it starts at start_bit with produced = 0, allows a distance up to `window` bytes in front of the piece
+// (0 for piece 0, which keeps the rule of decode_batch), and stops at a block end that is a candidate start behind it.
+// starts[0, n_pieces) are the pieces' start bits, sorted by construction (piece i's lies inside piece i), GZ_PIECE_NO_START for none.
+struct PieceDecoder {
+    Decoder d;
+    const uint64_t* starts;
+    uint32_t n_pieces, self, nc;   // nc: the first piece behind `self` whose start has not been passed
+    uint32_t window, skipped, landed;
+    uint64_t end_bit;
+};
+MXY_HD void piece_decoder_init(PieceDecoder& p, const uint8_t* in, uint32_t in_len, uint32_t cap, const uint64_t* starts, uint32_t n_pieces, uint32_t self, uint64_t start_bit) {
+    decoder_init(p.d, in, in_len, cap);
+    br_seek_bit(p.d.br, start_bit);
+    p.starts = starts; p.n_pieces = n_pieces; p.self = self; p.nc = self + 1u;
+    p.window = self ? GZ_PIECE_WINDOW : 0u;
+    p.skipped = 0; p.landed = GZ_PIECE_NONE; p.end_bit = start_bit;
+}
+// Counts the candidates in front of bit `at`: no block end can land on them any more. Every turn advances nc.
+MXY_HD void piece_pass_candidates(PieceDecoder& p, uint64_t at) {
+    while (p.nc < p.n_pieces && (p.starts[p.nc] == GZ_PIECE_NO_START || p.starts[p.nc] < at)) {
+        if (p.starts[p.nc] != GZ_PIECE_NO_START) ++p.skipped;
+        ++p.nc;
+    }
+    if (p.self && p.skipped >= GZ_PIECE_MAX_SKIP) p.d.status = GZ_PIECE_NO_LANDING;
+}
+// At a block end (the final block's aside): lands on a candidate at this bit, or counts the candidates passed.
+MXY_HD void piece_block_end(PieceDecoder& p) {
+    const uint64_t at = br_bit_pos(p.d.br);
+    piece_pass_candidates(p, at);
+    if (p.d.status == GZ_OK && p.nc < p.n_pieces && p.starts[p.nc] == at) { p.landed = p.nc; p.d.done = true; }
+}
+// Decodes until the queue is full, a stored run is due, the piece has landed or the stream has ended (d.done, p.landed), or an error.
+// A match token's `pos` is relative to the piece; its distance may exceed pos by up to p.window.
+MXY_HD void piece_decode_batch(PieceDecoder& p, Tables& t, Token* q, uint32_t max_q, Batch& out) {
+    Decoder& d = p.d;
+    BitReader& b = d.br;
+    out.n = 0; out.stored_src = 0; out.stored_len = 0; out.stored_pos = 0;
+    uint32_t v;
+    // once per call, inside a block too: a false start whose block never ends gives up max_q tokens behind the last candidate it may
+    // pass, not at the member's capacity. Where a piece gives up therefore depends on max_q, which is GZ_PIECE_QUEUE for every caller.
+    if (!d.done && d.status == GZ_OK) piece_pass_candidates(p, br_bit_pos(b));
+    while (out.n < max_q && !d.done && d.status == GZ_OK) {
+        if (!d.in_block) {
+            uint32_t type;
+            if (!br_take(b, 1, v) || !br_take(b, 2, type)) { d.status = GZ_TRUNCATED; break; }
+            d.final = v != 0;
+            if (type == 0) {
+                uint32_t len, nlen;
+                (void)br_align(b);
+                if (!br_take(b, 16, len) || !br_take(b, 16, nlen)) { d.status = GZ_TRUNCATED; break; }
+                if ((len ^ 0xFFFFu) != nlen) { d.status = GZ_BAD_BLOCK; break; }
+                const uint32_t at = br_align(b);
+                if (len > b.end - at) { d.status = GZ_TRUNCATED; break; }
+                if (len > d.cap - d.produced) { d.status = GZ_OVERFLOW; break; }
+                br_seek(b, at + len);
+                out.stored_src = at; out.stored_len = len; out.stored_pos = d.produced;
+                d.produced += len;
+                if (d.final) { d.done = true; p.landed = GZ_PIECE_END; } else piece_block_end(p);
+                if (len) break;   // what follows may copy from these bytes: they are written first
+            } else if (type == 1) {
+                d.status = build_fixed(t);
+                d.in_block = true;
+            } else if (type == 2) {
+                d.status = read_dynamic(b, t);
+                d.in_block = true;
+            } else d.status = GZ_BAD_BLOCK;
+            continue;
+        }
+        const int s = decode_lit(b, t);
+        if (s < 0) { d.status = s == SYM_TRUNCATED ? GZ_TRUNCATED : GZ_BAD_SYMBOL; break; }
+        if (s < 256) {
+            if (d.produced >= d.cap) { d.status = GZ_OVERFLOW; break; }
+            q[out.n].pos = d.produced++; q[out.n].v = (uint32_t)s; ++out.n;
+            continue;
+        }
+        if (s == 256) {
+            d.in_block = false;
+            if (d.final) { d.done = true; p.landed = GZ_PIECE_END; } else piece_block_end(p);
+            continue;
+        }
+        if (s >= 286) { d.status = GZ_BAD_SYMBOL; break; }
+        const uint32_t ls = (uint32_t)s - 257u;
+        uint32_t len = 3u + ls;
+        if (ls == 28u) len = 258u;
+        else if (ls >= 8u) {
+            const uint32_t eb = (ls >> 2) - 1u;
+            if (!br_take(b, eb, v)) { d.status = GZ_TRUNCATED; break; }
+            len = 3u + ((4u + (ls & 3u)) << eb) + v;
+        }
+        const int ds = decode_sym(b, t.dist_count, t.dist_sym);
+        if (ds < 0) { d.status = ds == SYM_TRUNCATED ? GZ_TRUNCATED : GZ_BAD_SYMBOL; break; }
+        if (ds >= 30) { d.status = GZ_BAD_SYMBOL; break; }
+        uint32_t dist = 1u + (uint32_t)ds;
+        if (ds >= 4) {
+            const uint32_t eb = ((uint32_t)ds >> 1) - 1u;
+            if (!br_take(b, eb, v)) { d.status = GZ_TRUNCATED; break; }
+            dist = 1u + ((2u + ((uint32_t)ds & 1u)) << eb) + v;
+        }
+        if (dist > d.produced && dist - d.produced > p.window) { d.status = GZ_BAD_DISTANCE; break; }
+        if (len > d.cap - d.produced) { d.status = GZ_OVERFLOW; break; }
+        q[out.n].pos = d.produced; q[out.n].v = TOKEN_MATCH | len | dist << 9; ++out.n;
+        d.produced += len;
+    }
+    if (d.done || d.status != GZ_OK) p.end_bit = br_bit_pos(b);
+}
+
+// One piece as the passes hand it on. Filled by the find (start_bit, FLAG_START), the count (end_bit, next, produced, status), the chain
+// (out_pos, FLAG_LIVE) and the verdict (FLAG_HANDED); member and sym_base come from the host. The first 32 bytes are matchy_gz_piece_t.
+struct Piece {
+    uint64_t start_bit, end_bit;
+    uint32_t member, produced, out_pos, flags;
+    uint32_t next, crc, sym_base;   // sym_base: where the member's symbols begin in the scratch
+    int32_t status;
+};
+static_assert(sizeof(Piece) == 48, "matchy_gz_piece_t and the passes' own four words");
+constexpr uint32_t PIECE_HAS_START = 1, PIECE_LIVE = 2, PIECE_HANDED = 4;
+
+// The find for piece i of a member whose body has body_len bytes: the first candidate in [i * piece_bytes * 8, (i + 1) * piece_bytes * 8)
+// and in front of the body's end. At most 8 * piece_bytes offsets. (The kernel tries 64 per turn; the result is the same.)
+MXY_HD uint64_t piece_find(const uint8_t* in, uint32_t body_len, uint32_t piece_bytes, uint32_t i, Tables& t) {
+    if (i == 0) return 0;
+    const uint64_t lo = (uint64_t)i * piece_bytes * 8u, total = (uint64_t)body_len * 8u;
+    const uint64_t hi = lo + (uint64_t)piece_bytes * 8u < total ? lo + (uint64_t)piece_bytes * 8u : total;
+    for (uint64_t bit = lo; bit < hi; ++bit) if (piece_probe(in, body_len, bit, t)) return bit;
+    return GZ_PIECE_NO_START;
+}
+
+// The chain of one member over pieces[0, n): walks from piece 0 along `next` (strictly increasing: at most n turns), sets out_pos and
+// PIECE_LIVE, and returns whether the chain is complete: it reaches the end of the final block through pieces that are all OK, their
+// bytes sum to `cap`, and exactly the 8 bytes of a trailer whose ISIZE is `cap` follow the last block's last byte. (The CRC is the
+// resolve pass's.)
+MXY_HD bool piece_chain(Piece* pieces, uint32_t n, const uint8_t* in, uint32_t body_len, uint32_t cap) {
+    uint64_t sum = 0;
+    uint32_t i = 0;
+    for (uint32_t turn = 0; turn < n; ++turn) {
+        Piece& p = pieces[i];
+        if (!(p.flags & PIECE_HAS_START) || p.status != GZ_OK || sum + p.produced > cap) return false;
+        p.out_pos = (uint32_t)sum; p.flags |= PIECE_LIVE;
+        sum += p.produced;
+        if (p.next == GZ_PIECE_END) {
+            const uint64_t at = (p.end_bit + 7u) >> 3;
+            if (sum != cap || at > body_len || body_len - at != 8u) return false;
+            const uint8_t* t = in + at + 4;
+            return ((uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24) == cap;
+        }
+        if (p.next <= i || p.next >= n) return false;
+        i = p.next;
+    }
+    return false;
+}
+
+// A symbol to its byte: text[0, cap) is the member's text, pos the symbol's position in it, piece_pos its piece's out_pos. False: a
+// marker that points in front of the member's first byte (the sequential path calls it BAD_DISTANCE).
+MXY_HD bool piece_resolve_sym(uint32_t sym, const uint8_t* text, uint32_t piece_pos, uint8_t& byte) {
+    if (sym < GZ_SYM_MARKER) { byte = (uint8_t)sym; return true; }
+    const uint32_t k = sym - GZ_SYM_MARKER;
+    if (k >= GZ_PIECE_WINDOW || piece_pos + k < GZ_PIECE_WINDOW) return false;
+    byte = text[piece_pos - GZ_PIECE_WINDOW + k];
+    return true;
+}
+
 }  // namespace gz
 }  // namespace mxy

@@ -86,6 +86,7 @@ struct MultiScanner {
     bool hit_lines = false;  // matchy_multi_scanner_set_hit_lines: likewise
     bool tally = false, tally_ever = false;   // matchy_multi_scanner_set_tally: likewise
     bool whole_lines = false;   // matchy_multi_scanner_set_whole_lines: likewise
+    uint32_t gz_pieces = 0;     // matchy_multi_scanner_set_gz_pieces: likewise, before a gz scan
     std::shared_ptr<const RenderSpec> render_next;   // matchy_multi_scanner_set_render: goes with the next batch submitted
     matchy_multi_batch_fn hook = nullptr;
     void* hook_user = nullptr;
@@ -106,6 +107,7 @@ struct MultiScanner {
         for (;;) {
             MultiJob j{};
             bool want_lines = false, want_hit_lines = false, want_tally = false, touch_tally = false, want_whole_lines = false;
+            uint32_t want_gz_pieces = 0;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return closing || !q.empty(); });
@@ -120,6 +122,7 @@ struct MultiScanner {
                 want_lines = line_ctx; want_hit_lines = hit_lines;
                 want_tally = tally; touch_tally = tally_ever;
                 want_whole_lines = whole_lines;
+                want_gz_pieces = gz_pieces;
             }
             MultiDone d;
             d.data = j.data; d.len = j.len; d.tag = j.tag; d.worker = w;
@@ -134,6 +137,7 @@ struct MultiScanner {
                 matchy_scanner_set_line_context(sc, want_lines || (j.is_gz() && j.render && !j.gz_text));
                 matchy_scanner_set_hit_lines(sc, want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(sc, want_tally);
+                if (j.is_gz()) (void)matchy_scanner_set_gz_pieces(sc, want_gz_pieces);   // tested by matchy_multi_scanner_set_gz_pieces
                 if (j.kind == JobKind::SEGMENTS) d.status = matchy_scanner_set_segments(sc, j.starts.data(), j.starts.size());
                 if (j.render) j.render->arm(sc);
                 const matchy_gz_window_t window{j.carry.data(), (uint32_t)j.carry.size(), j.carry_cap, j.window_flags};
@@ -224,6 +228,14 @@ void matchy_multi_scanner_set_hit_lines(matchy_multi_scanner_t* h, bool enabled)
     MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
     std::lock_guard<std::mutex> lk(ms->mu);
     ms->hit_lines = enabled;
+}
+int32_t matchy_multi_scanner_set_gz_pieces(matchy_multi_scanner_t* h, uint32_t piece_bytes) {
+    if (!h) return MATCHY_ERROR_INVALID_PARAM;
+    if (piece_bytes && !gz_piece_bytes_valid(piece_bytes)) { set_error("matchy_multi_scanner_set_gz_pieces: piece_bytes is 0 or a power of two from 512 to 1 MiB"); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiScanner* ms = reinterpret_cast<MultiScanner*>(h);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    ms->gz_pieces = piece_bytes;
+    return MATCHY_SUCCESS;
 }
 // Rendered records: the parameters arm the NEXT batch submitted (whichever submit call that is) and no other; the worker that takes
 // the batch arms its scanner with them. The result of the batch owns the block (matchy_scan_result_ndjson).
