@@ -8,9 +8,12 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <list>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "capi_internal.h"
@@ -19,15 +22,9 @@
 #include "engine.h"
 #include "host_lookup.h"
 #include "inflate_core.h"
+#include "ndjson_host.h"
 #include "netaddr.h"
 #include "render_core.h"
-#include "utf8_lossy.h"
-
-#include <deque>
-#include <list>
-#include <thread>
-#include <unordered_map>
-#include <unordered_set>
 
 using namespace mxy;
 using namespace mxy::capi;
@@ -125,10 +122,7 @@ struct MatchesInternal {
 struct ScannerH {
     const Db* db;
     std::unique_ptr<Scanner> sc;
-    // matchy_scan_result_to_ndjson: the JSON text of an entry's data by its data-section offset (indicator lists carry a few hundred
-    // distinct payloads for millions of hits: decoding the MMDB value and serialising it per hit was most of the rendering time)
-    std::unordered_map<uint32_t, std::string> json_of_data;
-    std::string json_source, json_source_of;   // the last source name, JSON-escaped
+    ndjson::Renderer ndjson;   // matchy_scan_result_to_ndjson*: the payload texts and the escaped source live across calls
     // matchy_scanner_submit_device -> matchy_scanner_wait
     bool pending = false;
     size_t pending_len = 0;
@@ -214,10 +208,16 @@ static_assert(sizeof(FinalHit) == sizeof(matchy_scan_hit_t) && sizeof(FinalHit) 
                   offsetof(FinalHit, n_ids) == offsetof(matchy_scan_hit_t, n_ids) && offsetof(FinalHit, kind) == offsetof(matchy_scan_hit_t, kind),
               "pack_record writes matchy_scan_hit_t records directly");
 
-// Hand the dense records to the caller. borrowed=true: pointers go straight to the scanner's pinned buffers (no per-hit
-// host work at all); otherwise the arrays are copied into the result and optionally put into canonical order.
-void fill_result(const FinalHit* fin, size_t n_fin, const uint32_t* ids, const long long* offs, size_t n_ids, uint64_t lines, uint64_t cands,
-                 uint64_t bytes, bool borrowed, bool sorted, matchy_scan_result_t* out) {
+// the internal block of a result, created where its arrays are borrowed
+ScanResultInternal* internal_of(matchy_scan_result_t* out) {
+    if (!out->_internal) out->_internal = new ScanResultInternal();
+    return reinterpret_cast<ScanResultInternal*>(out->_internal);
+}
+
+// Hand the dense records to the caller. borrowed=true: pointers go straight to the scanner's pinned buffers (no per-hit host work at all);
+// otherwise the arrays are copied into the result (canonical order is produced on the GPU, sort_hits.hip: the copy keeps it).
+void fill_result(const FinalHit* fin, size_t n_fin, const uint32_t* ids, const long long* offs, size_t n_ids, uint64_t lines, uint64_t cands, uint64_t bytes, bool borrowed,
+                 matchy_scan_result_t* out) {
     memset(out, 0, sizeof(*out));
     out->lines = lines; out->candidates = cands; out->bytes = bytes;
     out->n_hits = n_fin; out->n_ids = n_ids;
@@ -227,47 +227,42 @@ void fill_result(const FinalHit* fin, size_t n_fin, const uint32_t* ids, const l
         out->data_offsets = reinterpret_cast<const int64_t*>(offs);
         return;
     }
-    auto* in = new ScanResultInternal();
+    ScanResultInternal* in = internal_of(out);
     in->hits.resize(n_fin);
     if (n_fin) memcpy(in->hits.data(), fin, n_fin * sizeof(FinalHit));
     in->ids.assign(ids, ids + n_ids);
     in->offs.assign(offs, offs + n_ids);
-    (void)sorted;  // canonical order is produced on the GPU (sort_hits.hip); the copy keeps it
     out->hits = in->hits.data();
     out->pattern_ids = in->ids.data(); out->data_offsets = in->offs.data();
-    out->_internal = in;
 }
 
-// MATCHY_SCAN_FETCH_COMPACT only means something for unsorted host-resident records
-bool compact_mode(uint32_t fetch_mode) { return (fetch_mode & MATCHY_SCAN_FETCH_COMPACT) && (fetch_mode & 7u) == MATCHY_SCAN_FETCH_HITS; }
-
-// fetch_mode MATCHY_SCAN_FETCH_DEVICE: the records stay where the lookup kernel wrote them (device memory); only the counters
-// come back.
-void fill_device_result(Scanner& sc, const ScanOutput& so, uint64_t bytes, matchy_scan_result_t* out) {
-    memset(out, 0, sizeof(*out));
-    out->lines = so.lines; out->candidates = so.n_cand; out->bytes = bytes;
-    out->n_hits = so.n_hits; out->n_ids = sc.device_final_id_count();
-    out->hits = reinterpret_cast<const matchy_scan_hit_t*>(sc.device_final());
-    out->pattern_ids = sc.device_final_ids();
-    out->data_offsets = reinterpret_cast<const int64_t*>(sc.device_final_offs());
-    auto* in = new ScanResultInternal();   // marks the residency: host-side readers of the result refuse device pointers
-    in->on_device = true;
-    out->_internal = in;
-}
+// What a fetch mode asks for, decoded once. The arrays a result hands out all lie in one place: device memory, the scanner's pinned
+// blocks (borrowed: no per-hit host work at all), or copies the result owns.
+enum class Placement { DEVICE, BORROWED, OWNED };
+struct FetchPlan {
+    bool records, sorted, device, compact;
+    explicit FetchPlan(uint32_t fetch_mode)
+        : records(fetch_mode & 1u), sorted(fetch_mode & 2u), device((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE),
+          // MATCHY_SCAN_FETCH_COMPACT only means something for unsorted host-resident records
+          compact((fetch_mode & MATCHY_SCAN_FETCH_COMPACT) && (fetch_mode & 7u) == MATCHY_SCAN_FETCH_HITS) {}
+    // which fetches render and gather hit lines: those that hand records out (on the host or on the device), not a counts-only fetch
+    bool renders() const { return records || device; }
+    HitMode hit_mode() const { return records ? HITS_FINAL : HITS_NONE; }
+    Placement placement() const { return device ? Placement::DEVICE : sorted ? Placement::OWNED : Placement::BORROWED; }
+};
 
 static_assert(sizeof(LineRec) == sizeof(matchy_scan_line_t) && offsetof(LineRec, line_end) == offsetof(matchy_scan_line_t, line_end), "k_line_resolve writes matchy_scan_line_t records directly");
 
 // Line context of a scan_device / wait result: the result gets (or keeps) its internal block; the arrays follow the hit arrays of the
 // same result — device pointers, the scanner's pinned block, or an owned copy.
-void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, matchy_scan_result_t* out) {
+void attach_lines(Scanner& sc, const ScanOutput& so, Placement at, matchy_scan_result_t* out) {
     if (!so.has_lines) return;
-    if (!out->_internal) out->_internal = new ScanResultInternal();
-    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    ScanResultInternal* in = internal_of(out);
     in->has_lines = true;
     in->lines_with_matches = so.lines_with_matches;
-    if (device) {
+    if (at == Placement::DEVICE) {
         in->lines = out->n_hits ? reinterpret_cast<const matchy_scan_line_t*>(sc.device_lines()) : nullptr;
-    } else if (owned) {
+    } else if (at == Placement::OWNED) {
         if (so.fin_lines) in->lines_own.assign(reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines), reinterpret_cast<const matchy_scan_line_t*>(so.fin_lines) + so.n_fin);
         in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
     } else {
@@ -276,35 +271,38 @@ void attach_lines(Scanner& sc, const ScanOutput& so, bool device, bool owned, ma
     }
 }
 
-// Hit lines. What the scan entries ask of the engine for a fetch mode: the setting turns line context on for the scan, and a fetch that
-// hands out no records (MATCHY_SCAN_FETCH_COUNTS) gathers nothing. Returns the setting, which the entry hands to attach_hit_lines.
-bool request_lines(const Scanner& sc, uint32_t fetch_mode, ScanRequest& rq) {
+// The request of a lookup scan of [ptr, ptr + len) on `stream` for a fetch plan, with whole lines, segments and render armed. The hit-lines
+// setting turns line context on for the scan, and a fetch that hands out no records (MATCHY_SCAN_FETCH_COUNTS) gathers nothing; the
+// setting is returned for finish_result. fork: the entry forks the scan into slices() (one batch in flight; ScanRequest::fork).
+// behind_gz: the scan shares the stream of the inflate kernels, and whole lines were armed (or refused) in front of them.
+bool build_request(Scanner& sc, const FetchPlan& plan, const uint8_t* ptr, size_t len, hipStream_t stream, bool fork, bool behind_gz, ScanRequest& rq) {
+    rq.ptr = ptr; rq.len = (uint32_t)len; rq.lookup = true;
+    rq.host_mirror = plan.records && !plan.sorted; rq.compact = plan.compact;
+    if (fork) { rq.fork = true; rq.slices = sc.slices(); }
     rq.lines = sc.line_context() || sc.hit_lines();
-    rq.hit_lines = sc.hit_lines() && ((fetch_mode & 1u) || (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE);
+    rq.hit_lines = sc.hit_lines() && plan.renders();
+    if (!behind_gz) sc.arm_whole_lines(rq);
+    sc.arm_segments(len, stream);
+    sc.arm_render(rq, plan.renders(), stream);
     return sc.hit_lines();
 }
 
-// which fetches render: those that hand records out (on the host or on the device), not a counts-only fetch
-bool fetch_renders(uint32_t fetch_mode) { return (fetch_mode & 1u) || (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE; }
-
 // The rendered block of a result whose scan was armed: it follows the hit arrays of the same result.
-void attach_render(const ScanOutput& so, bool owned, matchy_scan_result_t* out) {
+void attach_render(const ScanOutput& so, Placement at, matchy_scan_result_t* out) {
     if (!so.render.armed) return;
-    if (!out->_internal) out->_internal = new ScanResultInternal();
-    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    ScanResultInternal* in = internal_of(out);
     in->has_render = true;
     in->render_status = (int32_t)so.render.status;
     in->render_len = so.render.len;
     in->render_text = so.render.text;
-    if (owned && so.render.text) { in->render_own.assign(so.render.text, so.render.text + so.render.len); in->render_text = in->render_own.data(); }
+    if (at == Placement::OWNED && so.render.text) { in->render_own.assign(so.render.text, so.render.text + so.render.len); in->render_text = in->render_own.data(); }
 }
 
 // Hit lines of a result (`wanted`: the setting of its scan): the block and its arrays follow the hit arrays of the same result — device
 // pointers, the scanner's pinned blocks, or an owned copy. A scan that gathered nothing answers with the count alone.
-void attach_hit_lines(const ScanOutput& so, bool wanted, bool owned, matchy_scan_result_t* out) {
+void attach_hit_lines(const ScanOutput& so, bool wanted, Placement at, matchy_scan_result_t* out) {
     if (!wanted) return;
-    if (!out->_internal) out->_internal = new ScanResultInternal();
-    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    ScanResultInternal* in = internal_of(out);
     in->has_hit_lines = true;
     matchy_scan_hit_lines_t& h = in->hit_lines;
     h = matchy_scan_hit_lines_t{};
@@ -313,7 +311,7 @@ void attach_hit_lines(const ScanOutput& so, bool wanted, bool owned, matchy_scan
     const HitLinesView& v = so.hit_lines;
     h.text = v.text; h.text_len = v.text_len; h.n_lines = v.n_lines;
     h.line_off = v.line_off; h.line_no = v.line_no; h.line_of_hit = v.line_of_fin; h.line_of_ip4_hit = v.line_of_c4;
-    if (!owned) return;   // an owned result has no compact records
+    if (at != Placement::OWNED) return;   // an owned result has no compact records
     if (v.text_len) in->hl_text_own.assign(v.text, v.text + v.text_len);
     h.text = in->hl_text_own.empty() ? nullptr : in->hl_text_own.data();
     const size_t n_hits = v.line_of_fin ? out->n_hits : 0;
@@ -326,44 +324,49 @@ void attach_hit_lines(const ScanOutput& so, bool wanted, bool owned, matchy_scan
     h.line_of_ip4_hit = nullptr;
 }
 
-// The text of hit i of a host-resident result that carries hit lines, and its whole line, inside the block; false when the result has
-// none (the caller then reads the batch).
-struct BlockLine { const uint8_t* hit; const uint8_t* line; uint32_t line_len; };
-bool block_line_of(const ScanResultInternal* in, bool in_hits, size_t i, uint32_t hit_start, BlockLine& bl) {
-    if (!in || !in->has_hit_lines || in->on_device || !in->hit_lines.text || !in->has_lines) return false;
-    const matchy_scan_hit_lines_t& h = in->hit_lines;
-    const uint32_t* of = in_hits ? h.line_of_hit : h.line_of_ip4_hit;
-    const matchy_scan_line_t* ln = in_hits ? in->lines : in->ip4_lines;
-    if (!of || !ln) return false;
-    const uint32_t k = of[i];
-    if (k >= h.n_lines) return false;
-    bl.line = h.text + h.line_off[k];
-    bl.line_len = h.line_off[k + 1] - 1u - h.line_off[k];
-    bl.hit = bl.line + (hit_start - ln[i].line_start);
-    return true;
-}
-
 static_assert(sizeof(SegmentRec) == sizeof(matchy_scan_segment_t) && offsetof(SegmentRec, lines_with_matches) == offsetof(matchy_scan_segment_t, lines_with_matches),
               "k_seg_build writes matchy_scan_segment_t records directly");
 
 // Segments of a result: the table is copied into the result's internal block (created when the arrays are borrowed); the per-record
 // indices are device pointers, the scanner's pinned block, or an owned copy, like the hit arrays of the same result.
-void attach_segments(Scanner& sc, const ScanOutput& so, bool device, bool owned, matchy_scan_result_t* out) {
+void attach_segments(Scanner& sc, const ScanOutput& so, Placement at, matchy_scan_result_t* out) {
     if (!so.has_segments) return;
-    if (!out->_internal) out->_internal = new ScanResultInternal();
-    auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+    ScanResultInternal* in = internal_of(out);
     in->has_segments = true;
     const matchy_scan_segment_t* t = reinterpret_cast<const matchy_scan_segment_t*>(so.segments);
     in->segments.assign(t, t + so.n_segments);
-    if (device) {
+    if (at == Placement::DEVICE) {
         in->segment_of_hit = out->n_hits ? sc.device_segment_of() : nullptr;
-    } else if (owned) {
+    } else if (at == Placement::OWNED) {
         if (so.seg_of_fin) in->segment_of_own.assign(so.seg_of_fin, so.seg_of_fin + out->n_hits);   // one per record of the result (scan_host gathers them itself)
         in->segment_of_hit = in->segment_of_own.empty() ? nullptr : in->segment_of_own.data();
     } else {
         in->segment_of_hit = so.seg_of_fin;
         in->segment_of_ip4_hit = so.seg_of_c4;
     }
+}
+
+// The result of a fetched scan of `bytes` bytes: the records where the plan places them, and what the scan attached to them.
+// hit_lines: the scanner's setting when the scan was queued (build_request).
+void finish_result(Scanner& sc, const FetchPlan& plan, const ScanOutput& so, uint64_t bytes, bool hit_lines, matchy_scan_result_t* out) {
+    if (plan.device) {   // the records stay where the lookup kernel wrote them (device memory); only the counters come back
+        memset(out, 0, sizeof(*out));
+        out->lines = so.lines; out->candidates = so.n_cand; out->bytes = bytes;
+        out->n_hits = so.n_hits; out->n_ids = sc.device_final_id_count();
+        out->hits = reinterpret_cast<const matchy_scan_hit_t*>(sc.device_final());
+        out->pattern_ids = sc.device_final_ids();
+        out->data_offsets = reinterpret_cast<const int64_t*>(sc.device_final_offs());
+        internal_of(out)->on_device = true;   // marks the residency: host-side readers of the result refuse device pointers
+    } else {
+        fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, bytes, !plan.sorted, out);
+        out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
+        if (!plan.records) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
+    }
+    const Placement at = plan.placement();
+    attach_lines(sc, so, at, out);
+    attach_segments(sc, so, at, out);
+    attach_hit_lines(so, hit_lines, at, out);
+    attach_render(so, at, out);
 }
 
 }  // namespace
@@ -1072,17 +1075,14 @@ int32_t matchy_scanner_scan(matchy_scanner_t* s, const uint8_t* data, size_t len
         std::vector<long long> foffs;
         std::vector<LineRec> flines;
         h->sc->scan_host(data, len, true, false, so, nullptr, &fin, &fids, &foffs, &flines);
-        fill_result(fin.data(), fin.size(), fids.data(), foffs.data(), fids.size(), so.lines, so.n_cand, len, false, true, out);
-        if (so.has_lines) {
-            auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
-            in->has_lines = true;
-            in->lines_with_matches = so.lines_with_matches;
-            in->lines_own.assign(reinterpret_cast<const matchy_scan_line_t*>(flines.data()), reinterpret_cast<const matchy_scan_line_t*>(flines.data()) + flines.size());
-            in->lines = in->lines_own.empty() ? nullptr : in->lines_own.data();
-        }
-        attach_segments(*h->sc, so, false, true, out);
-        attach_render(so, true, out);   // scan_host put the pieces' blocks end to end: the result takes a copy
-        if (h->sc->hit_lines()) {   // scan_host merged the pieces' blocks into vectors of its own: the result takes them
+        fill_result(fin.data(), fin.size(), fids.data(), foffs.data(), fids.size(), so.lines, so.n_cand, len, false, out);
+        so.fin_lines = flines.data(); so.n_fin = flines.size();   // the merged line records, where an owned result copies them from
+        attach_lines(*h->sc, so, Placement::OWNED, out);
+        attach_segments(*h->sc, so, Placement::OWNED, out);
+        attach_render(so, Placement::OWNED, out);   // scan_host put the pieces' blocks end to end: the result takes a copy
+        // The one attachment that differs from attach_hit_lines: scan_host merged the pieces' blocks into vectors of its own, and the
+        // result takes them by move instead of copying out of a pinned block.
+        if (h->sc->hit_lines()) {
             auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
             in->has_hit_lines = true;
             in->hl_text_own.swap(so.hl_text_own);
@@ -1109,25 +1109,13 @@ int32_t matchy_scanner_scan_device(matchy_scanner_t* s, const void* dptr, size_t
     ScannerH* h = reinterpret_cast<ScannerH*>(s);
     try {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        const bool sorted = (fetch_mode & 2) != 0;
+        const FetchPlan plan(fetch_mode);
         ScanRequest rq;
-        rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.fork = true; rq.slices = h->sc->slices(); rq.compact = compact_mode(fetch_mode);
-        const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
-        h->sc->arm_whole_lines(rq);
-        h->sc->arm_segments(len, st);
-        h->sc->arm_render(rq, fetch_renders(fetch_mode), st);
+        const bool hit_lines = build_request(*h->sc, plan, reinterpret_cast<const uint8_t*>(dptr), len, st, true, false, rq);
         h->sc->scan_device(rq, st);
         ScanOutput so;
-        h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); attach_render(so, false, out); return MATCHY_SUCCESS; }
-        fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, len, !sorted, sorted, out);
-        out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
-        if (!(fetch_mode & 1)) out->n_hits = so.n_hits;  // count only; `hits` stays NULL
-        attach_lines(*h->sc, so, false, sorted, out);
-        attach_segments(*h->sc, so, false, sorted, out);
-        attach_hit_lines(so, hit_lines, sorted, out);
-        attach_render(so, sorted, out);
+        h->sc->fetch(so, false, st, plan.hit_mode(), plan.sorted);
+        finish_result(*h->sc, plan, so, len, hit_lines, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1142,15 +1130,10 @@ int32_t matchy_scanner_submit_device(matchy_scanner_t* s, const void* dptr, size
     if (len >= 0x7FFF0000ull) return MATCHY_ERROR_INVALID_PARAM;
     ScannerH* h = reinterpret_cast<ScannerH*>(s);
     try {
-        const bool sorted = (fetch_mode & 2) != 0;
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         ScanRequest rq;   // not forked: several batches in flight (ScanRequest::fork)
-        rq.ptr = reinterpret_cast<const uint8_t*>(dptr); rq.len = (uint32_t)len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
-        h->pending_hit_lines = request_lines(*h->sc, fetch_mode, rq);
-        h->sc->arm_whole_lines(rq);
-        h->sc->arm_segments(len, reinterpret_cast<hipStream_t>(stream));
-        h->sc->arm_render(rq, fetch_renders(fetch_mode), reinterpret_cast<hipStream_t>(stream));
-        h->sc->scan_device(rq, reinterpret_cast<hipStream_t>(stream));
+        h->pending_hit_lines = build_request(*h->sc, FetchPlan(fetch_mode), reinterpret_cast<const uint8_t*>(dptr), len, st, false, false, rq);
+        h->sc->scan_device(rq, st);
         h->pending = true; h->pending_len = len; h->pending_mode = fetch_mode; h->pending_stream = stream;
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); return MATCHY_ERROR_INVALID_PARAM; }
@@ -1163,20 +1146,10 @@ int32_t matchy_scanner_wait(matchy_scanner_t* s, matchy_scan_result_t* out) {
     if (!h->pending) { set_error("matchy_scanner_wait: nothing was submitted"); return MATCHY_ERROR_INVALID_PARAM; }
     h->pending = false;
     try {
-        const uint32_t fetch_mode = h->pending_mode;
-        const bool sorted = (fetch_mode & 2) != 0;
-        const bool hit_lines = h->pending_hit_lines;
-        hipStream_t st = reinterpret_cast<hipStream_t>(h->pending_stream);
+        const FetchPlan plan(h->pending_mode);
         ScanOutput so;
-        h->sc->fetch(so, false, st, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
-        if ((fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE) { fill_device_result(*h->sc, so, h->pending_len, out); attach_lines(*h->sc, so, true, false, out); attach_segments(*h->sc, so, true, false, out); attach_hit_lines(so, hit_lines, false, out); attach_render(so, false, out); return MATCHY_SUCCESS; }
-        fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, h->pending_len, !sorted, sorted, out);
-        out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
-        if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
-        attach_lines(*h->sc, so, false, sorted, out);
-        attach_segments(*h->sc, so, false, sorted, out);
-        attach_hit_lines(so, hit_lines, sorted, out);
-        attach_render(so, sorted, out);
+        h->sc->fetch(so, false, reinterpret_cast<hipStream_t>(h->pending_stream), plan.hit_mode(), plan.sorted);
+        finish_result(*h->sc, plan, so, h->pending_len, h->pending_hit_lines, out);
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); memset(out, 0, sizeof(*out)); return MATCHY_ERROR_INVALID_PARAM; }   // thrown in front of fill_result
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1201,32 +1174,17 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
         const Scanner::GzBatch b = window ? h->sc->gz_inflate_window(packed, packed_len, window->carry, window->carry_len, window->carry_cap, (window->flags & MATCHY_WINDOW_LAST) != 0)
                                    : files ? h->sc->gz_inflate_files(packed, packed_len, reinterpret_cast<const GzFileIn*>(files), n)
                                            : h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
-        const bool sorted = (fetch_mode & 2) != 0;
+        const FetchPlan plan(fetch_mode);
         ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
-        rq.ptr = b.text; rq.len = b.len; rq.lookup = true;
-        rq.host_mirror = (fetch_mode & 1) && !sorted; rq.compact = compact_mode(fetch_mode);
-        const bool hit_lines = request_lines(*h->sc, fetch_mode, rq);
-        h->sc->arm_segments(b.len, b.stream);
-        h->sc->arm_render(rq, fetch_renders(fetch_mode), b.stream);
+        const bool hit_lines = build_request(*h->sc, plan, b.text, b.len, b.stream, false, true, rq);
         h->sc->scan_device(rq, b.stream);
         h->sc->gz_queue_results(want_text);
         ScanOutput so;
-        h->sc->fetch(so, false, b.stream, (fetch_mode & 1) ? HITS_FINAL : HITS_NONE, sorted);
+        h->sc->fetch(so, false, b.stream, plan.hit_mode(), plan.sorted);
         const GzInflate::Result g = h->sc->gz_finish();
-        const bool device = (fetch_mode & 7u) == MATCHY_SCAN_FETCH_DEVICE;
-        if (device) fill_device_result(*h->sc, so, g.ok_bytes, out);
-        else {
-            fill_result(so.fin, so.n_fin, so.fin_ids, so.fin_offs, so.n_fin_ids, so.lines, so.n_cand, g.ok_bytes, !sorted, sorted, out);
-            out->ip4_hits = reinterpret_cast<const matchy_scan_ip4_hit_t*>(so.c4); out->n_ip4_hits = so.n_c4;
-            if (!(fetch_mode & 1)) out->n_hits = so.n_hits;
-        }
+        finish_result(*h->sc, plan, so, g.ok_bytes, hit_lines, out);
         out->lines = so.lines - std::min<uint64_t>(so.lines, g.not_input_nl);
-        attach_lines(*h->sc, so, device, sorted, out);
-        attach_segments(*h->sc, so, device, sorted, out);
-        attach_hit_lines(so, hit_lines, !device && sorted, out);
-        attach_render(so, !device && sorted, out);
-        if (!out->_internal) out->_internal = new ScanResultInternal();
-        auto* in = reinterpret_cast<ScanResultInternal*>(out->_internal);
+        ScanResultInternal* in = internal_of(out);
         in->has_gz = true;
         in->gz_status.assign(g.status, g.status + g.n);
         if (g.file_status) {
@@ -1235,7 +1193,7 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
             in->gz_first_member.assign(g.first_member, g.first_member + g.n_files + 1);
         }
         in->gz_text = g.text; in->gz_text_len = g.text_len;
-        if (sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
+        if (plan.sorted && g.text) { in->gz_text_own.assign(g.text, g.text + g.text_len); in->gz_text = in->gz_text_own.data(); }
         if (g.first_piece) {   // pieces are on: the table may still be empty
             in->has_gz_pieces = true;
             in->gz_first_piece.assign(g.first_piece, g.first_piece + g.n + 1);
@@ -1381,263 +1339,60 @@ bool matchy_scan_result_on_device(const matchy_scan_result_t* r) {
     return r && r->_internal && reinterpret_cast<const ScanResultInternal*>(r->_internal)->on_device;
 }
 
+// ------------------------------------------------------------------------------------------------ NDJSON on the host (ndjson_host.h)
+// The plain view of a result for the host renderer. A host-resident result with hit lines and line context carries the text of its
+// records itself (the block); any other needs the batch.
+static ndjson::ResultView view_of(const matchy_scan_result_t* r, const uint8_t* text) {
+    ndjson::ResultView v;
+    v.hits = r->hits; v.n_hits = r->n_hits; v.ip4_hits = r->ip4_hits; v.n_ip4_hits = r->n_ip4_hits; v.data_offsets = r->data_offsets; v.text = text;
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in) return v;
+    if (in->has_lines) { v.lines = in->lines; v.ip4_lines = in->ip4_lines; }
+    if (in->has_segments) { v.segment_of_hit = in->segment_of_hit; v.segment_of_ip4_hit = in->segment_of_ip4_hit; v.segments = in->segments.data(); v.n_segments = in->segments.size(); }
+    if (in->has_hit_lines && !in->on_device && in->has_lines) v.block = &in->hit_lines;
+    return v;
+}
+static ndjson::Payloads payloads_of(const matchy_scanner_t* s) { return {&payload_json, &reinterpret_cast<const ScannerH*>(s)->sc->image()}; }
+
 char* matchy_scan_hit_to_json(const matchy_scanner_t* s, const matchy_scan_result_t* r, size_t i, const uint8_t* text, const char* source) {
     // i counts through hits, then through the compact IPv4 records of a MATCHY_SCAN_FETCH_COMPACT result
     if (!s || !r || i >= r->n_hits + r->n_ip4_hits) return nullptr;
-    if (i < r->n_hits ? !r->hits : !r->ip4_hits) return nullptr;
+    const bool in_hits = i < r->n_hits;
+    if (in_hits ? !r->hits : !r->ip4_hits) return nullptr;
     if (matchy_scan_result_on_device(r)) { set_error("matchy_scan_hit_to_json: the records of this result are in device memory (MATCHY_SCAN_FETCH_DEVICE)"); return nullptr; }
-    const DbImage& img = reinterpret_cast<const ScannerH*>(s)->sc->image();
-    const matchy_scan_hit_t h = i < r->n_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - r->n_hits]);
-    const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
-    // a result with hit lines carries the text of its hits itself; any other needs the batch
-    BlockLine bl{};
-    const bool from_block = block_line_of(reinterpret_cast<const ScanResultInternal*>(r->_internal), i < r->n_hits, i < r->n_hits ? i : i - r->n_hits, h.start, bl);
-    if (!from_block && !text) return nullptr;
-    std::string matched(from_block ? (const char*)bl.hit : (const char*)text + h.start, hlen), o = "{";
-    if (h.kind == 2) {
-        IpAddr ip;
-        std::string cidr;
-        // format_cidr_into parses matched_text again (cli_utils.rs:113); it always parses for extracted IPs
-        if (parse_ip(matched.data(), matched.size(), ip)) cidr = format_cidr(ip, h.prefix_len);
-        else cidr = matched + "/" + std::to_string((unsigned)h.prefix_len);
-        o += "\"cidr\":"; json_escape(cidr, o);
-        o += ",\"data\":";
-        DataValue dv;
-        if (img.decode_data(h.value, dv)) to_json(dv, o); else o += "null";
-        o += ",\"match_type\":\"ip\",\"matched_text\":"; json_escape(matched, o);
-        o += ",\"prefix_len\":" + std::to_string((unsigned)h.prefix_len);
-    } else {
-        std::string arr;
-        bool any = false;
-        for (uint32_t k = 0; k < h.n_ids; ++k) {
-            int64_t off = r->data_offsets[h.value + k];
-            if (off < 0) continue;
-            if (any) arr.push_back(',');
-            DataValue dv;
-            if (img.decode_data((uint32_t)off, dv)) to_json(dv, arr); else arr += "null";
-            any = true;
-        }
-        if (any) o += "\"data\":[" + arr + "],";
-        o += "\"match_type\":\"pattern\",\"matched_text\":"; json_escape(matched, o);
-        o += ",\"pattern_count\":" + std::to_string(h.n_ids);
-    }
-    o += ",\"source\":"; json_escape(source ? source : "-", o);
-    o += ",\"timestamp\":\"0.000\"}";
+    std::string o;
+    if (!ndjson::Renderer::record(view_of(r, text), in_hits, in_hits ? i : i - r->n_hits, source, payloads_of(s), o)) return nullptr;
     return strdup(o.c_str());
 }
 
-
-// Every match of a result as NDJSON, one line per hit in the order of the arrays (hits, then compact IPv4 records) — the text
-// matchy_scan_hit_to_json returns for each, concatenated with '\n' behind every line — in ONE call and one allocation: the default output
-// of `matchy match` (match_processor/parallel.rs:297-369). Per scanner the rendered data payloads are cached by data offset and the
-// fixed parts of a line are appended as literals, so a line costs a few memcpy instead of a decode of the MMDB value, a dozen
-// std::string temporaries and a strdup: the renderer was what bounded the command line with --format json (~6 GB/s of log against
-// 40+ with --format summary).
-// with_lines: "line_number" (and "input_line") from the result's line arrays go between "data" and "match_type" (keys stay sorted)
-// sources != NULL (matchy_scan_result_to_ndjson_segments): the result of a segmented scan; the source of a record is sources[its segment],
-// and with lines its number counts inside its segment: line_bases[s] + (line - segments[s].line_base) + 1
-static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, bool with_lines, uint64_t line_base,
-                                bool with_input_line, char** out, size_t* out_len, const char* const* sources = nullptr, const uint64_t* line_bases = nullptr) {
+// Every match of a result as NDJSON — the text matchy_scan_hit_to_json returns for each, with the line keys of `k` and '\n' behind every
+// line — in ONE call and one allocation.
+static int32_t result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const ndjson::Keys& k, char** out, size_t* out_len) {
     if (!s || !r || !out || !out_len) return MATCHY_ERROR_INVALID_PARAM;
-    // a host-resident result with hit lines renders from its block (`text` may be NULL); any other needs the batch
-    const ScanResultInternal* internal = reinterpret_cast<const ScanResultInternal*>(r->_internal);
-    const bool from_block = internal && internal->has_hit_lines && !internal->on_device && internal->has_lines && (internal->hit_lines.text || !internal->hit_lines.n_lines);
-    if (!from_block && !text && (r->n_hits || r->n_ip4_hits)) return MATCHY_ERROR_INVALID_PARAM;
-    const uint32_t* seg_of_hit = nullptr;
-    const uint32_t* seg_of_ip4 = nullptr;
-    const matchy_scan_segment_t* segs = nullptr;
-    size_t n_segs = 0;
-    if (sources && matchy_scan_result_segments(r, &seg_of_hit, &seg_of_ip4, &segs, &n_segs) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
-    if (sources && ((r->hits && r->n_hits && !seg_of_hit) || (r->ip4_hits && r->n_ip4_hits && !seg_of_ip4))) { set_error("matchy_scan_result_to_ndjson_segments: the result has no segment indices"); return MATCHY_ERROR_INVALID_PARAM; }
-    const matchy_scan_line_t* lines = nullptr;
-    const matchy_scan_line_t* ip4_lines = nullptr;
-    if (with_lines && matchy_scan_result_lines(r, &lines, &ip4_lines, nullptr) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
-    if (with_lines && ((r->hits && r->n_hits && !lines) || (r->ip4_hits && r->n_ip4_hits && !ip4_lines))) { set_error("matchy_scan_result_to_ndjson_lines: the result has no line records"); return MATCHY_ERROR_INVALID_PARAM; }
+    ndjson::ResultView v = view_of(r, text);
+    // a result renders from its block (`text` may be NULL) unless the block holds lines without their text (a counts-only fetch)
+    if (v.block && !v.block->text && v.block->n_lines) v.block = nullptr;
+    if (!v.block && !text && (r->n_hits || r->n_ip4_hits)) return MATCHY_ERROR_INVALID_PARAM;
+    if (k.sources && matchy_scan_result_segments(r, nullptr, nullptr, nullptr, nullptr) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
+    if (k.with_lines && matchy_scan_result_lines(r, nullptr, nullptr, nullptr) != MATCHY_SUCCESS) return MATCHY_ERROR_INVALID_PARAM;
     if (matchy_scan_result_on_device(r)) { set_error("matchy_scan_result_to_ndjson: the records of this result are in device memory (MATCHY_SCAN_FETCH_DEVICE)"); return MATCHY_ERROR_INVALID_PARAM; }
-    ScannerH* sh = reinterpret_cast<ScannerH*>(s);
-    const DbImage& img = sh->sc->image();
-    const size_t n = (r->hits ? r->n_hits : 0) + (r->ip4_hits ? r->n_ip4_hits : 0);
-    if (sh->json_source_of != (source ? source : "-") || sh->json_source.empty()) {
-        sh->json_source_of = source ? source : "-";
-        sh->json_source.clear();
-        json_escape(sh->json_source_of, sh->json_source);
-    }
-    // the JSON text of the source of every segment that owns a record
-    std::vector<std::string> seg_source;
-    if (sources) {
-        seg_source.resize(n_segs);
-        for (size_t k = 0; k < n_segs; ++k) if (segs[k].hits) json_escape(sources[k] ? sources[k] : "-", seg_source[k]);
-    }
-    // One piece of the result per thread (large results only: a 256 MiB batch of a web-server log carries ~70 K matches, ~15 MB of text; one thread
-    // renders ~9 M lines a second, which is less than two scanners on one GPU deliver). While pieces are rendered side by side the cache of
-    // payload texts is only read: a payload that is not in it yet is decoded into the piece's own list and joins the cache behind the threads.
-    struct Piece {
-        std::string o;
-        std::deque<std::pair<uint32_t, std::string>> fresh;          // payloads decoded by this piece (stable addresses)
-        std::unordered_map<uint32_t, const std::string*> fresh_at;
-    };
-    auto render = [&](size_t i0, size_t i1, Piece& pc, bool alone) {
-        std::string& o = pc.o;
-        o.reserve((i1 - i0) * 192 + 64);
-        auto data_json = [&](uint32_t off) -> const std::string& {
-            auto it = sh->json_of_data.find(off);
-            if (it != sh->json_of_data.end()) return it->second;
-            if (alone) {
-                if (sh->json_of_data.size() > (1u << 20)) sh->json_of_data.clear();   // a database with millions of distinct payloads: bounded
-                std::string js;
-                DataValue dv;
-                if (img.decode_data(off, dv)) to_json(dv, js); else js = "null";
-                return sh->json_of_data.emplace(off, std::move(js)).first->second;
-            }
-            auto f = pc.fresh_at.find(off);
-            if (f != pc.fresh_at.end()) return *f->second;
-            std::string js;
-            DataValue dv;
-            if (img.decode_data(off, dv)) to_json(dv, js); else js = "null";
-            pc.fresh.emplace_back(off, std::move(js));
-            pc.fresh_at.emplace(off, &pc.fresh.back().second);
-            return pc.fresh.back().second;
-        };
-        char num[16];
-        auto append_uint = [&](unsigned v) { const int k = snprintf(num, sizeof(num), "%u", v); o.append(num, (size_t)k); };
-        // does the text need more than quotes around it? (extracted items are almost always plain ASCII without '"' or a backslash)
-        auto append_quoted = [&](const char* p, size_t len) {
-            bool plain = true;
-            for (size_t k = 0; k < len; ++k) { const unsigned char c = (unsigned char)p[k]; if (c < 0x20 || c == '"' || c == 0x5C || c >= 0x7F) { plain = false; break; } }
-            if (plain) { o.push_back('"'); o.append(p, len); o.push_back('"'); }
-            else json_escape(std::string(p, len), o);
-        };
-        std::string raw_line;
-        char num64[24];
-        for (size_t i = i0; i < i1; ++i) {
-            const bool in_hits = r->hits && i < r->n_hits;
-            const matchy_scan_hit_t h = in_hits ? r->hits[i] : matchy_scan_ip4_hit_expand(r->ip4_hits[i - (r->hits ? r->n_hits : 0)]);
-            const uint32_t hlen = MATCHY_SCAN_HIT_LEN(h);
-            BlockLine bl{};
-            if (from_block && !block_line_of(internal, in_hits, in_hits ? i : i - (r->hits ? r->n_hits : 0), h.start, bl))
-                throw std::out_of_range("matchy_scan_result_to_ndjson: a record has no line in the block of hit lines");
-            const char* mt = from_block ? (const char*)bl.hit : (const char*)text + h.start;
-            const uint32_t seg = !sources ? 0u : in_hits ? seg_of_hit[i] : seg_of_ip4[i - (r->hits ? r->n_hits : 0)];
-            if (sources && seg >= n_segs) throw std::out_of_range("matchy_scan_result_to_ndjson_segments: a segment index lies outside the table");
-            auto append_line_keys = [&] {
-                if (!with_lines) return;
-                const matchy_scan_line_t ln = in_hits ? lines[i] : ip4_lines[i - (r->hits ? r->n_hits : 0)];
-                if (with_input_line) {
-                    o += "\"input_line\":";
-                    raw_line.clear();
-                    if (from_block) utf8_lossy_append(bl.line, bl.line_len, raw_line);
-                    else utf8_lossy_append(text + ln.line_start, ln.line_end - ln.line_start, raw_line);
-                    json_escape(raw_line, o);
-                    o.push_back(',');
-                }
-                o += "\"line_number\":";
-                const uint64_t base = sources ? line_bases[seg] - segs[seg].line_base : line_base;
-                const int k = snprintf(num64, sizeof(num64), "%llu", (unsigned long long)(base + ln.line + 1));
-                o.append(num64, (size_t)k);
-                o.push_back(',');
-            };
-            if (h.kind == 2) {
-                IpAddr ip;
-                o += "{\"cidr\":";
-                // format_cidr_into parses matched_text again (cli_utils.rs:113); it always parses for extracted IPs
-                if (parse_ip(mt, hlen, ip)) { const std::string c = format_cidr(ip, h.prefix_len); o.push_back('"'); o += c; o.push_back('"'); }
-                else { std::string c(mt, hlen); c += "/"; c += std::to_string((unsigned)h.prefix_len); json_escape(c, o); }
-                o += ",\"data\":";
-                o += data_json(h.value);
-                o.push_back(',');
-                append_line_keys();
-                o += "\"match_type\":\"ip\",\"matched_text\":";
-                append_quoted(mt, hlen);
-                o += ",\"prefix_len\":";
-                append_uint((unsigned)h.prefix_len);
-            } else {
-                o.push_back('{');
-                bool any = false;
-                for (uint32_t k = 0; k < h.n_ids; ++k) {
-                    const int64_t off = r->data_offsets[h.value + k];
-                    if (off < 0) continue;
-                    o += any ? "," : "\"data\":[";
-                    o += data_json((uint32_t)off);
-                    any = true;
-                }
-                if (any) o += "],";
-                append_line_keys();
-                o += "\"match_type\":\"pattern\",\"matched_text\":";
-                append_quoted(mt, hlen);
-                o += ",\"pattern_count\":";
-                append_uint((unsigned)h.n_ids);
-            }
-            o += ",\"source\":";
-            o += sources ? seg_source[seg] : sh->json_source;
-            o += ",\"timestamp\":\"0.000\"}\n";
-        }
-    };
-    static const unsigned max_threads = [] {
-        if (const char* e = getenv("MATCHY_AMD_JSON_THREADS")) return (unsigned)std::max(1, atoi(e));
-        const unsigned hw = std::thread::hardware_concurrency();
-        return hw >= 8 ? 4u : hw >= 4 ? 2u : 1u;
-    }();
-    const unsigned nt = (unsigned)std::min<size_t>(max_threads, std::max<size_t>(1, n / 16384));
-    std::vector<Piece> pieces(nt);
-    try {
-        if (nt == 1) render(0, n, pieces[0], true);
-        else {
-            // An exception must not leave a render thread (std::terminate), and none may leave this scope while a thread is still
-            // joinable: every piece catches its own, the joiner runs on every way out, the first failure is rethrown afterwards.
-            std::atomic<bool> failed{false};
-            std::vector<std::thread> th;
-            struct Joiner { std::vector<std::thread>& t; ~Joiner() { for (auto& x : t) if (x.joinable()) x.join(); } } joiner{th};
-            auto guarded = [&](size_t i0, size_t i1, Piece& pc) {
-                try { render(i0, i1, pc, false); } catch (...) { failed.store(true); }
-            };
-            th.reserve(nt);
-            for (unsigned t = 1; t < nt; ++t) th.emplace_back([&, t] { guarded(n * t / nt, n * (t + 1) / nt, pieces[t]); });
-            guarded(0, n / nt, pieces[0]);
-            for (auto& x : th) x.join();
-            if (failed.load()) throw std::bad_alloc();
-            for (Piece& pc : pieces)
-                for (auto& e : pc.fresh) {
-                    if (sh->json_of_data.size() > (1u << 20)) sh->json_of_data.clear();
-                    sh->json_of_data.emplace(e.first, std::move(e.second));
-                }
-        }
-    } catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_OUT_OF_MEMORY; }
-    size_t total = 0;
-    for (const Piece& pc : pieces) total += pc.o.size();
-    char* buf = (char*)malloc(total + 1);
-    if (!buf) { set_error("matchy_scan_result_to_ndjson: out of memory"); return MATCHY_ERROR_OUT_OF_MEMORY; }
-    {
-        std::vector<std::thread> th;
-        struct Joiner { std::vector<std::thread>& t; ~Joiner() { for (auto& x : t) if (x.joinable()) x.join(); } } joiner{th};
-        size_t at = 0;
-        for (unsigned t = 0; t < nt; ++t) {
-            char* dst = buf + at;
-            at += pieces[t].o.size();
-            bool spawned = false;
-            if (t + 1 < nt) {
-                try { th.emplace_back([dst, &pieces, t] { memcpy(dst, pieces[t].o.data(), pieces[t].o.size()); }); spawned = true; }
-                catch (...) {}   // no thread to be had: copy here
-            }
-            if (!spawned) memcpy(dst, pieces[t].o.data(), pieces[t].o.size());
-        }
-    }
-    buf[total] = 0;
-    *out = buf; *out_len = total;
-    return MATCHY_SUCCESS;
+    std::string error;
+    const int32_t rc = reinterpret_cast<ScannerH*>(s)->ndjson.render(v, k, payloads_of(s), out, out_len, error);
+    if (rc != MATCHY_SUCCESS) set_error(error);
+    return rc;
 }
 
 int32_t matchy_scan_result_to_ndjson(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, char** out, size_t* out_len) {
-    return result_to_ndjson(s, r, text, source, false, 0, false, out, out_len);
+    return result_to_ndjson(s, r, text, ndjson::Keys{source, nullptr, false, false, 0, nullptr}, out, out_len);
 }
 int32_t matchy_scan_result_to_ndjson_lines(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* source, uint64_t line_base,
                                            bool with_input_line, char** out, size_t* out_len) {
-    return result_to_ndjson(s, r, text, source, true, line_base, with_input_line, out, out_len);
+    return result_to_ndjson(s, r, text, ndjson::Keys{source, nullptr, true, with_input_line, line_base, nullptr}, out, out_len);
 }
-
 int32_t matchy_scan_result_to_ndjson_segments(matchy_scanner_t* s, const matchy_scan_result_t* r, const uint8_t* text, const char* const* sources,
                                               const uint64_t* line_bases, bool with_input_line, char** out, size_t* out_len) {
     if (!sources) return MATCHY_ERROR_INVALID_PARAM;
-    return result_to_ndjson(s, r, text, nullptr, line_bases != nullptr, 0, with_input_line, out, out_len, sources, line_bases);
+    return result_to_ndjson(s, r, text, ndjson::Keys{nullptr, sources, line_bases != nullptr, with_input_line, 0, line_bases}, out, out_len);
 }
 
 }  // extern "C"

@@ -1448,8 +1448,6 @@ void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool 
     }
 }
 
-static void payload_json(const void* ctx, uint32_t data_off, std::string& json);   // below, with set_render
-
 // The wait for everything queued, what the passes read behind it, and the padding slots of partially filled chunks dropped.
 void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, hipStream_t stream) {
     const ScanCounters& c = host_counters_;
@@ -1508,10 +1506,10 @@ void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMod
 }
 
 // Rendered records (render.h). The parameters are the caller's until arm_render() takes them for one scan.
-static void payload_json(const void* ctx, uint32_t data_off, std::string& json) {
+void payload_json(const void* img, uint32_t data_off, std::string& json) {
     json.clear();
     DataValue dv;
-    if (static_cast<const DbImage*>(ctx)->decode_data(data_off, dv)) to_json(dv, json); else json = "null";
+    if (static_cast<const DbImage*>(img)->decode_data(data_off, dv)) to_json(dv, json); else json = "null";
 }
 
 void Scanner::set_render(const RenderParams* p) {

@@ -193,6 +193,10 @@ void append_shifted_lines(const Line* lines, size_t n, uint32_t base, uint32_t l
 // of the piece arithmetic).
 size_t host_piece_bytes();
 
+// Payload JSON of the data record at `data_off` of the DbImage `img`, "null" where it does not decode: the one rule of both NDJSON renderers
+// (NdjsonRender::PayloadFn, ndjson::PayloadFn).
+void payload_json(const void* img, uint32_t data_off, std::string& json);
+
 // A scan session: owns the per-launch work buffers on one device. Not thread-safe; create one per thread/stream.
 class Scanner {
 public:

@@ -143,7 +143,7 @@ struct RenderParams {
 // the block of hit lines. Not thread-safe, like the scanner. Throws mxy::HipError.
 class NdjsonRender {
 public:
-    // payload JSON of a data offset ("null" where the value does not decode), as the host renderer makes it
+    // payload JSON of a data offset ("null" where the value does not decode): payload_json (engine.h), which the host renderer uses too
     using PayloadFn = void (*)(const void* ctx, uint32_t data_off, std::string& json);
     // The tables of the scan go to the device on `stream`, in front of its kernels.
     void arm(const RenderParams& p, hipStream_t stream);

@@ -1,6 +1,6 @@
-// NDJSON records of a scan result: everything that decides a byte of the output, as host/device code. The specification is the host
-// renderer result_to_ndjson (capi.cpp); the kernels of render.hip, the sequential model of their test and the CPU test
-// (tests/cpp/test_render_core.cpp) all go through the definitions below.
+// NDJSON records of a scan result: everything that decides a byte of the output, as host/device code. record_emit() below is the
+// grammar of a record; its users are the host renderer (ndjson_host.cpp), the kernels of render.hip, the sequential model of their
+// test and the CPU test (tests/cpp/test_render_core.cpp). None of them spells a key, a literal or the "cidr" rule itself.
 //
 // A record is a sequence of parts, emitted by record_emit() into a SINK: literals, decimal numbers, verbatim bytes (payload JSON and
 // the escaped source, both made by the host) and the two escaped fields, "matched_text" (json_escape of the raw bytes) and
