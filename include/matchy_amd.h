@@ -550,7 +550,8 @@ void matchy_scanner_get_gz_window_timing(const matchy_scanner_t *scanner, float 
  * (gzip -1 on some builds, zlib Z_FIXED) is decoded by piece 0 at one wave's pace and costs the find on top. A member that is handed
  * over costs what it costs with pieces off, plus the passes that ran. The symbol scratch is 2 bytes per inflated byte of the split
  * members (at most 4 GiB, which a batch below 2^31 bytes never reaches). What a batch cannot hold stays outside
- * this call: a member larger than a batch, and a single-stream file larger than a batch — windows need member boundaries. */
+ * this call: a member larger than a batch. A single-stream file larger than a batch is scanned as a chain of stream windows
+ * (matchy_scanner_scan_gz_stream, below), which need this setting on. */
 typedef struct matchy_gz_piece_t {
     uint64_t start_bit, end_bit;  /* in the member's DEFLATE body; end_bit: where its decoder stopped. 0 without MATCHY_PIECE_HAS_START */
     uint32_t member;              /* index into the statuses of matchy_scan_result_gz */
@@ -569,6 +570,56 @@ int32_t matchy_scan_result_gz_pieces(const matchy_scan_result_t *result, const m
 /* With matchy_scanner_set_profile: milliseconds of the find, count, chain and symbols kernels, of windows + resolve + verdict, and of the
  * handover inflate of the last gz scan (all part of out_ms[0] of matchy_scanner_get_gz_timing); zeros where no member was split. */
 void matchy_scanner_get_gz_pieces_timing(const matchy_scanner_t *scanner, float out_ms[6]);
+/* ---- stream windows (opt-in, beside the calls above, which stay as they are; matchy_scanner_set_gz_pieces must be on): ONE DEFLATE
+ * stream that is larger than a batch — what `gzip access.log` writes — is scanned as a chain of windows. A window is a run of the
+ * stream's compressed bytes whose first block starts at bit `bit` of its first byte; what the windows in front produced is the STATE:
+ * the text's length, its CRC-32 and its last 32 KiB. The device cuts the window into pieces as for a split member, piece 0 starting at
+ * that bit with the state's history in reach, follows the chain of pieces as far as the window's bytes and text_cap carry it, resolves
+ * markers (piece 0's from the history), folds the CRC into the state's and reports where it stopped: consumed_bits, counted from bit 0
+ * of packed[0], the gzip header of the first window included. The NEXT window starts at byte consumed_bits / 8 of this one with
+ * bit = consumed_bits % 8 and the state handed out (csrc/gz_stream.h decides how many bytes it gets). The stream's end counts only in a
+ * window that carries MATCHY_STREAM_FILE_END: there the trailer is verified — exactly 8 bytes behind the last block, ISIZE equal to the
+ * whole text's length modulo 2^32, the CRC-32 of the whole text — with the precedence of every gz scan. Layout of the batch, one segment:
+ *   [carry][window text][one '\n' separator, only where the stream ended here and carry + text > 0]
+ * and, because the text's length is known on the device only, '\n' up to carry_len + text_cap + 1 bytes, which is what is scanned; `bytes`
+ * and `lines` follow the accounting of matchy_scanner_scan_gz_window, so over the windows of a file they sum to its inflated length and
+ * line count. The carry is the partial line behind the window's last '\n', as there.
+ * Outcomes:  MATCHY_STREAM_OK           text scanned; consumed_bits, text_len, ended, the new state and the new carry are handed out
+ *            MATCHY_STREAM_NO_PROGRESS  no piece was taken: the window holds no whole block that ends on a found block start (a stream of
+ *                                       stored or fixed blocks has none), or one block is larger than text_cap
+ *            MATCHY_STREAM_NO_LINE_END  as MATCHY_WINDOW_NO_LINE_END
+ *            MATCHY_STREAM_FAILED       gz_status names it: a header that does not parse (first window, on the host), a stream error in
+ *                                       the window's first block, a distance in front of the stream's first byte, or the trailer
+ *            In all but the first the whole batch is '\n': no hit, bytes 0, an empty carry, no state; the caller falls back (gzread)
+ *            from the text the windows in front gave. Windows in front stay reported: a failing trailer is seen in the last window.
+ * The result also answers matchy_scan_result_gz (one member: gz_status; the text, carry included), matchy_scan_result_gz_pieces (the
+ * window's pieces; bits relative to the window's first DEFLATE byte) and matchy_scan_result_segments. Fetch modes, line context, hit
+ * lines, rendered records, the tally and the refusal of whole-line queries are those of matchy_scanner_scan_gz_window. The symbol scratch
+ * is 2 * text_cap bytes. MATCHY_ERROR_INVALID_PARAM with a message, and a scanner that stays usable: NULL handles, packed_len == 0 or
+ * 4 GiB and more, pieces off, carry_len > carry_cap, carry == NULL with carry_len > 0, text_cap == 0, carry_len + text_cap reaching 2^31,
+ * no state without MATCHY_STREAM_FIRST, state->bit > 7, history_len > 32768 or > text_bytes, unknown flag bits. */
+typedef struct matchy_gz_stream_state_t { uint64_t text_bytes; uint32_t crc, bit, history_len; uint8_t history[32768]; } matchy_gz_stream_state_t;
+typedef struct matchy_gz_stream_window_t {
+    const matchy_gz_stream_state_t *state;   /* NULL with MATCHY_STREAM_FIRST (it is not read then) */
+    const uint8_t *carry; uint32_t carry_len, carry_cap, text_cap, flags;
+} matchy_gz_stream_window_t;
+#define MATCHY_STREAM_FIRST 1u      /* packed begins with the gzip header (parsed on the host: MATCHY_GZ_BAD_HEADER as elsewhere) */
+#define MATCHY_STREAM_FILE_END 2u   /* packed reaches the file's last byte */
+#define MATCHY_STREAM_OK 0
+#define MATCHY_STREAM_NO_LINE_END 1
+#define MATCHY_STREAM_NO_PROGRESS 2
+#define MATCHY_STREAM_FAILED 3
+int32_t matchy_scanner_scan_gz_stream(matchy_scanner_t *scanner, const uint8_t *packed, size_t packed_len, const matchy_gz_stream_window_t *window,
+                                      uint32_t fetch_mode, bool want_text, matchy_scan_result_t *result);
+/* status: MATCHY_STREAM_*; gz_status: MATCHY_GZ_*; text_len: the window's inflated bytes; state_out, carry: owned by the result (valid
+ * until it is freed), meaningful for MATCHY_STREAM_OK (state_out is NULL otherwise). MATCHY_ERROR_INVALID_PARAM for a result of another
+ * kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_gz_stream(const matchy_scan_result_t *result, int32_t *status, int32_t *gz_status, uint64_t *consumed_bits, uint32_t *text_len,
+                                     bool *ended, const matchy_gz_stream_state_t **state_out, const uint8_t **carry, size_t *carry_len);
+/* With matchy_scanner_set_profile: milliseconds of the passes of the last stream window: find, count, chain, symbols, windows, resolve,
+ * verdict, line tail; zeros where none ran. */
+#define MATCHY_STREAM_PASSES 8
+void matchy_scanner_get_gz_stream_timing(const matchy_scanner_t *scanner, float out_ms[MATCHY_STREAM_PASSES]);
 /* Per-kernel HIP-event timing of the last scan (recorded on the scan's stream):
  * out[0..4] = k_anchor, k_validate_dom + k_validate, k_rare, k_lookup (incl. writing the hit records), total (milliseconds).
  * matchy_scanner_scan_device runs the kernels behind k_anchor on three streams: then out[1] is that whole tail and out[2] = out[3] = 0. */
@@ -687,6 +738,11 @@ int32_t matchy_multi_scanner_submit_gz_files(matchy_multi_scanner_t *ms, const u
  * bytes stay the caller's). The batch from _next answers matchy_scan_result_gz_window as well. The windows of one file are serial: the
  * caller takes a window's batch, and with it the carry, before it submits the next. */
 int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_window_t *window,
+                                              bool want_text, void *tag);
+/* The same for one window of one large DEFLATE stream (matchy_scanner_scan_gz_stream: state and carry are copied at the call, the packed
+ * bytes stay the caller's; matchy_multi_scanner_set_gz_pieces must be on, else the batch comes back with MATCHY_ERROR_INVALID_PARAM). The
+ * batch from _next answers matchy_scan_result_gz_stream as well. The windows of one stream are serial: submit one, take it, submit the next. */
+int32_t matchy_multi_scanner_submit_gz_stream(matchy_multi_scanner_t *ms, const uint8_t *packed, size_t packed_len, const matchy_gz_stream_window_t *window,
                                               bool want_text, void *tag);
 /* matchy_scanner_set_gz_pieces for every worker: each sets its scanner to the value in front of a gz batch it takes. */
 int32_t matchy_multi_scanner_set_gz_pieces(matchy_multi_scanner_t *ms, uint32_t piece_bytes);

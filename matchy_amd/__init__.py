@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_scan_gz_window", "matchy_scan_result_gz_window", "matchy_multi_scanner_submit_gz_window", "matchy_scanner_get_gz_window_timing",
     "matchy_scanner_set_gz_pieces", "matchy_scanner_get_gz_pieces", "matchy_scan_result_gz_pieces", "matchy_scanner_get_gz_pieces_timing",
     "matchy_multi_scanner_set_gz_pieces",
+    "matchy_scanner_scan_gz_stream", "matchy_scan_result_gz_stream", "matchy_scanner_get_gz_stream_timing", "matchy_multi_scanner_submit_gz_stream",
     "matchy_scanner_set_hit_lines", "matchy_scanner_hit_lines", "matchy_scan_result_hit_lines", "matchy_scanner_get_hit_lines_timing",
     "matchy_multi_scanner_set_hit_lines",
     "matchy_scanner_set_render", "matchy_scan_result_ndjson", "matchy_scanner_get_render_timing", "matchy_scanner_get_render_counters",
@@ -180,6 +181,69 @@ GZ_WINDOW_TAIL_BLOCK = 4096   # csrc/inflate.h GZ_TAIL_BLOCK: the bytes k_gz_win
 class _GzWindow(C.Structure):
     # matchy_gz_window_t (24 bytes)
     _fields_ = [("carry", C.c_void_p), ("carry_len", C.c_uint32), ("carry_cap", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# MATCHY_STREAM_*: the flags and the statuses of a stream window (Scanner.scan_gz_stream, ScanResult.gz_stream)
+STREAM_FIRST, STREAM_FILE_END = 1, 2
+STREAM_OK, STREAM_NO_LINE_END, STREAM_NO_PROGRESS, STREAM_FAILED = 0, 1, 2, 3
+GZ_STREAM_PASSES = ("find", "count", "chain", "symbols", "windows", "resolve", "verdict", "tail")
+
+
+class GzStreamState(C.Structure):
+    """matchy_gz_stream_state_t: what the windows in front of a stream window produced — the text's length, its CRC-32, the bit of the
+    next window's first byte at which its first block starts, and the text's last history_len <= 32768 bytes"""
+    _fields_ = [("text_bytes", C.c_uint64), ("crc", C.c_uint32), ("bit", C.c_uint32), ("history_len", C.c_uint32), ("history", C.c_uint8 * 32768)]
+
+    def history_bytes(self):
+        return bytes(self.history[:self.history_len])
+
+
+class _GzStreamWindow(C.Structure):
+    # matchy_gz_stream_window_t (32 bytes)
+    _fields_ = [("state", C.POINTER(GzStreamState)), ("carry", C.c_void_p), ("carry_len", C.c_uint32), ("carry_cap", C.c_uint32), ("text_cap", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class GzStreamWalker:
+    """csrc/gz_stream.h GzStreamWalker, line by line: where the next window of a chain of stream windows starts, how many compressed
+    bytes it gets, and when the chain is over. next() -> (offset, length, bit, flags); accept(window, consumed_bits, text_len, ended)
+    behind an OK window, refuse() behind any other."""
+    MIN_PIECES = 4
+
+    def __init__(self, file_len, window_bytes, piece_bytes, text_cap, first_bytes=0):
+        self.file_len, self.window_bytes, self.piece_bytes, self.text_cap = file_len, window_bytes, piece_bytes, text_cap
+        self.at = self.text_bytes = self.bit = self.windows = 0
+        self.want = first_bytes or window_bytes
+        self.over, self.ended = file_len == 0, False
+
+    def _clamp(self, n):
+        return max(min(self.MIN_PIECES * self.piece_bytes, self.window_bytes), min(n, self.window_bytes))
+
+    def next(self):
+        left, w = self.file_len - self.at, self._clamp(self.want)
+        flags = STREAM_FIRST if self.windows == 0 else 0
+        if left <= w + w // 4:
+            return self.at, left, self.bit, flags | STREAM_FILE_END
+        return self.at, w, self.bit, flags
+
+    def accept(self, window, consumed_bits, text_len, ended):
+        offset, length, bit, _ = window
+        self.windows += 1
+        if consumed_bits <= bit or consumed_bits > length * 8:
+            self.over = True
+            return False
+        nbytes = consumed_bits // 8
+        self.at, self.bit = offset + nbytes, consumed_bits % 8
+        self.text_bytes += text_len
+        fill = (max(nbytes, 1) * self.text_cap + text_len - 1) // text_len if text_len else self.window_bytes
+        self.want = self._clamp(fill + fill // 8 + self.piece_bytes)
+        if ended:
+            self.over = self.ended = True
+        return True
+
+    def refuse(self):
+        self.windows += 1
+        self.over = True
 
 
 class _GzPiece(C.Structure):
@@ -350,6 +414,11 @@ def lib():
         "matchy_scan_result_gz_window": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_multi_scanner_submit_gz_window": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzWindow), C.c_bool, vp]),
         "matchy_scanner_get_gz_window_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_scan_gz_stream": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzStreamWindow), C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_gz_stream": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                                     C.POINTER(C.c_bool), C.POINTER(C.POINTER(GzStreamState)), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "matchy_scanner_get_gz_stream_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_multi_scanner_submit_gz_stream": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzStreamWindow), C.c_bool, vp]),
         "matchy_scanner_set_gz_pieces": (C.c_int32, [vp, C.c_uint32]),
         "matchy_scanner_get_gz_pieces": (C.c_uint32, [vp]),
         "matchy_scan_result_gz_pieces": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(C.POINTER(_GzPiece)), C.POINTER(C.c_size_t), C.POINTER(vp)]),
@@ -761,6 +830,24 @@ class ScanResult:
             return None
         return st.value, (C.string_at(p.value, n.value) if n.value else b"")
 
+    def gz_stream(self):
+        """the verdict of a gz scan of a stream window (Scanner.scan_gz_stream) as a dict: status (STREAM_*), gz_status (GZ_*),
+        consumed_bits (from bit 0 of the window's first byte, the gzip header of the first window included), text_len, ended, state (a
+        GzStreamState of its own for the next window; None unless the status is STREAM_OK) and carry (bytes); None for any other scan"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        st, gst, bits, tl, ended = C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_uint32(0), C.c_bool(False)
+        state, p, n = C.POINTER(GzStreamState)(), C.c_void_p(), C.c_size_t(0)
+        if lib().matchy_scan_result_gz_stream(C.byref(self._raw), C.byref(st), C.byref(gst), C.byref(bits), C.byref(tl), C.byref(ended), C.byref(state), C.byref(p),
+                                              C.byref(n)) != 0:
+            return None
+        own = None
+        if state:
+            own = GzStreamState()
+            C.memmove(C.byref(own), state, C.sizeof(GzStreamState))
+        return dict(status=st.value, gz_status=gst.value, consumed_bits=bits.value, text_len=tl.value, ended=bool(ended.value), state=own,
+                    carry=C.string_at(p.value, n.value) if n.value else b"")
+
     def _gz_file_arrays(self):
         """(file status pointer, n_files, first_member pointer) of a gz scan of files, else None"""
         if self._raw is None:
@@ -1141,6 +1228,27 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_scan_gz_window failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def scan_gz_stream(self, blob, state=None, carry=b"", carry_cap=1 << 20, text_cap=1 << 20, first=False, file_end=False, want_text=False, fetch_mode=1) -> ScanResult:
+        """inflate and scan one window of ONE DEFLATE stream that is larger than a batch (matchy_scanner_scan_gz_stream; set_gz_pieces
+        comes first): `blob` are the window's compressed bytes — with `first` they begin with the gzip header —, `state` the GzStreamState
+        the window in front handed out (None with `first`), `carry` its partial line, text_cap the most text the window may give. The
+        result has gz_stream() (status, consumed_bits, text_len, ended, the next state and carry), one segment, gz_status() / gz_text()
+        (the carry included) and gz_pieces(). GzStreamWalker decides where the next window starts."""
+        keep = C.create_string_buffer(bytes(carry), len(carry)) if carry else None
+        w = _GzStreamWindow(C.pointer(state) if state is not None else None, C.addressof(keep) if keep is not None else None, len(carry), carry_cap, text_cap,
+                            (STREAM_FIRST if first else 0) | (STREAM_FILE_END if file_end else 0))
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_gz_stream(self._h, bytes(blob), len(blob), C.byref(w), fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_gz_stream failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
+    def gz_stream_timing_ms(self):
+        """with set_profile: milliseconds per pass of the last stream window (GZ_STREAM_PASSES)"""
+        out = (C.c_float * len(GZ_STREAM_PASSES))()
+        lib().matchy_scanner_get_gz_stream_timing(self._h, out)
+        return dict(zip(GZ_STREAM_PASSES, out))
+
     def set_gz_pieces(self, piece_bytes=0):
         """pieces of one stream for the next gz scans (matchy_scanner_set_gz_pieces): every member of at least 2 * piece_bytes compressed
         bytes is inflated by one wave per piece. 0 = off (the default); otherwise a power of two from 512 to 1 MiB, else ValueError"""
@@ -1307,6 +1415,17 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_segments failed ({rc}): " + last_error())
 
+    def submit_gz_stream_ptr(self, host_ptr: int, nbytes: int, state=None, carry=b"", carry_cap=1 << 20, text_cap=1 << 20, first=False, file_end=False, want_text=False,
+                             tag: int = 0):
+        """queue one window of one large DEFLATE stream whose compressed bytes live at a host address (matchy_multi_scanner_submit_gz_stream;
+        set_gz_pieces comes first). next() then carries "gz_stream" (ScanResult.gz_stream) and, with want_text, the batch"""
+        keep = C.create_string_buffer(bytes(carry), len(carry)) if carry else None
+        w = _GzStreamWindow(C.pointer(state) if state is not None else None, C.addressof(keep) if keep is not None else None, len(carry), carry_cap, text_cap,
+                            (STREAM_FIRST if first else 0) | (STREAM_FILE_END if file_end else 0))
+        rc = lib().matchy_multi_scanner_submit_gz_stream(self._h, host_ptr, nbytes, C.byref(w), bool(want_text), tag)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_gz_stream failed ({rc}): " + last_error())
+
     def submit_gz_ptr(self, host_ptr: int, nbytes: int, members, want_text=False, tag: int = 0):
         """queue a pack of gzip files that lives at a host address: members = [(offset, len, out_len)] (matchy_multi_scanner_submit_gz).
         next() then carries gz_status, the segment table and, with want_text, the inflated text"""
@@ -1387,6 +1506,8 @@ class MultiScanner:
                 out["gz_file_status"], out["gz_first_member"] = r.gz_file_status(), r.gz_first_member()
             if r.gz_window() is not None:
                 out["window_status"], out["carry"] = r.gz_window()
+            if r.gz_stream() is not None:
+                out["gz_stream"] = r.gz_stream()
         r.close()
         return out
 

@@ -20,6 +20,7 @@
 #include "db_builder.h"
 #include "db_image.h"
 #include "engine.h"
+#include "gz_stream.h"
 #include "host_lookup.h"
 #include "inflate_core.h"
 #include "ndjson_host.h"
@@ -379,6 +380,22 @@ const char* mxy::capi::gz_window_refusal(const uint8_t* packed, size_t packed_le
     if (w->carry_len > w->carry_cap) return "carry_len is above carry_cap";
     if (!w->carry && w->carry_len) return "carry is NULL with a carry_len above 0";
     if (w->carry_cap >= (1u << 31) || packed_len > 0xFFFFFFFFull) return "the batch reaches 2^31 bytes";
+    return nullptr;
+}
+const char* mxy::capi::gz_stream_refusal(const uint8_t* packed, size_t packed_len, const matchy_gz_stream_window_t* w) {
+    if (!packed || packed_len == 0) return "no compressed bytes (packed_len is 0)";
+    if (packed_len > 0xFFFFFFFFull) return "a window holds less than 4 GiB of compressed bytes";
+    if (!w) return "no window";
+    if (w->flags & ~(MATCHY_STREAM_FIRST | MATCHY_STREAM_FILE_END)) return "unknown flag bits";
+    if (w->carry_len > w->carry_cap) return "carry_len is above carry_cap";
+    if (!w->carry && w->carry_len) return "carry is NULL with a carry_len above 0";
+    if (w->text_cap == 0) return "text_cap is 0";
+    if ((uint64_t)w->carry_len + w->text_cap + 1 >= 0x7FFF0000ull || w->carry_cap >= (1u << 31)) return "the batch reaches 2^31 bytes (carry_len + text_cap)";
+    if (!(w->flags & MATCHY_STREAM_FIRST)) {
+        if (!w->state) return "no state (only a window with MATCHY_STREAM_FIRST has none)";
+        if (w->state->bit > 7) return "state: bit is above 7";
+        if (w->state->history_len > 32768 || w->state->history_len > w->state->text_bytes) return "state: history_len is above 32768 or above text_bytes";
+    }
     return nullptr;
 }
 
@@ -1168,10 +1185,13 @@ static_assert(sizeof(GzFileIn) == sizeof(matchy_gz_file_t) && offsetof(GzFileIn,
 // files of one member or many, file i is segment i), or `window` (matchy_scanner_scan_gz_window: packed[0, packed_len) are the whole members of
 // one window, which is segment 0)
 static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, const matchy_gz_file_t* files, size_t n,
-                            uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out, const matchy_gz_window_t* window = nullptr) {
+                            uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out, const matchy_gz_window_t* window = nullptr,
+                            const matchy_gz_stream_window_t* sw = nullptr) {
     try {
         { ScanRequest mode; mode.lookup = true; h->sc->arm_whole_lines(mode, true); }   // refused in front of the inflate kernels
-        const Scanner::GzBatch b = window ? h->sc->gz_inflate_window(packed, packed_len, window->carry, window->carry_len, window->carry_cap, (window->flags & MATCHY_WINDOW_LAST) != 0)
+        const Scanner::GzBatch b = sw ? h->sc->gz_inflate_stream(packed, packed_len, reinterpret_cast<const gz::StreamState*>(sw->state), sw->carry, sw->carry_len, sw->carry_cap,
+                                                                  sw->text_cap, (sw->flags & MATCHY_STREAM_FIRST) != 0, (sw->flags & MATCHY_STREAM_FILE_END) != 0)
+                                   : window ? h->sc->gz_inflate_window(packed, packed_len, window->carry, window->carry_len, window->carry_cap, (window->flags & MATCHY_WINDOW_LAST) != 0)
                                    : files ? h->sc->gz_inflate_files(packed, packed_len, reinterpret_cast<const GzFileIn*>(files), n)
                                            : h->sc->gz_inflate(packed, packed_len, reinterpret_cast<const GzMemberIn*>(members), n);
         const FetchPlan plan(fetch_mode);
@@ -1205,6 +1225,13 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
             in->gz_window_status = g.window_status;
             in->gz_carry.assign(g.carry, g.carry + g.carry_len);
         }
+        if (g.stream) {   // state and carry are the next window's input: always owned
+            in->has_gz_stream = true;
+            in->gz_stream_status = g.stream_status; in->gz_stream_gz_status = g.stream_gz_status;
+            in->gz_stream_consumed_bits = g.consumed_bits; in->gz_stream_text_len = g.stream_text_len; in->gz_stream_ended = g.ended;
+            if (g.state_out) { in->gz_stream_state.resize(1); memcpy(in->gz_stream_state.data(), g.state_out, sizeof(matchy_gz_stream_state_t)); }
+            if (g.carry_len) in->gz_carry.assign(g.carry, g.carry + g.carry_len);
+        }
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1231,6 +1258,37 @@ int32_t matchy_scanner_scan_gz_window(matchy_scanner_t* s, const uint8_t* packed
     memset(out, 0, sizeof(*out));
     if (const char* why = gz_window_refusal(packed, packed_len, window)) { set_error(std::string("matchy_scanner_scan_gz_window: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
     return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, nullptr, nullptr, 1, fetch_mode, want_text, out, window);
+}
+static_assert(sizeof(matchy_gz_stream_state_t) == sizeof(gz::StreamState) && offsetof(matchy_gz_stream_state_t, history) == offsetof(gz::StreamState, history) &&
+                  offsetof(matchy_gz_stream_state_t, bit) == offsetof(gz::StreamState, bit), "the pass reads matchy_gz_stream_state_t directly");
+static_assert(MATCHY_STREAM_OK == gz::STREAM_OK && MATCHY_STREAM_NO_LINE_END == gz::STREAM_NO_LINE_END && MATCHY_STREAM_NO_PROGRESS == gz::STREAM_NO_PROGRESS &&
+                  MATCHY_STREAM_FAILED == gz::STREAM_FAILED && MATCHY_STREAM_FIRST == GZ_STREAM_FIRST && MATCHY_STREAM_FILE_END == GZ_STREAM_FILE_END &&
+                  MATCHY_STREAM_PASSES == GZ_STREAM_PASSES, "k_gz_stream_verdict writes MATCHY_STREAM_* values directly");
+int32_t matchy_scanner_scan_gz_stream(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_stream_window_t* window, uint32_t fetch_mode, bool want_text,
+                                      matchy_scan_result_t* out) {
+    if (!s || !out) { set_error("matchy_scanner_scan_gz_stream: no scanner or no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    memset(out, 0, sizeof(*out));
+    if (const char* why = gz_stream_refusal(packed, packed_len, window)) { set_error(std::string("matchy_scanner_scan_gz_stream: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    if (!reinterpret_cast<ScannerH*>(s)->sc->gz_pieces()) { set_error("matchy_scanner_scan_gz_stream: pieces of one stream are off (matchy_scanner_set_gz_pieces comes first)"); return MATCHY_ERROR_INVALID_PARAM; }
+    return scan_gz_pack(reinterpret_cast<ScannerH*>(s), packed, packed_len, nullptr, nullptr, 1, fetch_mode, want_text, out, nullptr, window);
+}
+int32_t matchy_scan_result_gz_stream(const matchy_scan_result_t* r, int32_t* status, int32_t* gz_status, uint64_t* consumed_bits, uint32_t* text_len, bool* ended,
+                                     const matchy_gz_stream_state_t** state_out, const uint8_t** carry, size_t* carry_len) {
+    if (!r) { set_error("matchy_scan_result_gz_stream: no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_gz_stream) { set_error("matchy_scan_result_gz_stream: the result was not produced by a gz scan of a stream window"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (status) *status = in->gz_stream_status;
+    if (gz_status) *gz_status = in->gz_stream_gz_status;
+    if (consumed_bits) *consumed_bits = in->gz_stream_consumed_bits;
+    if (text_len) *text_len = in->gz_stream_text_len;
+    if (ended) *ended = in->gz_stream_ended;
+    if (state_out) *state_out = in->gz_stream_state.empty() ? nullptr : in->gz_stream_state.data();
+    if (carry) *carry = in->gz_carry.data();
+    if (carry_len) *carry_len = in->gz_carry.size();
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_gz_stream_timing(const matchy_scanner_t* s, float out[MATCHY_STREAM_PASSES]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->gz_stream_timing(out);
 }
 int32_t matchy_scan_result_gz_window(const matchy_scan_result_t* r, int32_t* window_status, const uint8_t** carry, size_t* carry_len) {
     if (!r) { set_error("matchy_scan_result_gz_window: no result"); return MATCHY_ERROR_INVALID_PARAM; }

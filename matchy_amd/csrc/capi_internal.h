@@ -15,6 +15,8 @@ void set_error(const std::string& e);           // the calling thread's matchy_a
 int default_device_of(const matchy_t* db);      // the HIP device a handle's scanners use when none is named
 // why matchy_scanner_scan_gz_window / matchy_multi_scanner_submit_gz_window refuse these arguments; nullptr: they do not
 const char* gz_window_refusal(const uint8_t* packed, size_t packed_len, const matchy_gz_window_t* window);
+// the same for matchy_scanner_scan_gz_stream / matchy_multi_scanner_submit_gz_stream (pieces off is the scanner's to refuse)
+const char* gz_stream_refusal(const uint8_t* packed, size_t packed_len, const matchy_gz_stream_window_t* window);
 
 struct ScanResultInternal {
     std::vector<matchy_scan_hit_t> hits;
@@ -63,6 +65,13 @@ struct ScanResultInternal {
     bool has_gz_window = false;
     int32_t gz_window_status = 0;
     std::vector<uint8_t> gz_carry;
+    // gz scan of a stream window (matchy_scan_result_gz_stream): the verdict and, for an OK window, the state behind it; the carry is
+    // gz_carry; owned
+    bool has_gz_stream = false, gz_stream_ended = false;
+    int32_t gz_stream_status = 0, gz_stream_gz_status = 0;
+    uint64_t gz_stream_consumed_bits = 0;
+    uint32_t gz_stream_text_len = 0;
+    std::vector<matchy_gz_stream_state_t> gz_stream_state;   // one, or none
     // gz scan with pieces on (matchy_scan_result_gz_pieces): the piece table and the pieces of member i, [first[i], first[i + 1]); owned
     bool has_gz_pieces = false;
     std::vector<matchy_gz_piece_t> gz_pieces;

@@ -29,6 +29,7 @@ int usage() {
             "               [--gz-on-gpu]   (consecutive small .gz files cross the bus compressed and are inflated on the GPU, one wave per file; not with --follow)\n"
             "               [--gz-members]   (with --gz-on-gpu: a .gz file of many small members that fits one batch is inflated by one wave per member)\n"
             "               [--gz-windows]   (with --gz-on-gpu --gz-members: a multi-member .gz file larger than a batch is scanned as a chain of windows of whole members)\n"
+            "               [--gz-stream-windows]   (with --gz-on-gpu --gz-pieces: a .gz file of ONE member that does not fit a batch, compressed or inflated, is scanned as a chain of windows of its stream)\n"
             "               [--gz-pieces[=BYTES]]   (with --gz-on-gpu: one large DEFLATE stream is inflated by many waves, in pieces of BYTES compressed bytes,\n"
             "                                        a power of two from 512 to 1048576; a .gz member may then be as large as a batch holds)\n"
             "               [--gather-lines]   (the lines with a match are gathered on the GPU and records are rendered from them: with --gz-on-gpu no inflated\n"

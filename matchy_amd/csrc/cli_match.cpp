@@ -13,6 +13,9 @@
 // (matchy_multi_scanner_submit_gz_files): one wave per member, the file is one segment, the verdict is per file.
 // --gz-windows (with both) extends that to multi-member .gz files LARGER than a batch: the mapped file goes out as a chain of windows of
 // whole members (matchy_multi_scanner_submit_gz_window), one at a time; every window hands the partial line behind its last '\n' to the next.
+// --gz-stream-windows (with --gz-on-gpu --gz-pieces) does the same for a .gz file of ONE member that does not fit a batch: a chain of
+// windows of its DEFLATE stream (matchy_multi_scanner_submit_gz_stream; gz_stream.h walks it), each handing the bit it stopped at, the
+// CRC and length so far and the last 32 KiB of text to the next, with the partial line.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -32,6 +35,7 @@
 #include "cli_common.h"
 #include "batch_reader.h"
 #include "gz_packer.h"
+#include "gz_stream.h"
 
 using namespace mxy;
 
@@ -53,6 +57,12 @@ struct GzVerdict {
     int32_t window_status = MATCHY_WINDOW_OK;
     std::vector<uint8_t> carry;
     uint64_t bytes = 0;
+    // --gz-stream-windows: MATCHY_STREAM_*, where the window stopped, and the state for the next window; written before set()
+    int32_t stream_status = MATCHY_STREAM_OK;
+    uint64_t consumed_bits = 0;
+    uint32_t text_len = 0;
+    bool ended = false;
+    std::shared_ptr<matchy_gz_stream_state_t> state;
     void set(const int32_t* st, size_t n) {
         { std::lock_guard<std::mutex> lk(mu); if (done) return; status.assign(st, st + n); done = true; }
         cv.notify_all();
@@ -69,8 +79,9 @@ struct GzVerdict {
 // are independent, the database is replicated, the host gathers the hit records and sums the counters; no collective).
 // STREAM: a newline-aligned piece of one input. PACK (--pack-inputs): several files, one segment each. GZ_PACK (--gz-on-gpu): gzip files,
 // compressed, one segment each. GZ_WINDOW (--gz-windows): one window of whole members of one gzip file: ONE segment like a pack of one
-// file, but its lines count on from those of the windows in front.
-enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW };
+// file, but its lines count on from those of the windows in front. GZ_STREAM (--gz-stream-windows): one window of ONE DEFLATE stream, a
+// segment whose lines count on in the same way.
+enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW, GZ_STREAM };
 struct Batch {
     BatchKind kind = BatchKind::STREAM;
     size_t input = 0;                   // the input of a stream batch or a window; the first of a pack
@@ -82,15 +93,17 @@ struct Batch {
     size_t appended = 0;                // PACK: the newlines the packer added
     std::vector<GzFile> gz;             // GZ_PACK: its files, end to end in `ptr`; GZ_WINDOW: gz[0] is the window
     std::shared_ptr<GzVerdict> verdict; // GZ_PACK, GZ_WINDOW: where the reader waits for the verdict on them
-    std::vector<uint8_t> carry;         // GZ_WINDOW: the partial line the window in front left behind
-    uint32_t carry_cap = 0;             // GZ_WINDOW
+    std::vector<uint8_t> carry;         // GZ_WINDOW, GZ_STREAM: the partial line the window in front left behind
+    uint32_t carry_cap = 0;             // GZ_WINDOW, GZ_STREAM
+    std::shared_ptr<matchy_gz_stream_state_t> stream_state;   // GZ_STREAM: the state the window in front handed out (none for the first)
+    uint32_t stream_text_cap = 0, stream_flags = 0;           // GZ_STREAM: MATCHY_STREAM_*
     bool window_last = false;           // GZ_WINDOW: the file ends with this window
     bool armed = false;                 // --render-on-gpu: the batch was submitted with matchy_multi_scanner_set_render
 
-    bool is_gz() const { return kind == BatchKind::GZ_PACK || kind == BatchKind::GZ_WINDOW; }
+    bool is_gz() const { return kind == BatchKind::GZ_PACK || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
     bool segmented() const { return kind != BatchKind::STREAM; }   // the scan result carries a segment table
     // the batch goes on where its input's earlier batches ended: only the first has line base 0 (every segment of a pack is a whole file)
-    bool continues_lines() const { return kind == BatchKind::STREAM || kind == BatchKind::GZ_WINDOW; }
+    bool continues_lines() const { return kind == BatchKind::STREAM || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
     // a gz batch: its inflated text comes back only where something is rendered from it on the host
     bool wants_text(bool json, bool gather) const { return json && !gather && !armed; }
     // every input the batch carries, in segment order
@@ -98,7 +111,7 @@ struct Batch {
         switch (kind) {
             case BatchKind::STREAM: f(input); break;
             case BatchKind::PACK: for (const PackedInput& pi : pack) f(pi.input); break;
-            case BatchKind::GZ_PACK: case BatchKind::GZ_WINDOW: for (const GzFile& g : gz) f(g.input); break;
+            case BatchKind::GZ_PACK: case BatchKind::GZ_WINDOW: case BatchKind::GZ_STREAM: for (const GzFile& g : gz) f(g.input); break;
         }
     }
 };
@@ -221,6 +234,11 @@ struct MatchPipeline {
                 rc = matchy_multi_scanner_submit_gz_window(ms, hb->ptr, hb->len, &w, text, hb);
                 break;
             }
+            case BatchKind::GZ_STREAM: {
+                const matchy_gz_stream_window_t w{hb->stream_state.get(), hb->carry.data(), (uint32_t)hb->carry.size(), hb->carry_cap, hb->stream_text_cap, hb->stream_flags};
+                rc = matchy_multi_scanner_submit_gz_stream(ms, hb->ptr, hb->len, &w, text, hb);
+                break;
+            }
         }
         if (rc == MATCHY_SUCCESS) return seq;
         // not queued (cannot happen for batches below 4 GiB): the printer never sees it
@@ -266,13 +284,23 @@ struct MatchPipeline {
             t.lines += r.lines; t.candidates += r.candidates; t.bytes += r.bytes; t.matches += r.n_hits;
             const int32_t* st = nullptr;
             size_t n_st = 0;
-            const int32_t got = gz_members ? matchy_scan_result_gz_files(&r, &st, &n_st, nullptr) : matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr);   // per file either way
+            const int32_t got = gz_members && b.kind != BatchKind::GZ_STREAM ? matchy_scan_result_gz_files(&r, &st, &n_st, nullptr) : matchy_scan_result_gz(&r, &st, &n_st, nullptr, nullptr);   // per file either way
             if (got != MATCHY_SUCCESS) { st = nullptr; n_st = 0; d.ok = false; }
             if (b.kind == BatchKind::GZ_WINDOW && got == MATCHY_SUCCESS) {
                 const uint8_t* carry = nullptr;
                 size_t n_carry = 0;
                 if (matchy_scan_result_gz_window(&r, &b.verdict->window_status, &carry, &n_carry) == MATCHY_SUCCESS) { b.verdict->carry.assign(carry, carry + n_carry); b.verdict->bytes = r.bytes; }
                 else { st = nullptr; n_st = 0; d.ok = false; }
+            }
+            if (b.kind == BatchKind::GZ_STREAM && got == MATCHY_SUCCESS) {
+                GzVerdict& v = *b.verdict;
+                const matchy_gz_stream_state_t* state = nullptr;
+                const uint8_t* carry = nullptr;
+                size_t n_carry = 0;
+                if (matchy_scan_result_gz_stream(&r, &v.stream_status, nullptr, &v.consumed_bits, &v.text_len, &v.ended, &state, &carry, &n_carry) == MATCHY_SUCCESS) {
+                    v.carry.assign(carry, carry + n_carry); v.bytes = r.bytes;
+                    if (state) v.state = std::make_shared<matchy_gz_stream_state_t>(*state);
+                } else { st = nullptr; n_st = 0; d.ok = false; }
             }
             b.verdict->set(st, n_st);
             if (!d.ok) { fprintf(stderr, "[ERROR] no gz statuses in the scan result of a gz pack: %s\n", matchy_amd_last_error()); return; }
@@ -569,15 +597,20 @@ struct GzReader {
     // goes out as a chain of windows of whole members: up to max_text of text and batch_bytes compressed each.
     bool windows = false;
     size_t win_windows = 0, win_files = 0, win_host = 0;   // windows the GPU accepted, files that went out as windows, of those finished on the host
+    // --gz-stream-windows: a .gz input of ONE member that the packer leaves (compressed or inflated, it does not fit a pack) is mapped and
+    // goes out as a chain of stream windows (gz_stream.h): up to stream_text_cap of text each, in pieces of piece_bytes.
+    bool stream_windows = false;
+    uint32_t piece_bytes = 0;
+    size_t sw_windows = 0, sw_files = 0, sw_host = 0;      // the same three counts for stream windows
 
-    GzReader(MatchPipeline& p, HostReader& h, bool members, bool win, bool pieces) : pl(p), host(h), windows(win) {
+    GzReader(MatchPipeline& p, HostReader& h, bool members, bool win, uint32_t pieces, bool stream_win) : pl(p), host(h), windows(win), stream_windows(stream_win), piece_bytes(pieces) {
         auto env = [](const char* name) { const char* e = getenv(name); return e ? std::optional<uint64_t>(strtoull(e, nullptr, 10)) : std::nullopt; };
         // --gz-pieces: a member is inflated by many waves, so it may be as large as a pack holds
         packer.bounds = (pieces ? gz_bounds_pieces : gz_bounds)(h.batch_bytes, env("MATCHY_AMD_GZ_MAX_MEMBER"), env("MATCHY_AMD_GZ_MAX_CARRY"));
         packer.members = members;
         packer.on_pack = [this](const std::vector<uint8_t>& packed, const std::vector<GzFile>& files) { send(packed, files); };
         // behind the pack in hand and its verdict: as a chain of windows, or the way it is read without the flags
-        packer.not_eligible = [this](size_t i) { settle(); if (!take_windows(i)) host.read(i); };
+        packer.not_eligible = [this](size_t i) { settle(); if (!take_windows(i) && !take_stream_windows(i)) host.read(i); };
     }
     void take(size_t i) { packer.take(i, host.paths[i]); }
     void barrier() { packer.flush(); settle(); }
@@ -632,6 +665,57 @@ struct GzReader {
         if (!ok) { ++win_host; host.read(i, consumed, bd.batch_bytes); }
         return true;
     }
+    // --gz-stream-windows, behind barrier() and take_windows(): input i as a chain of stream windows. False: not eligible (no regular .gz
+    // file, a header that does not parse, more than one member), nothing was submitted. The walker of gz_stream.h says where a window
+    // starts and how many bytes it gets; the windows go out one at a time, each with the state and the carry of the one in front, and the
+    // reader faults the next window's pages in while it waits. A window that is not OK ends the chain: what the windows in front
+    // reported is right — complete lines of text whose every block parsed — and the host finishes the file from the bytes they
+    // consumed, as for --gz-windows. The trailer is verified in the last window: a file whose CRC or length is wrong has had its text
+    // reported by then, the [ERROR] line is the host's.
+    bool take_stream_windows(size_t i) {
+        const std::string& path = host.paths[i];
+        const GzBounds& bd = packer.bounds;
+        struct stat sb;
+        if (!stream_windows || !piece_bytes || !pack_ends_with_gz(path) || bd.max_text < 2) return false;
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18) { close(fd); return false; }
+        const size_t size = (size_t)sb.st_size;
+        void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        close(fd);
+        if (m == MAP_FAILED) return false;
+        const uint8_t* p = (const uint8_t*)m;
+        uint64_t body = 0, next = 0, next_body = 0;
+        if (gz_parse_header(p, size, body) != GZ_PLAN_OK || size - body < 8 || gz_next_member(p, size, 0, body, next, next_body)) { munmap(m, size); return false; }
+        // carry + text + the separator fit a batch; a window's compressed bytes are no more than its text may be
+        const uint32_t text_cap = (uint32_t)std::min<uint64_t>(bd.max_text - 1, 0x7FF00000ull - bd.carry_cap);
+        const uint32_t window_bytes = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(bd.batch_bytes, text_cap), piece_bytes);
+        GzStreamWalker walk(size, window_bytes, piece_bytes, text_cap, window_bytes / 4);
+        ++sw_files;
+        std::vector<uint8_t> carry;
+        std::shared_ptr<matchy_gz_stream_state_t> state;
+        uint64_t consumed = 0;
+        size_t last_seq = 0;
+        while (!walk.over) {
+            const GzStreamWindow w = walk.next();
+            Batch b;
+            b.kind = BatchKind::GZ_STREAM; b.input = i; b.ptr = p + w.offset; b.len = (size_t)w.len;
+            b.carry = carry; b.carry_cap = (uint32_t)bd.carry_cap; b.stream_state = state; b.stream_text_cap = text_cap; b.stream_flags = w.flags;
+            b.gz.push_back(GzFile{i, 0, (uint32_t)b.len, 0, 1});
+            b.verdict = std::make_shared<GzVerdict>();
+            const std::shared_ptr<GzVerdict> v = b.verdict;
+            last_seq = pl.submit(std::move(b));
+            { volatile uint8_t sink = 0; for (uint64_t q = w.offset + w.len, end = std::min<uint64_t>(size, q + w.len); q < end; q += 4096) sink = sink + p[q]; }
+            v->wait();
+            if (v->status.size() != 1 || v->stream_status != MATCHY_STREAM_OK || !v->state) { walk.refuse(); break; }
+            if (!walk.accept(w, v->consumed_bits, v->text_len, v->ended)) break;
+            ++sw_windows; consumed += v->bytes;
+            carry = std::move(v->carry); state = v->state;
+        }
+        pl.add_mapping(m, size, last_seq);
+        if (!walk.ended) { ++sw_host; host.read(i, consumed, bd.batch_bytes); }
+        return true;
+    }
     // the verdict on the pack that is out: what the GPU accepted is counted, the rest is read the old way now
     void settle() {
         if (!pending) return;
@@ -670,7 +754,7 @@ struct GzReader {
 struct MatchOptions {
     std::vector<std::string> pos;   // the database, then the inputs
     std::string format = "json", extractors, devices;
-    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gz_windows = false, gather_lines = false, render_gpu = false, whole_lines = false;
+    bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gz_windows = false, gz_stream_windows = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
     // --gz-pieces[=BYTES] (with --gz-on-gpu): one large DEFLATE stream is inflated by many waves, in pieces of BYTES compressed bytes; 0 = off.
     // The default is the best of the sweep of tools/gz_pieces_timing.py: 4, 8 and 16 KiB lie within 3 % of each other on
@@ -687,7 +771,7 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
     typedef MatchOptions M;
     static const struct { const char* name; bool M::*on; } switches[] = {
         {"-s", &M::stats}, {"--stats", &M::stats}, {"-f", &M::follow}, {"--follow", &M::follow}, {"--line-numbers", &M::line_numbers}, {"--input-line", &M::input_line},
-        {"--pack-inputs", &M::pack}, {"--gz-on-gpu", &M::gz_gpu}, {"--gz-members", &M::gz_members}, {"--gz-windows", &M::gz_windows}, {"--gather-lines", &M::gather_lines},
+        {"--pack-inputs", &M::pack}, {"--gz-on-gpu", &M::gz_gpu}, {"--gz-members", &M::gz_members}, {"--gz-windows", &M::gz_windows}, {"--gz-stream-windows", &M::gz_stream_windows}, {"--gather-lines", &M::gather_lines},
         {"--render-on-gpu", &M::render_gpu}, {"--whole-lines", &M::whole_lines}, {"--tally", &M::tally}};
     if (const char* d = getenv("MATCHY_AMD_DEVICE")) o.device = atoi(d);
     for (int i = 0; i < argc; ++i) {
@@ -731,6 +815,7 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
     auto refuse = [](const char* why) { fprintf(stderr, "Error: %s\n", why); return 1; };
     if (o.format != "json" && o.format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", o.format.c_str()); return 1; }
     if (o.gz_windows && !(o.gz_gpu && o.gz_members)) return refuse("--gz-windows needs --gz-on-gpu --gz-members (it extends them to multi-member files larger than a batch)");
+    if (o.gz_stream_windows && !(o.gz_gpu && o.gz_pieces)) return refuse("--gz-stream-windows needs --gz-on-gpu --gz-pieces (it extends them to one DEFLATE stream larger than a batch)");
     if (o.gz_members && !o.gz_gpu) return refuse("--gz-members needs --gz-on-gpu (it extends the gz packs to files of many members)");
     if (o.gz_pieces && !o.gz_gpu) return refuse("--gz-pieces needs --gz-on-gpu (it inflates one large stream of a gz pack with many waves)");
     if (o.whole_lines) {
@@ -881,6 +966,7 @@ void report_stats(const MatchOptions& o, const MatchPipeline& pl, const GzReader
     if (o.gz_gpu) fprintf(stderr, "[INFO] Inflated %zu .gz inputs on the GPU in %zu batches (%llu -> %llu bytes), %zu read on the host\n", gzr.on_gpu, gzr.packs,
                           gzr.packed_bytes, gzr.text_bytes, gzr.on_host);
     if (o.gz_members) fprintf(stderr, "[INFO] gz members on the GPU: %zu in %zu multi-member files\n", gzr.multi_members, gzr.multi_files);
+    if (o.gz_stream_windows) fprintf(stderr, "[INFO] gz stream windows on the GPU: %zu windows of %zu files, %zu finished on the host\n", gzr.sw_windows, gzr.sw_files, gzr.sw_host);
     if (o.gz_windows) fprintf(stderr, "[INFO] gz windows on the GPU: %zu windows of %zu files, %zu finished on the host\n", gzr.win_windows, gzr.win_files, gzr.win_host);
 }
 
@@ -947,7 +1033,7 @@ int cmd_match(int argc, char** argv) {
     pl.line_base.assign(paths.size(), 0);
     pl.consumed.assign(paths.size(), -1);
     HostReader host{pl, paths, o.batch_bytes, std::vector<char>(paths.size(), 0)};
-    GzReader gzr(pl, host, o.gz_members, o.gz_windows, o.gz_pieces != 0);
+    GzReader gzr(pl, host, o.gz_members, o.gz_windows, o.gz_pieces, o.gz_stream_windows);
     PackStats packed;
     run_inputs(o, pl, host, gzr, packed, t, input_failed);
     uint64_t tally_distinct = 0;

@@ -1567,6 +1567,10 @@ Scanner::GzBatch Scanner::gz_inflate_files(const uint8_t* packed, size_t packed_
 Scanner::GzBatch Scanner::gz_inflate_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last) {
     return gz_pass([&](GzInflate& g) { g.launch_window(packed, packed_len, carry, carry_len, carry_cap, last, n_cu_, profile_, host_stream_); });
 }
+Scanner::GzBatch Scanner::gz_inflate_stream(const uint8_t* packed, size_t packed_len, const gz::StreamState* state, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap,
+                                            uint32_t text_cap, bool first, bool file_end) {
+    return gz_pass([&](GzInflate& g) { g.launch_stream(packed, packed_len, state, carry, carry_len, carry_cap, text_cap, first, file_end, n_cu_, profile_, host_stream_); });
+}
 void Scanner::gz_queue_results(bool want_text) { gz_->queue_results(want_text, host_stream_); }
 GzInflate::Result Scanner::gz_finish() { return gz_->finish(); }
 

@@ -263,6 +263,10 @@ public:
     GzBatch gz_inflate_files(const uint8_t* packed, size_t packed_len, const GzFileIn* files, size_t n_files);
     // one window of a file that is larger than a batch (GzInflate::launch_window): the window is segment 0, its carry lies in front
     GzBatch gz_inflate_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last);
+    // one window of one DEFLATE stream that is larger than a batch (GzInflate::launch_stream): the window is segment 0, its carry lies in
+    // front; gz pieces must be on
+    GzBatch gz_inflate_stream(const uint8_t* packed, size_t packed_len, const gz::StreamState* state, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, uint32_t text_cap,
+                              bool first, bool file_end);
     void gz_queue_results(bool want_text);
     GzInflate::Result gz_finish();
     // with set_profile: milliseconds of k_gz_inflate (CRC included), 0, and k_gz_seal of the last gz scan
@@ -273,6 +277,8 @@ public:
     void set_gz_pieces(uint32_t piece_bytes) { gz_piece_bytes_ = piece_bytes; }
     uint32_t gz_pieces() const { return gz_piece_bytes_; }
     void gz_pieces_timing(float out_ms[6]) const { for (int k = 0; k < 6; ++k) out_ms[k] = 0; if (gz_) gz_->pieces_timing(out_ms); }
+    // stream windows: find, count, chain, symbols, windows, resolve, verdict, tail of the last profiled window
+    void gz_stream_timing(float out_ms[GZ_STREAM_PASSES]) const { for (int k = 0; k < GZ_STREAM_PASSES; ++k) out_ms[k] = 0; if (gz_) gz_->stream_timing(out_ms); }
     void gz_window_timing(float out_ms[4]) const { gz_timing(out_ms); out_ms[3] = gz_ ? gz_->tail_ms() : 0; }
     // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
     // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.

@@ -73,6 +73,43 @@ hipError_t gz_piece_windows_launch(const GzPieceArgs& a, hipStream_t stream);
 hipError_t gz_piece_resolve_launch(const GzPieceArgs& a, hipStream_t stream);
 hipError_t gz_piece_verdict_launch(const GzPieceArgs& a, int32_t* status, uint32_t* handover, hipStream_t stream);
 
+// Windows of one stream (inflate_pieces.hip "stream windows"; the rules: inflate_core.h "windows of one stream"). One window is
+// in[0, in_len), compressed bytes of one DEFLATE stream whose first block starts at bit `bit` of in[0]; *state is the text in front of
+// it (all zero for the first window; bit and history_len are also passed by value, tested by the host). The batch is
+// batch[0, batch_len) = [carry_len bytes of carry][text_cap bytes for the window's text]['\n'], the scratch has text_cap symbols.
+// The launches run in this order on one stream behind the copies of the compressed bytes, the state and the carry and a zeroed *dev:
+// find, count, chain, symbols, windows, resolve, verdict, tail. The verdict writes dev->status / gz_status, on STREAM_OK *state_out and
+// '\n' over everything behind the text, otherwise '\n' over the whole batch; the tail (k_gz_window_tail's rule, with the text's end
+// and "the stream ended here" read from *dev) then hands the partial line behind the last '\n' out. Nothing is loaded outside
+// in[0, in_len), nothing stored outside batch[0, batch_len), scratch[0, text_cap), the tables, *dev and *state_out.
+struct GzStreamDev {
+    uint64_t consumed_bits;              // the chain: the end bit of the last live piece, relative to in[0]
+    uint32_t n_live, text_len, ended;
+    int32_t chain_failed;                // gz::StreamChain::failed
+    uint32_t bad, crc;                   // a marker pointed in front of the history; xor of the pieces' CRC parts (both zeroed by the host)
+    int32_t status, gz_status;           // the verdict: gz::STREAM_*, and the MATCHY_GZ_* value of STREAM_FAILED
+    uint32_t reserved[2];                // 48 bytes: the host zeroes whole 16-byte units
+};
+static_assert(sizeof(GzStreamDev) == 48, "three 16-byte units");
+struct GzStreamArgs {
+    const uint8_t* in; uint32_t in_len, bit, history_len;
+    gz::Piece* pieces; uint64_t* starts; uint32_t n_pieces, piece_bytes;
+    const gz::StreamState* state; gz::StreamState* state_out; GzStreamDev* dev;
+    uint16_t* scratch;
+    uint8_t* batch; uint32_t batch_len, carry_len, text_cap, file_end;
+};
+hipError_t gz_stream_find_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_count_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_chain_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_symbols_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_windows_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_resolve_launch(const GzStreamArgs& a, hipStream_t stream);
+hipError_t gz_stream_verdict_launch(const GzStreamArgs& a, hipStream_t stream);
+// result[0] = the tail's length, result[1] = GZ_WINDOW_OK or GZ_WINDOW_NO_LINE_END, as for gz_window_tail_launch
+hipError_t gz_stream_tail_launch(uint8_t* batch, uint32_t batch_len, uint32_t carry_len, uint32_t text_cap, const GzStreamDev* dev, uint32_t carry_cap, uint8_t* carry_out,
+                                 uint32_t* result, hipStream_t stream);
+constexpr int GZ_STREAM_PASSES = 8;   // find, count, chain, symbols, windows, resolve, verdict, tail
+
 // The gz pass of a scanner (Scanner::gz_inflate): the plan of the pack in flight and the buffers of the pass, grown on demand and reused
 // between scans. A scan runs as launch() in front of the scan's kernels, queue_results() behind them on the same stream and finish()
 // behind the wait. Not thread-safe, like the scanner. Throws mxy::HipError and, for a table that breaks its rules, mxy::ParamError.
@@ -89,6 +126,13 @@ public:
     // segment 0 of the scan.
     void launch_window(const uint8_t* packed, size_t packed_len, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, bool last, int n_cu, bool profile,
                        hipStream_t stream);
+    // One window of one DEFLATE stream that is larger than a batch (GzStreamArgs above). packed[0, packed_len) are the window's compressed
+    // bytes; with `first` they begin with the gzip header, which is parsed here (a header that does not parse: STREAM_FAILED with
+    // GZ_BAD_HEADER, nothing is launched but the fill), and state is not read; otherwise *state is the state the window in front handed
+    // out. The batch is [carry][text_cap bytes][one '\n'], segment 0 of the scan. Pieces must be on. On the device: the eight passes,
+    // no host round trip between them.
+    void launch_stream(const uint8_t* packed, size_t packed_len, const gz::StreamState* state, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, uint32_t text_cap,
+                       bool first, bool file_end, int n_cu, bool profile, hipStream_t stream);
     // Pieces of one stream: 0 = off (the default), otherwise a power of two in [GZ_PIECE_BYTES_MIN, GZ_PIECE_BYTES_MAX]
     // (gz_piece_bytes_valid). From the next launch on, every member of at least 2 * piece_bytes compressed bytes is split
     // (gz_plan_pieces) and inflated by one wave per piece; with 0 no piece kernel is launched and nothing of them is allocated.
@@ -111,7 +155,13 @@ public:
                     bool window = false; int32_t window_status = 0; const uint8_t* carry = nullptr; uint32_t carry_len = 0;
                     // pieces of one stream: the table of the launch (empty with pieces off or no member split), borrowed like status;
                     // the pieces of member i are [first_piece[i], first_piece[i + 1]), n + 1 entries
-                    const gz::Piece* pieces = nullptr; size_t n_pieces = 0; const uint32_t* first_piece = nullptr; };
+                    const gz::Piece* pieces = nullptr; size_t n_pieces = 0; const uint32_t* first_piece = nullptr;
+                    // behind launch_stream(): the window's status (gz::STREAM_*; STREAM_NO_LINE_END is the tail's), the MATCHY_GZ_* value of
+                    // a failed one, the bits consumed from packed[0] on (header included), the window's text length, whether the stream ended
+                    // in it, and the state behind it (borrowed like status; meaningful for STREAM_OK only). status[0] is stream_gz_status,
+                    // carry / carry_len, ok_bytes and not_input_nl are as behind launch_window()
+                    bool stream = false; int32_t stream_status = 0, stream_gz_status = 0; uint64_t consumed_bits = 0; uint32_t stream_text_len = 0; bool ended = false;
+                    const gz::StreamState* state_out = nullptr; };
     Result finish();
     // milliseconds of k_gz_inflate (CRC included: it runs in the same kernel), 0, and k_gz_seal (k_gz_file_verdict + k_gz_seal_files
     // behind launch_files) of the last profiled launch
@@ -121,6 +171,8 @@ public:
     // pieces: find, count, chain, symbols, windows + resolve + verdict, handover inflate of the last profiled launch; zeros with pieces
     // off or no member split. (These times are part of timing()'s first value.)
     void pieces_timing(float out_ms[6]) const { for (int k = 0; k < 6; ++k) out_ms[k] = piece_ms_[k]; }
+    // stream windows: find, count, chain, symbols, windows, resolve, verdict, tail of the last profiled launch_stream(); zeros otherwise
+    void stream_timing(float out_ms[GZ_STREAM_PASSES]) const { for (int k = 0; k < GZ_STREAM_PASSES; ++k) out_ms[k] = stream_ms_[k]; }
 
 private:
     void inflate_files(GzFilesPlan& fp, const uint8_t* packed, size_t packed_len, int n_cu, bool profile, hipStream_t stream);
@@ -162,6 +214,19 @@ private:
     Event ev_piece_[7];
     bool pieces_timed_ = false;
     float piece_ms_[6] = {0, 0, 0, 0, 0, 0};
+    // stream windows: nothing below is allocated without launch_stream
+    void queue_stream_results(bool want_text, hipStream_t stream);
+    Result finish_stream();
+    bool stream_ = false, stream_timed_ = false;
+    uint64_t stream_body_ = 0;
+    int32_t stream_host_status_ = 0, stream_host_gz_ = 0;   // decided in front of the kernels (the header, no bytes behind it): then nothing is launched
+    uint32_t stream_text_cap_ = 0;
+    DevBuf<gz::StreamState> stream_state_;     // [0] the state handed in, [1] the state handed out
+    DevBuf<GzStreamDev> stream_dev_;
+    PinnedBuf<gz::StreamState> stream_state_pinned_;   // [0] staging of the state handed in, [1] the state handed out
+    PinnedBuf<GzStreamDev> stream_dev_pinned_;
+    Event ev_stream_[GZ_STREAM_PASSES + 1];
+    float stream_ms_[GZ_STREAM_PASSES] = {0, 0, 0, 0, 0, 0, 0, 0};
     float ms_[3] = {0, 0, 0};
     bool timed_ = false, with_text_ = false;
     int waves_per_cu_ = 0;

@@ -174,14 +174,12 @@ __global__ __launch_bounds__(64) void k_gz_seal_files(const GzMemberDev* __restr
 // ceil((min(carry_cap, seg_end) + 1) / GZ_TAIL_BLOCK) turns. The tail is then moved by all lanes: a lane loads its byte, stores it to
 // carry_out and stores '\n' over it — program order per lane on addresses no other lane touches. Every text index is below seg_end <=
 // text_len, every carry_out index below tail_len <= carry_cap.
-__global__ __launch_bounds__(GZ_TAIL_THREADS) void k_gz_window_tail(uint8_t* text, uint32_t text_len, uint32_t seg_end_arg, uint32_t carry_len_arg,
-                                                                    const int32_t* __restrict__ file_status, uint32_t carry_cap, uint32_t last,
-                                                                    uint8_t* __restrict__ carry_out, uint32_t* __restrict__ result) {
-    __shared__ uint32_t found;   // position + 1 of the last '\n' of the block in hand, 0: none
+// (The body is a function of its own: k_gz_stream_tail below runs the same rule with arguments it reads from device memory.)
+__device__ __forceinline__ void d_window_tail(uint8_t* text, uint32_t text_len, uint32_t seg_end_arg, uint32_t carry_len_arg, bool failed, uint32_t carry_cap, uint32_t last,
+                                              uint8_t* __restrict__ carry_out, uint32_t* __restrict__ result, uint32_t& found) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t seg_end = min(seg_end_arg, text_len), carry_len = min(carry_len_arg, seg_end);
-    if (blockIdx.x != 0) return;
-    if (file_status[0] != gz::GZ_OK) {   // the seal has blanked the members' regions (and written the separator, if they have any text)
+    if (failed) {   // the seal has blanked the members' regions (and written the separator, if they have any text)
         for (uint32_t i = tid; i < carry_len; i += GZ_TAIL_THREADS) text[i] = (uint8_t)'\n';
         if (tid == 0) {
             if (last && seg_end != 0 && seg_end < text_len) text[seg_end] = (uint8_t)'\n';
@@ -238,6 +236,29 @@ __global__ __launch_bounds__(GZ_TAIL_THREADS) void k_gz_window_tail(uint8_t* tex
     if (tid == 0) { result[0] = tail_len; result[1] = status; }
 }
 
+__global__ __launch_bounds__(GZ_TAIL_THREADS) void k_gz_window_tail(uint8_t* text, uint32_t text_len, uint32_t seg_end_arg, uint32_t carry_len_arg,
+                                                                    const int32_t* __restrict__ file_status, uint32_t carry_cap, uint32_t last,
+                                                                    uint8_t* __restrict__ carry_out, uint32_t* __restrict__ result) {
+    __shared__ uint32_t found;   // position + 1 of the last '\n' of the block in hand, 0: none
+    if (blockIdx.x != 0) return;
+    d_window_tail(text, text_len, seg_end_arg, carry_len_arg, file_status[0] != gz::GZ_OK, carry_cap, last, carry_out, result, found);
+}
+
+// Stream windows (inflate_pieces.hip), behind k_gz_stream_verdict: the same tail over batch[0, carry_len + dev->text_len), where the text's
+// length and "the stream ended here" (nothing is cut, the separator is written) are known on the device only. A window whose verdict
+// is not STREAM_OK is '\n' throughout already and has no tail. Every branch around a barrier depends on arguments and *dev only.
+__global__ __launch_bounds__(GZ_TAIL_THREADS) void k_gz_stream_tail(uint8_t* batch, uint32_t batch_len, uint32_t carry_len, uint32_t text_cap, const GzStreamDev* dev,
+                                                                    uint32_t carry_cap, uint8_t* __restrict__ carry_out, uint32_t* __restrict__ result) {
+    __shared__ uint32_t found;
+    if (blockIdx.x != 0) return;
+    if (dev->status != gz::STREAM_OK) {
+        if (threadIdx.x == 0) { result[0] = 0; result[1] = (uint32_t)GZ_WINDOW_OK; }
+        return;
+    }
+    const uint32_t seg_end = carry_len + min(dev->text_len, text_cap);
+    d_window_tail(batch, batch_len, seg_end, carry_len, false, carry_cap, dev->ended, carry_out, result, found);
+}
+
 }  // namespace
 
 int gz_inflate_waves_per_cu() {
@@ -280,13 +301,20 @@ hipError_t gz_window_tail_launch(uint8_t* text, uint32_t text_len, uint32_t seg_
     return hipGetLastError();
 }
 
+hipError_t gz_stream_tail_launch(uint8_t* batch, uint32_t batch_len, uint32_t carry_len, uint32_t text_cap, const GzStreamDev* dev, uint32_t carry_cap, uint8_t* carry_out,
+                                 uint32_t* result, hipStream_t stream) {
+    if (carry_len > batch_len || text_cap > batch_len - carry_len) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gz_stream_tail, dim3(1), dim3(GZ_TAIL_THREADS), 0, stream, batch, batch_len, carry_len, text_cap, dev, carry_cap, carry_out, result);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ host driver
 void GzInflate::launch(const uint8_t* packed, size_t packed_len, const GzMemberIn* members, size_t n, int n_cu, bool profile, hipStream_t stream) {
     std::string err;
     if (!packed && packed_len) throw ParamError{"gz scan: no buffer"};
     if (!gz_plan(packed, packed_len, members, n, plan_, err)) throw ParamError{err};
     if (plan_.total >= 0x7FFF0000ull) throw ParamError{"gz plan: the inflated batch is too large for one scan (Scanner::scan_device takes less than 2^31 - 64 KiB)"};
-    files_ = false; window_ = false;
+    files_ = false; window_ = false; stream_ = false;
     members_host_.resize(n);
     status_host_.resize(n);
     for (size_t i = 0; i < n; ++i) {
@@ -305,7 +333,7 @@ void GzInflate::launch_files(const uint8_t* packed, size_t packed_len, const GzF
     if (!packed && packed_len) throw ParamError{"gz scan: no buffer"};
     if (!gz_plan_files(packed, packed_len, files, n_files, fp, err)) throw ParamError{err};
     if (fp.total >= 0x7FFF0000ull) throw ParamError{"gz plan: the inflated batch is too large for one scan (Scanner::scan_device takes less than 2^31 - 64 KiB)"};
-    window_ = false;
+    window_ = false; stream_ = false;
     inflate_files(fp, packed, packed_len, n_cu, profile, stream);
     if (profile) MXY_HIP(hipEventRecord(ev_[2], stream));
 }
@@ -319,7 +347,7 @@ void GzInflate::launch_window(const uint8_t* packed, size_t packed_len, const ui
     if (!carry && carry_len) throw ParamError{"gz window: no carry"};
     if (!gz_plan_window(packed, packed_len, carry_len, last, fp, err)) throw ParamError{err};
     if (fp.total >= 0x7FFF0000ull) throw ParamError{"gz plan: the inflated batch is too large for one scan (Scanner::scan_device takes less than 2^31 - 64 KiB)"};
-    window_ = true; window_last_ = last; carry_len_ = carry_len; carry_cap_ = carry_cap;
+    window_ = true; stream_ = false; window_last_ = last; carry_len_ = carry_len; carry_cap_ = carry_cap;
     if (carry_out_.n < (size_t)carry_cap + 16) carry_out_.alloc((size_t)carry_cap + 16);
     if (!window_result_.p) window_result_.alloc(2);
     if (carry_len) {
@@ -435,6 +463,7 @@ void GzInflate::inflate_pieces(size_t packed_len, int n_cu, bool profile, hipStr
 }
 
 void GzInflate::queue_results(bool want_text, hipStream_t stream) {
+    if (stream_) { queue_stream_results(want_text, stream); return; }
     const size_t n = plan_.members.size();
     status_pinned_.ensure(n, n / 4 + 1024);
     MXY_HIP(hipMemcpyAsync(status_pinned_.p, status_.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -462,6 +491,7 @@ void GzInflate::queue_results(bool want_text, hipStream_t stream) {
 }
 
 GzInflate::Result GzInflate::finish() {
+    if (stream_) return finish_stream();
     Result r;
     r.status = status_pinned_.p; r.n = plan_.members.size();
     r.text_len = plan_.total;
@@ -491,6 +521,7 @@ GzInflate::Result GzInflate::finish() {
     if (!pieces_host_.empty()) { r.pieces = pieces_pinned_.p; r.n_pieces = pieces_host_.size(); }
     if (piece_bytes_) r.first_piece = piece_plan_.first_piece.data();
     for (float& v : piece_ms_) v = 0;
+    for (float& v : stream_ms_) v = 0;
     if (pieces_timed_) for (int k = 0; k < 6; ++k) MXY_HIP(hipEventElapsedTime(&piece_ms_[k], ev_piece_[k], ev_piece_[k + 1]));
     ms_[0] = ms_[1] = ms_[2] = tail_ms_ = 0;
     if (timed_) {
@@ -498,6 +529,134 @@ GzInflate::Result GzInflate::finish() {
         MXY_HIP(hipEventElapsedTime(&ms_[2], ev_[1], ev_[2]));
         if (window_) MXY_HIP(hipEventElapsedTime(&tail_ms_, ev_tail_, ev_[2]));
     }
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ stream windows
+void GzInflate::launch_stream(const uint8_t* packed, size_t packed_len, const gz::StreamState* state, const uint8_t* carry, uint32_t carry_len, uint32_t carry_cap, uint32_t text_cap,
+                              bool first, bool file_end, int n_cu, bool profile, hipStream_t stream) {
+    (void)n_cu;
+    auto grown = [](size_t c) { return c + c / 8 + 4096; };
+    if (!piece_bytes_) throw ParamError{"gz stream: pieces of one stream are off (set_gz_pieces comes first)"};
+    if (!packed || !packed_len) throw ParamError{"gz stream: no compressed bytes"};
+    if (packed_len > 0xFFFFFFFFull) throw ParamError{"gz stream: a window holds less than 4 GiB of compressed bytes"};
+    if (carry_len > carry_cap) throw ParamError{"gz stream: the carry is longer than carry_cap"};
+    if (!carry && carry_len) throw ParamError{"gz stream: no carry"};
+    if (!text_cap) throw ParamError{"gz stream: text_cap is 0"};
+    if ((uint64_t)carry_len + text_cap + 1 >= 0x7FFF0000ull) throw ParamError{"gz stream: carry_len + text_cap is too large for one scan (Scanner::scan_device takes less than 2^31 - 64 KiB)"};
+    if (!first && !state) throw ParamError{"gz stream: no state (only the first window has none)"};
+    if (!first && !gz::stream_state_valid(state->text_bytes, state->bit, state->history_len)) throw ParamError{"gz stream: the state breaks its rules (bit <= 7, history_len <= 32768 and <= text_bytes)"};
+    uint64_t body = 0;
+    stream_host_status_ = gz::STREAM_OK; stream_host_gz_ = gz::GZ_OK;
+    if (first && gz_parse_header(packed, packed_len, body) != GZ_PLAN_OK) { stream_host_status_ = gz::STREAM_FAILED; stream_host_gz_ = gz::GZ_BAD_HEADER; body = 0; }
+    else if (body == packed_len) stream_host_status_ = gz::STREAM_NO_PROGRESS;   // the header and nothing behind it
+    const uint32_t in_len = (uint32_t)(packed_len - body);
+    const uint32_t batch_len = carry_len + text_cap + 1u;
+    const size_t np = stream_host_status_ == gz::STREAM_OK ? (size_t)(((uint64_t)in_len + piece_bytes_ - 1) / piece_bytes_) : 0;
+    plan_ = GzPlan();
+    plan_.members.push_back(GzPlanned{body, in_len, carry_len, text_cap, stream_host_gz_});
+    plan_.starts.push_back(0);
+    plan_.total = batch_len; plan_.packed_bytes = packed_len;
+    files_ = false; window_ = false; stream_ = true; timed_ = false; pieces_timed_ = false;
+    stream_body_ = body; stream_text_cap_ = text_cap; carry_len_ = carry_len; carry_cap_ = carry_cap;
+    piece_plan_ = GzPiecePlan();
+    piece_plan_.first_piece = {0u, (uint32_t)np};
+    pieces_host_.assign(np, gz::Piece{});
+    if (packed_.n < packed_len) packed_.alloc(grown(packed_len));
+    if (text_.n < (size_t)batch_len + 16) text_.alloc(grown((size_t)batch_len + 16));
+    if (carry_out_.n < (size_t)carry_cap + 16) carry_out_.alloc((size_t)carry_cap + 16);
+    if (!window_result_.p) window_result_.alloc(2);
+    if (!stream_state_.p) { stream_state_.alloc(2); stream_dev_.alloc(1); }
+    stream_timed_ = false;
+    if (stream_host_status_ != gz::STREAM_OK) {   // all '\n', no hit
+        MXY_HIP(hipMemsetAsync(text_.p, '\n', batch_len, stream));
+        return;
+    }
+    if (pieces_.n < np) { pieces_.alloc(grown(np)); piece_starts_.alloc(pieces_.n); }
+    if (scratch_.n < text_cap) scratch_.alloc(grown(text_cap));
+    stream_state_pinned_.ensure(2);
+    gz::StreamState& in = stream_state_pinned_.p[0];
+    if (first) memset(&in, 0, sizeof in); else memcpy(&in, state, sizeof in);
+    if (carry_len) {
+        carry_in_pinned_.ensure(carry_len, carry_cap - carry_len);
+        memcpy(carry_in_pinned_.p, carry, carry_len);
+    }
+    MXY_HIP(hipMemcpyAsync(packed_.p, packed, packed_len, hipMemcpyHostToDevice, stream));
+    MXY_HIP(hipMemcpyAsync(stream_state_.p, &in, sizeof in, hipMemcpyHostToDevice, stream));
+    if (carry_len) MXY_HIP(hipMemcpyAsync(text_.p, carry_in_pinned_.p, carry_len, hipMemcpyHostToDevice, stream));
+    MXY_HIP(hipMemsetAsync(stream_dev_.p, 0, sizeof(GzStreamDev), stream));
+    MXY_HIP(hipMemsetAsync(pieces_.p, 0, np * sizeof(gz::Piece), stream));
+    GzStreamArgs a{};
+    a.in = packed_.p + body; a.in_len = in_len; a.bit = in.bit; a.history_len = in.history_len;
+    a.pieces = pieces_.p; a.starts = piece_starts_.p; a.n_pieces = (uint32_t)np; a.piece_bytes = piece_bytes_;
+    a.state = stream_state_.p; a.state_out = stream_state_.p + 1; a.dev = stream_dev_.p;
+    a.scratch = scratch_.p;
+    a.batch = text_.p; a.batch_len = batch_len; a.carry_len = carry_len; a.text_cap = text_cap; a.file_end = file_end ? 1u : 0u;
+    stream_timed_ = profile;
+    int e = 0;
+    auto mark = [&] { if (profile) { ev_stream_[e].create(); MXY_HIP(hipEventRecord(ev_stream_[e], stream)); ++e; } };
+    mark();
+    MXY_HIP(gz_stream_find_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_count_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_chain_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_symbols_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_windows_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_resolve_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_verdict_launch(a, stream)); mark();
+    MXY_HIP(gz_stream_tail_launch(text_.p, batch_len, carry_len, text_cap, stream_dev_.p, carry_cap, carry_out_.p, window_result_.p, stream)); mark();
+}
+
+void GzInflate::queue_stream_results(bool want_text, hipStream_t stream) {
+    status_pinned_.ensure(1, 1024);
+    with_text_ = want_text;
+    if (want_text) {
+        text_pinned_.ensure(plan_.total, plan_.total / 8 + 4096);
+        MXY_HIP(hipMemcpyAsync(text_pinned_.p, text_.p, plan_.total, hipMemcpyDeviceToHost, stream));
+    }
+    if (stream_host_status_ != gz::STREAM_OK) return;
+    const size_t n_carry = std::min<size_t>(carry_cap_, (size_t)carry_len_ + stream_text_cap_);
+    stream_dev_pinned_.ensure(1);
+    window_result_pinned_.ensure(2);
+    carry_out_pinned_.ensure(n_carry + 1, carry_cap_ - n_carry);
+    MXY_HIP(hipMemcpyAsync(stream_dev_pinned_.p, stream_dev_.p, sizeof(GzStreamDev), hipMemcpyDeviceToHost, stream));
+    MXY_HIP(hipMemcpyAsync(&stream_state_pinned_.p[1], stream_state_.p + 1, sizeof(gz::StreamState), hipMemcpyDeviceToHost, stream));
+    MXY_HIP(hipMemcpyAsync(window_result_pinned_.p, window_result_.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (n_carry) MXY_HIP(hipMemcpyAsync(carry_out_pinned_.p, carry_out_.p, n_carry, hipMemcpyDeviceToHost, stream));
+    if (!pieces_host_.empty()) {
+        pieces_pinned_.ensure(pieces_host_.size(), pieces_host_.size() / 4 + 1024);
+        MXY_HIP(hipMemcpyAsync(pieces_pinned_.p, pieces_.p, pieces_host_.size() * sizeof(gz::Piece), hipMemcpyDeviceToHost, stream));
+    }
+}
+
+GzInflate::Result GzInflate::finish_stream() {
+    Result r;
+    r.status = status_pinned_.p; r.n = 1;
+    r.text_len = plan_.total;
+    if (with_text_) r.text = text_pinned_.p;
+    r.stream = true;
+    r.stream_status = stream_host_status_; r.stream_gz_status = stream_host_gz_;
+    r.not_input_nl = plan_.total;
+    r.first_piece = piece_plan_.first_piece.data();
+    for (float& v : stream_ms_) v = 0;
+    for (float& v : piece_ms_) v = 0;
+    ms_[0] = ms_[1] = ms_[2] = tail_ms_ = 0;
+    if (stream_host_status_ == gz::STREAM_OK) {
+        const GzStreamDev& d = stream_dev_pinned_.p[0];
+        r.stream_status = d.status; r.stream_gz_status = d.gz_status;
+        if (d.status == gz::STREAM_OK && window_result_pinned_.p[1] != (uint32_t)GZ_WINDOW_OK) r.stream_status = gz::STREAM_NO_LINE_END;
+        if (r.stream_status == gz::STREAM_OK) {
+            const uint32_t text_len = std::min(d.text_len, stream_text_cap_);
+            const uint64_t text = (uint64_t)carry_len_ + text_len;
+            r.consumed_bits = d.consumed_bits + stream_body_ * 8u; r.stream_text_len = text_len; r.ended = d.ended != 0;
+            r.state_out = &stream_state_pinned_.p[1];
+            r.carry = carry_out_pinned_.p;
+            r.carry_len = r.ended ? 0u : (uint32_t)std::min<uint64_t>(window_result_pinned_.p[0], std::min<uint64_t>(carry_cap_, text));
+            r.ok_bytes = text - r.carry_len; r.not_input_nl = plan_.total - r.ok_bytes;
+        }
+        if (!pieces_host_.empty()) { r.pieces = pieces_pinned_.p; r.n_pieces = pieces_host_.size(); }
+        if (stream_timed_) for (int k = 0; k < GZ_STREAM_PASSES; ++k) MXY_HIP(hipEventElapsedTime(&stream_ms_[k], ev_stream_[k], ev_stream_[k + 1]));
+    }
+    status_pinned_.p[0] = r.stream_gz_status;
     return r;
 }
 

@@ -569,5 +569,125 @@ MXY_HD bool piece_resolve_sym(uint32_t sym, const uint8_t* text, uint32_t piece_
     return true;
 }
 
+
+// ------------------------------------------------------------------------------------------------ windows of one stream
+// One DEFLATE stream that is larger than a batch goes through the passes above as a chain of STREAM WINDOWS (inflate_pieces.hip "stream
+// windows", gz_stream.h for the host's side). A window is a run in[0, in_len) of the stream's compressed bytes whose first block starts at
+// bit `bit` (0..7) of in[0]; the text in front of it has text_bytes bytes, CRC-32 `crc` and the last history_len = min(text_bytes, 32768)
+// of them are history[0, history_len). The window is cut into pieces like a split member, with three differences: piece 0 starts at
+// `bit`; piece 0 allows distances up to history_len beyond its own bytes (they become markers, like every later piece's); and the chain
+// is OPEN: it ends in front of the first piece that cannot be taken, and where it ends is where the next window begins. Every live piece
+// starts at the bit where the one in front ended and piece 0 starts at a true block start, so the end of every live piece is a true
+// block end of the stream. Piece 0 still never gives up on passed candidates (piece_pass_candidates tests p.self).
+struct StreamState {
+    uint64_t text_bytes;
+    uint32_t crc, bit, history_len;
+    uint8_t history[GZ_PIECE_WINDOW];
+};
+static_assert(sizeof(StreamState) == 24 + GZ_PIECE_WINDOW, "matchy_gz_stream_state_t");
+// a state a caller may hand in
+MXY_HD bool stream_state_valid(uint64_t text_bytes, uint32_t bit, uint32_t history_len) {
+    return bit <= 7u && history_len <= GZ_PIECE_WINDOW && history_len <= text_bytes;
+}
+
+// Status of a window, bit-identical to MATCHY_STREAM_* (include/matchy_amd.h); NO_LINE_END has the value of GZ_WINDOW_NO_LINE_END and is
+// the line tail's.
+enum : int32_t { STREAM_OK = 0, STREAM_NO_LINE_END = 1, STREAM_NO_PROGRESS = 2, STREAM_FAILED = 3 };
+
+// piece_find for a window: piece 0 starts at the state's bit
+MXY_HD uint64_t stream_piece_find(const uint8_t* in, uint32_t in_len, uint32_t piece_bytes, uint32_t i, uint32_t bit, Tables& t) {
+    return i == 0 ? (uint64_t)bit : piece_find(in, in_len, piece_bytes, i, t);
+}
+// piece_decoder_init for a window: piece 0 may reach history_len bytes in front of itself. A distance beyond produced + history_len
+// stays GZ_BAD_DISTANCE (the preset-dictionary case of the first window, whose history is empty).
+MXY_HD void stream_piece_decoder_init(PieceDecoder& p, const uint8_t* in, uint32_t in_len, uint32_t cap, const uint64_t* starts, uint32_t n_pieces, uint32_t self,
+                                      uint64_t start_bit, uint32_t history_len) {
+    piece_decoder_init(p, in, in_len, cap, starts, n_pieces, self, start_bit);
+    if (self == 0) p.window = history_len < GZ_PIECE_WINDOW ? history_len : GZ_PIECE_WINDOW;
+}
+
+// What the open chain of a window found. n_live == 0: no progress, or (failed != GZ_OK) piece 0, which starts at a true block start,
+// met an error of the stream itself; the end of the input and the capacity are no such errors: a later window may hold more.
+struct StreamChain {
+    uint64_t consumed_bits;   // the end bit of the last live piece, relative to in[0]
+    uint32_t n_live, text_len, last;   // last: the last live piece
+    int32_t failed;
+    bool ended;               // the last live piece landed on the end of the final block
+};
+// The open chain over pieces[0, n): walks from piece 0 along `next` (strictly increasing: at most n turns), sets out_pos and PIECE_LIVE, and
+// stops, without failing, in front of the first piece that has no start, is not OK, has not landed or would take the sum above `cap`. A
+// piece that lands on the end of the final block is live only with file_end (the window's bytes reach the file's end): the trailer
+// behind it belongs to the window that can see all of it.
+MXY_HD StreamChain stream_chain(Piece* pieces, uint32_t n, uint32_t cap, bool file_end) {
+    StreamChain c;
+    c.consumed_bits = 0; c.n_live = 0; c.text_len = 0; c.last = 0; c.failed = GZ_OK; c.ended = false;
+    uint64_t sum = 0;
+    uint32_t i = 0;
+    for (uint32_t turn = 0; turn < n; ++turn) {
+        Piece& p = pieces[i];
+        if (!(p.flags & PIECE_HAS_START) || p.status != GZ_OK || sum + p.produced > cap) break;
+        const bool end = p.next == GZ_PIECE_END;
+        if (end ? !file_end : (p.next <= i || p.next >= n)) break;
+        p.out_pos = (uint32_t)sum; p.flags |= PIECE_LIVE;
+        sum += p.produced;
+        c.consumed_bits = p.end_bit; c.last = i; ++c.n_live;
+        if (end) { c.ended = true; break; }
+        i = p.next;
+    }
+    c.text_len = (uint32_t)sum;
+    if (c.n_live == 0 && n != 0 && (pieces[0].flags & PIECE_HAS_START)) {
+        const int32_t st = pieces[0].status;
+        if (st == GZ_BAD_BLOCK || st == GZ_BAD_CODES || st == GZ_BAD_SYMBOL || st == GZ_BAD_DISTANCE) c.failed = st;
+    }
+    return c;
+}
+
+// piece_resolve_sym for a window: a marker that points in front of the window's first text byte reads the history, one that points in
+// front of the history fails (GZ_BAD_DISTANCE). text is the window's text, piece_pos the piece's out_pos in it.
+MXY_HD bool stream_resolve_sym(uint32_t sym, const uint8_t* text, uint32_t piece_pos, const uint8_t* history, uint32_t history_len, uint8_t& byte) {
+    if (sym < GZ_SYM_MARKER) { byte = (uint8_t)sym; return true; }
+    const uint32_t k = sym - GZ_SYM_MARKER;
+    if (k >= GZ_PIECE_WINDOW) return false;
+    const int64_t at = (int64_t)piece_pos + (int64_t)k - (int64_t)GZ_PIECE_WINDOW;
+    if (at >= 0) { byte = text[at]; return true; }
+    if (-at > (int64_t)history_len || history_len > GZ_PIECE_WINDOW) return false;
+    byte = history[(int64_t)history_len + at];
+    return true;
+}
+
+// A piece's CRC times x^(8 * bytes behind it in the window): text_len, not the capacity, is the window's end.
+MXY_HD uint32_t stream_piece_crc(uint32_t piece_crc, uint32_t text_len, uint32_t out_pos, uint32_t produced) {
+    return crc_mul(piece_crc, crc_xpow8(text_len - out_pos - produced));
+}
+// CRC-32 of (text in front ‖ window text) from the two CRCs
+MXY_HD uint32_t stream_crc_combine(uint32_t crc_before, uint32_t window_crc, uint32_t text_len) { return crc_mul(crc_before, crc_xpow8(text_len)) ^ window_crc; }
+// ISIZE is the stream's length modulo 2^32
+MXY_HD uint32_t stream_isize(uint64_t text_bytes, uint32_t text_len) { return (uint32_t)((text_bytes + text_len) & 0xFFFFFFFFull); }
+
+// The stream ended in this window, whose bytes reach the file's end: exactly the 8 bytes of the trailer follow the last block's last
+// byte, ISIZE is the whole text's length and the CRC the whole text's. The order is check_trailer's: TRUNCATED, SIZE_MISMATCH,
+// CRC_MISMATCH, TRAILING_DATA.
+MXY_HD int32_t stream_end_check(const uint8_t* in, uint32_t in_len, uint64_t end_bit, uint64_t text_bytes, uint32_t text_len, uint32_t crc) {
+    const uint64_t at = (end_bit + 7u) >> 3;
+    if (at > in_len || in_len - at < 8u) return GZ_TRUNCATED;
+    const uint8_t* p = in + at;
+    const uint32_t want_crc = p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+    const uint32_t isize = p[4] | (uint32_t)p[5] << 8 | (uint32_t)p[6] << 16 | (uint32_t)p[7] << 24;
+    if (isize != stream_isize(text_bytes, text_len)) return GZ_SIZE_MISMATCH;
+    if (want_crc != crc) return GZ_CRC_MISMATCH;
+    return in_len - at == 8u ? GZ_OK : GZ_TRAILING_DATA;
+}
+
+// The history behind a window: the last min(32768, history_len + text_len) bytes of history ‖ text. Byte j of it. (The kernel copies
+// one byte per lane and turn; out and history do not overlap.)
+MXY_HD uint32_t stream_history_len(uint32_t history_len, uint32_t text_len) {
+    const uint64_t all = (uint64_t)history_len + text_len;
+    return all < GZ_PIECE_WINDOW ? (uint32_t)all : GZ_PIECE_WINDOW;
+}
+MXY_HD uint8_t stream_history_byte(const uint8_t* history, uint32_t history_len, const uint8_t* text, uint32_t text_len, uint32_t new_len, uint32_t j) {
+    const uint64_t at = (uint64_t)history_len + text_len - new_len + j;   // position in history ‖ text
+    return at < history_len ? history[at] : text[at - history_len];
+}
+
 }  // namespace gz
 }  // namespace mxy

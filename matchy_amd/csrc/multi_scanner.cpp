@@ -47,7 +47,7 @@ struct RenderSpec {
 };
 // what a batch is: set by the submit call that queued it (matchy_multi_scanner_submit / _submit_near, _submit_segments, _submit_gz,
 // _submit_gz_files, _submit_gz_window, in this order), read by the worker that scans it
-enum class JobKind { PLAIN, SEGMENTS, GZ_MEMBERS, GZ_FILES, GZ_WINDOW };
+enum class JobKind { PLAIN, SEGMENTS, GZ_MEMBERS, GZ_FILES, GZ_WINDOW, GZ_STREAM };
 struct MultiJob {
     JobKind kind;
     const uint8_t* data;                      // the caller's bytes: text, or (gz kinds) the compressed pack
@@ -61,9 +61,11 @@ struct MultiJob {
     std::vector<matchy_gz_file_t> gz_files;   // GZ_FILES: of files of one member or many
     std::vector<uint8_t> carry;               // GZ_WINDOW: the batch is one window of a large file behind this carry, copied at the submit
     uint32_t carry_cap = 0, window_flags = 0; // GZ_WINDOW
+    std::unique_ptr<matchy_gz_stream_state_t> stream_state;   // GZ_STREAM: the state of the window (none for the first), copied at the submit like the carry
+    uint32_t stream_text_cap = 0;             // GZ_STREAM (carry, carry_cap and window_flags as for GZ_WINDOW)
     bool gz_text = false;                     // gz kinds: the inflated text comes back with the result
     std::shared_ptr<const RenderSpec> render; // matchy_multi_scanner_set_render, taken by the submit that followed it
-    bool is_gz() const { return kind == JobKind::GZ_MEMBERS || kind == JobKind::GZ_FILES || kind == JobKind::GZ_WINDOW; }
+    bool is_gz() const { return kind == JobKind::GZ_MEMBERS || kind == JobKind::GZ_FILES || kind == JobKind::GZ_WINDOW || kind == JobKind::GZ_STREAM; }
 };
 struct MultiDone { int32_t status = MATCHY_SUCCESS; matchy_scan_result_t res{}; const uint8_t* data = nullptr; size_t len = 0; void* tag = nullptr; void* payload = nullptr; size_t worker = 0; };
 struct MultiScanner {
@@ -141,11 +143,13 @@ struct MultiScanner {
                 if (j.kind == JobKind::SEGMENTS) d.status = matchy_scanner_set_segments(sc, j.starts.data(), j.starts.size());
                 if (j.render) j.render->arm(sc);
                 const matchy_gz_window_t window{j.carry.data(), (uint32_t)j.carry.size(), j.carry_cap, j.window_flags};
+                const matchy_gz_stream_window_t stream_window{j.stream_state.get(), j.carry.data(), (uint32_t)j.carry.size(), j.carry_cap, j.stream_text_cap, j.window_flags};
                 if (d.status == MATCHY_SUCCESS) switch (j.kind) {
                     case JobKind::PLAIN: case JobKind::SEGMENTS: d.status = matchy_scanner_scan(sc, j.data, j.len, &d.res); break;
                     case JobKind::GZ_MEMBERS: d.status = matchy_scanner_scan_gz(sc, j.data, j.len, j.gz.data(), j.gz.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                     case JobKind::GZ_FILES: d.status = matchy_scanner_scan_gz_files(sc, j.data, j.len, j.gz_files.data(), j.gz_files.size(), MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                     case JobKind::GZ_WINDOW: d.status = matchy_scanner_scan_gz_window(sc, j.data, j.len, &window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
+                    case JobKind::GZ_STREAM: d.status = matchy_scanner_scan_gz_stream(sc, j.data, j.len, &stream_window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                 }
                 if (j.is_gz()) {   // the batch's data / len become the inflated text, which the result owns
                     d.data = nullptr; d.len = 0;
@@ -375,6 +379,16 @@ int32_t matchy_multi_scanner_submit_gz_window(matchy_multi_scanner_t* h, const u
     MultiJob j{JobKind::GZ_WINDOW, packed, packed_len, tag};
     j.gz_text = want_text; j.carry_cap = window->carry_cap; j.window_flags = window->flags;
     if (window->carry_len) j.carry.assign(window->carry, window->carry + window->carry_len);
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_gz_stream(matchy_multi_scanner_t* h, const uint8_t* packed, size_t packed_len, const matchy_gz_stream_window_t* window, bool want_text,
+                                              void* tag) {
+    if (!h) { set_error("matchy_multi_scanner_submit_gz_stream: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (const char* why = gz_stream_refusal(packed, packed_len, window)) { set_error(std::string("matchy_multi_scanner_submit_gz_stream: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiJob j{JobKind::GZ_STREAM, packed, packed_len, tag};
+    j.gz_text = want_text; j.carry_cap = window->carry_cap; j.window_flags = window->flags; j.stream_text_cap = window->text_cap;
+    if (window->carry_len) j.carry.assign(window->carry, window->carry + window->carry_len);
+    if (!(window->flags & MATCHY_STREAM_FIRST)) j.stream_state = std::make_unique<matchy_gz_stream_state_t>(*window->state);
     return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
 }
 size_t matchy_multi_scanner_pending(const matchy_multi_scanner_t* h) {
