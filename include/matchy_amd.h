@@ -827,6 +827,41 @@ void matchy_scanner_get_whole_lines_counters(const matchy_scanner_t *scanner, ui
 void matchy_scanner_get_whole_lines_timing(const matchy_scanner_t *scanner, float out_ms[3]);
 /* The mode for every worker's scanner; needs matchy_multi_scanner_pending() == 0 (MATCHY_ERROR_INVALID_PARAM otherwise). */
 int32_t matchy_multi_scanner_set_whole_lines(matchy_multi_scanner_t *ms, bool enabled);
+
+/* ---- UTF-16 inputs (opt-in: with these calls never made a scanner allocates, launches and copies nothing more and every output stays
+ * as it is). `data` — host or device memory — is `len` bytes of UTF-16 in the given byte order; it is transcoded to UTF-8 on the GPU
+ * (count, prefix, write: three passes over the batch and one 16-byte read of the text's length) and the ordinary lookup scan runs over
+ * the UTF-8 text on the same stream.
+ *   len / 2 code units; a surrogate pair becomes the 4 bytes of its code point; every unpaired surrogate and an odd last byte become
+ *   EF BF BD (U+FFFD) each — Rust's String::from_utf16_lossy, with one more U+FFFD for the odd byte. CPython's codec differs in one
+ *   place: it writes ONE U+FFFD for a high surrogate followed by an odd last byte, this call writes two.
+ *   No BOM handling: the bytes handed in are transcoded, U+FEFF becomes EF BB BF and U+FFFE becomes EF BF BE. Skip a BOM before the call.
+ * Every fetch mode of matchy_scanner_scan_device, line context, hit lines, rendered records and the tally work as they do there:
+ * `bytes` is the length of the UTF-8 text, `lines` counts its '\n' bytes and the offsets of hits and line records are offsets into it.
+ * want_text: the UTF-8 batch is copied to pinned host memory once, behind the scan, for matchy_scan_hit_to_json and the NDJSON calls.
+ * NOT combined with segments or whole-line queries. MATCHY_ERROR_INVALID_PARAM with a message, and a scanner that stays usable: NULL
+ * handles, byte_order above 1, an input whose bound 3 * (len / 2) + 3 * (len & 1) reaches 2^31, a pending segment table (dropped) and
+ * whole-line mode. */
+#define MATCHY_UTF16_LE 0u
+#define MATCHY_UTF16_BE 1u
+int32_t matchy_scanner_scan_utf16(matchy_scanner_t *scanner, const uint8_t *data, size_t len, uint32_t byte_order, uint32_t fetch_mode,
+                                  bool want_text, matchy_scan_result_t *out);
+/* text / text_len: the UTF-8 batch — NULL / its length without want_text; borrowed from the scanner until its next scan, or owned by
+ * the result for MATCHY_SCAN_FETCH_SORTED (like the hit arrays of that mode). code_units: len / 2. replaced: U+FFFD written.
+ * MATCHY_ERROR_INVALID_PARAM for a result of another kind of scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_utf16(const matchy_scan_result_t *result, const uint8_t **text, size_t *text_len, uint64_t *code_units,
+                                 uint64_t *replaced);
+/* Milliseconds of the count, prefix and write steps of the last UTF-16 scan (recorded for every such scan, with or without
+ * matchy_scanner_set_profile: four event records per batch); zeros before the first. */
+void matchy_scanner_get_utf16_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* Input bytes per tile of the passes, and tiles per workgroup of the prefix step (tests place their cases on these boundaries). */
+void matchy_amd_utf16_geometry(uint32_t out[2]);
+/* matchy_multi_scanner_submit of a UTF-16 batch: the worker that takes it transcodes and scans it on its GPU. The batch from _next
+ * answers matchy_scan_result_utf16; its data / len are the UTF-8 text, owned by the result, and its length — NULL and the length
+ * without want_text. pinned_range as for matchy_multi_scanner_submit. A batch armed with matchy_multi_scanner_set_render that is
+ * submitted without want_text is scanned with line context whatever the setting is, like an armed gz pack. */
+int32_t matchy_multi_scanner_submit_utf16(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, uint32_t byte_order, bool want_text,
+                                          void *tag, const void *pinned_range);
 /* Deterministic builds for tests: fixes the build_epoch metadata value. */
 int32_t matchy_builder_set_build_epoch(matchy_builder_t *b, uint64_t epoch);
 

@@ -68,7 +68,11 @@ EXPORTED_SYMBOLS = [
     "matchy_multi_scanner_set_render",
     "matchy_scanner_set_whole_lines", "matchy_scanner_whole_lines", "matchy_scanner_get_whole_lines_counters",
     "matchy_scanner_get_whole_lines_timing", "matchy_multi_scanner_set_whole_lines",
+    "matchy_scanner_scan_utf16", "matchy_scan_result_utf16", "matchy_scanner_get_utf16_timing", "matchy_amd_utf16_geometry",
+    "matchy_multi_scanner_submit_utf16",
 ]
+
+UTF16_LE, UTF16_BE = 0, 1   # MATCHY_UTF16_*: the byte order of a UTF-16 scan (Scanner.scan_utf16)
 
 # MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
 GZ_OK, GZ_BAD_HEADER, GZ_TRUNCATED, GZ_BAD_BLOCK, GZ_BAD_CODES, GZ_BAD_SYMBOL, GZ_BAD_DISTANCE = 0, 1, 2, 3, 4, 5, 6
@@ -406,6 +410,11 @@ def lib():
         "matchy_scanner_scan_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
         "matchy_scan_result_gz": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "matchy_scanner_get_gz_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_scanner_scan_utf16": (C.c_int32, [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_utf16": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "matchy_scanner_get_utf16_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_amd_utf16_geometry": (None, [C.POINTER(C.c_uint32)]),
+        "matchy_multi_scanner_submit_utf16": (C.c_int32, [vp, vp, C.c_size_t, C.c_uint32, C.c_bool, vp, vp]),
         "matchy_multi_scanner_submit_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_bool, vp]),
         "matchy_scanner_scan_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
         "matchy_scan_result_gz_files": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
@@ -820,6 +829,16 @@ class ScanResult:
         ga = self._gz_arrays()
         return None if ga is None else ga[3]
 
+    def utf16(self):
+        """what a UTF-16 scan (Scanner.scan_utf16; matchy_scan_result_utf16) says about its batch, as a dict: text (the UTF-8 batch as
+        bytes, a copy; None without want_text), text_len, code_units and replaced (U+FFFD written); None for any other scan"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        t, n, units, repl = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64()
+        if lib().matchy_scan_result_utf16(C.byref(self._raw), C.byref(t), C.byref(n), C.byref(units), C.byref(repl)) != 0:
+            return None
+        return dict(text=C.string_at(t.value, n.value) if t.value else None, text_len=int(n.value), code_units=int(units.value), replaced=int(repl.value))
+
     def gz_window(self):
         """(WINDOW_* status, carry bytes) of a gz scan of a window (Scanner.scan_gz_window): the carry is the partial line behind the
         window's last newline, to be handed to the next window; None for any other scan"""
@@ -1205,6 +1224,27 @@ class Scanner:
             raise RuntimeError(f"matchy_scanner_scan_gz failed: rc={rc} {last_error()}")
         return ScanResult(self, raw)
 
+    def scan_utf16(self, data, byte_order=UTF16_LE, want_text=False, fetch_mode=1, nbytes=None) -> ScanResult:
+        """transcode the UTF-16 batch `data` to UTF-8 on the GPU and scan the text (matchy_scanner_scan_utf16). data: bytes, or an
+        address (host or device memory) together with nbytes. The result's offsets are offsets into the UTF-8 text; utf16() has the
+        text (with want_text), its length, the code units and the U+FFFD written. No BOM handling."""
+        if isinstance(data, int):
+            ptr, n = data, int(nbytes)
+        else:
+            data = bytes(data)
+            ptr, n = C.cast(C.c_char_p(data), C.c_void_p), len(data)
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_utf16(self._h, ptr, n, byte_order, fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_utf16 failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
+    def utf16_timing_ms(self):
+        """(count, prefix, write) milliseconds of the last UTF-16 scan; zeros before the first"""
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_utf16_timing(self._h, out)
+        return tuple(out)
+
     def scan_gz_files(self, blobs, want_text=False, fetch_mode=1) -> ScanResult:
         """inflate the gzip files `blobs` (bytes each, of one member or many) on the GPU, one wave per member, and scan them as one batch
         of len(blobs) segments (matchy_scanner_scan_gz_files). The result has .segments / .segment_of like a segmented scan,
@@ -1426,6 +1466,13 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_gz_stream failed ({rc}): " + last_error())
 
+    def submit_utf16_ptr(self, host_ptr: int, nbytes: int, byte_order=UTF16_LE, want_text=False, tag: int = 0):
+        """queue one UTF-16 batch that lives at a host address (matchy_multi_scanner_submit_utf16). next() then carries "utf16" (code
+        units and U+FFFD written) and "text": the UTF-8 batch with want_text, else None"""
+        rc = lib().matchy_multi_scanner_submit_utf16(self._h, host_ptr, nbytes, byte_order, bool(want_text), tag, None)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_utf16 failed ({rc}): " + last_error())
+
     def submit_gz_ptr(self, host_ptr: int, nbytes: int, members, want_text=False, tag: int = 0):
         """queue a pack of gzip files that lives at a host address: members = [(offset, len, out_len)] (matchy_multi_scanner_submit_gz).
         next() then carries gz_status, the segment table and, with want_text, the inflated text"""
@@ -1508,6 +1555,10 @@ class MultiScanner:
                 out["window_status"], out["carry"] = r.gz_window()
             if r.gz_stream() is not None:
                 out["gz_stream"] = r.gz_stream()
+        u = r.utf16()
+        if u is not None:   # a UTF-16 batch: data / len are the UTF-8 text (NULL without want_text) and its length
+            out["text"] = C.string_at(b.data, b.len) if b.data else None
+            out["utf16"] = dict(text_len=u["text_len"], code_units=u["code_units"], replaced=u["replaced"])
         r.close()
         return out
 
@@ -1543,6 +1594,13 @@ class MultiScanner:
             self.close()
         except Exception:
             pass
+
+
+def utf16_geometry():
+    """(input bytes per tile, tiles per workgroup of the prefix step) of the UTF-16 passes (matchy_amd_utf16_geometry)"""
+    out = (C.c_uint32 * 2)()
+    lib().matchy_amd_utf16_geometry(out)
+    return int(out[0]), int(out[1])
 
 
 def numa_cpus(sysfs_root: str, pci_bus_id: str):

@@ -26,6 +26,46 @@ inline size_t newline_cut(const uint8_t* base, size_t pos, size_t size, size_t b
     return fw ? (size_t)((const uint8_t*)fw - base) + 1 : size;
 }
 
+// The same rule over UTF-16 code units (byte_order: MATCHY_UTF16_LE / _BE): base[0] is the first byte of the stream that is transcoded
+// and `pos` is even, so units lie at even offsets. A batch ends behind a 000A unit: the window's last one that lies inside it as a
+// whole, or — a line longer than the window — the first one behind those, or at `size`. '\n' is no surrogate, so no pair and no line
+// spans two batches; every cut but `size` is even, and an odd last byte can only be the input's last. A 0A that is the other byte
+// of a unit (U+0A41), or a 00 0A at an odd offset (xx00 0Ayy), is no line end.
+inline bool is_newline16(const uint8_t* u, uint32_t byte_order) { return u[byte_order ? 1 : 0] == '\n' && u[byte_order ? 0 : 1] == 0; }
+// offset behind the last 000A unit that lies in b[0, n) as a whole, 0: none
+inline size_t last_newline16(const uint8_t* b, size_t n, uint32_t byte_order) {
+    for (size_t i = n & ~(size_t)1; i >= 2; i -= 2)
+        if (is_newline16(b + i - 2, byte_order)) return i;
+    return 0;
+}
+// offset behind the first 000A unit that starts at or behind `from` (rounded down to a unit) and lies in b[0, n) as a whole, 0: none
+inline size_t first_newline16(const uint8_t* b, size_t from, size_t n, uint32_t byte_order) {
+    for (size_t i = from & ~(size_t)1; i + 2 <= n; i += 2)
+        if (is_newline16(b + i, byte_order)) return i + 2;
+    return 0;
+}
+inline size_t newline_cut16(const uint8_t* base, size_t pos, size_t size, size_t batch_bytes, uint32_t byte_order) {
+    if (size - pos <= batch_bytes) return size;
+    if (const size_t k = last_newline16(base + pos, batch_bytes, byte_order)) return pos + k;
+    const size_t k = first_newline16(base + pos, batch_bytes, size - pos, byte_order);
+    return k ? pos + k : size;
+}
+
+// What read_batches needs of a cut rule, over a buffer that starts at a batch's first byte. whole: the cut of b[0, have) when nothing
+// follows it; last: the offset behind the last line end inside the window b[0, n), 0 = none; first: behind the first line end at or
+// behind `from`, 0 = none in b[0, n) yet.
+struct CutBytes {
+    size_t whole(const uint8_t* b, size_t have, size_t batch_bytes) const { return newline_cut(b, 0, have, batch_bytes); }
+    size_t last(const uint8_t* b, size_t n) const { const void* nl = memrchr(b, '\n', n); return nl ? (size_t)((const uint8_t*)nl - b) + 1 : 0; }
+    size_t first(const uint8_t* b, size_t from, size_t n) const { const void* nl = memchr(b + from, '\n', n - from); return nl ? (size_t)((const uint8_t*)nl - b) + 1 : 0; }
+};
+struct CutUnits16 {
+    uint32_t byte_order;
+    size_t whole(const uint8_t* b, size_t have, size_t batch_bytes) const { return newline_cut16(b, 0, have, batch_bytes, byte_order); }
+    size_t last(const uint8_t* b, size_t n) const { return last_newline16(b, n, byte_order); }
+    size_t first(const uint8_t* b, size_t from, size_t n) const { return first_newline16(b, from, n, byte_order); }
+};
+
 // malloc'ed bytes (no value-initialisation: a 256 MiB batch buffer would be zeroed before every read; realloc grows it for a long
 // line). Whoever takes a batch from the reader owns it; across the C ABI it travels as release() and comes back through free().
 struct FreeBytes { void operator()(uint8_t* p) const { free(p); } };
@@ -37,8 +77,10 @@ enum class StreamEnd { DONE, STOPPED, FAILED };   // STOPPED: the sink returned 
 // batches cut EXACTLY where newline_cut cuts the whole stream, whatever sizes the reads return. For that a window is decided only
 // once a byte behind it has been read, or the end of input is known: a stream that ends on a window goes out whole, as it does mapped.
 // The rest behind a cut is carried into the next buffer. 16 spare bytes lie behind every buffer; an empty stream has no batch.
-template <class Read, class Sink>
-StreamEnd read_batches(Read rd, size_t batch_bytes, Sink sink) {
+// read_batches_cut is the reader under a cut rule (CutBytes, CutUnits16); read_batches is the one of newline_cut, read_batches16 the one
+// of newline_cut16.
+template <class Read, class Sink, class Cut>
+StreamEnd read_batches_cut(Read rd, size_t batch_bytes, Sink sink, Cut rule) {
     const size_t SPARE = 16, MAX_READ = (size_t)1 << 30;
     size_t cap = batch_bytes + 1, have = 0, searched = 0;   // searched != 0: no '\n' in buf[0, searched)
     uint64_t off = 0;
@@ -47,15 +89,14 @@ StreamEnd read_batches(Read rd, size_t batch_bytes, Sink sink) {
     if (!buf) return StreamEnd::FAILED;
     for (;;) {
         size_t cut = 0;   // 0 = undecided: more bytes are needed
-        if (eof) cut = newline_cut(buf.get(), 0, have, batch_bytes);
+        if (eof) cut = rule.whole(buf.get(), have, batch_bytes);
         else if (have > batch_bytes) {
-            const void* nl = searched ? nullptr : memrchr(buf.get(), '\n', batch_bytes);
-            if (!nl) {   // a line longer than the window: to its end, looking at every byte once however the reads arrive
+            cut = searched ? 0 : rule.last(buf.get(), batch_bytes);
+            if (!cut) {   // a line longer than the window: to its end, looking at every byte once however the reads arrive
                 if (searched < batch_bytes) searched = batch_bytes;
-                nl = memchr(buf.get() + searched, '\n', have - searched);
+                cut = rule.first(buf.get(), searched, have);
                 searched = have;
             }
-            if (nl) cut = (size_t)((const uint8_t*)nl - buf.get()) + 1;
         }
         if (!cut) {
             if (eof) return StreamEnd::DONE;
@@ -84,6 +125,11 @@ StreamEnd read_batches(Read rd, size_t batch_bytes, Sink sink) {
         off += cut; have = rest; searched = 0;
     }
 }
+
+template <class Read, class Sink>
+StreamEnd read_batches(Read rd, size_t batch_bytes, Sink sink) { return read_batches_cut(rd, batch_bytes, sink, CutBytes{}); }
+template <class Read, class Sink>
+StreamEnd read_batches16(Read rd, size_t batch_bytes, uint32_t byte_order, Sink sink) { return read_batches_cut(rd, batch_bytes, sink, CutUnits16{byte_order}); }
 
 // The whole pages inside [p, p + n): [a, b), true when there is one. Neighbouring batches never share a page of these ranges.
 inline bool inner_pages(const void* p, size_t n, uintptr_t& a, uintptr_t& b) {

@@ -399,6 +399,13 @@ const char* mxy::capi::gz_stream_refusal(const uint8_t* packed, size_t packed_le
     return nullptr;
 }
 
+const char* mxy::capi::utf16_refusal(const uint8_t* data, size_t len, uint32_t byte_order) {
+    if (!data && len) return "no input";
+    if (byte_order > MATCHY_UTF16_BE) return "byte_order is MATCHY_UTF16_LE or MATCHY_UTF16_BE";
+    if (len >= ((size_t)1 << 31) || utf16::out_bound(len) >= (1ull << 31)) return "the input may transcode to 2^31 bytes or more (3 bytes per code unit); cut it into smaller batches";
+    return nullptr;
+}
+
 // hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
 namespace {
 struct TallyInternal {
@@ -1237,6 +1244,53 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
+// UTF-16 inputs (Scanner::utf16_transcode, utf16.hip): the transcoding and the scan are queued on the scanner's own stream; the fetch is
+// that of matchy_scanner_scan_device
+static_assert(MATCHY_UTF16_LE == utf16::ORDER_LE && MATCHY_UTF16_BE == utf16::ORDER_BE, "the kernels take MATCHY_UTF16_* values directly");
+int32_t matchy_scanner_scan_utf16(matchy_scanner_t* s, const uint8_t* data, size_t len, uint32_t byte_order, uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out) {
+    if (!s || !out) { set_error("matchy_scanner_scan_utf16: no scanner or no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    memset(out, 0, sizeof(*out));
+    if (const char* why = utf16_refusal(data, len, byte_order)) { set_error(std::string("matchy_scanner_scan_utf16: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    ScannerH* h = reinterpret_cast<ScannerH*>(s);
+    try {
+        const Scanner::GzBatch b = h->sc->utf16_transcode(data, len, byte_order);   // refuses segments and whole-line mode
+        if (b.len >= 0x7FFF0000u) throw ParamError{"matchy_scanner_scan_utf16: the text reaches 2^31 bytes; cut the input into smaller batches"};
+        const FetchPlan plan(fetch_mode);
+        ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
+        const bool hit_lines = build_request(*h->sc, plan, b.text, b.len, b.stream, false, true, rq);
+        h->sc->scan_device(rq, b.stream);
+        h->sc->utf16_queue_text(want_text);
+        ScanOutput so;
+        h->sc->fetch(so, false, b.stream, plan.hit_mode(), plan.sorted);
+        const Utf16Transcode::Result u = h->sc->utf16_finish();
+        finish_result(*h->sc, plan, so, u.text_len, hit_lines, out);
+        ScanResultInternal* in = internal_of(out);
+        in->has_utf16 = true;
+        in->utf16_text = u.text; in->utf16_text_len = u.text_len;
+        in->utf16_code_units = u.code_units; in->utf16_replaced = u.replaced;
+        if (plan.sorted && u.text) { in->utf16_text_own.assign(u.text, u.text + u.text_len); in->utf16_text = in->utf16_text_own.data(); }
+        return MATCHY_SUCCESS;
+    } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+int32_t matchy_scan_result_utf16(const matchy_scan_result_t* r, const uint8_t** text, size_t* text_len, uint64_t* code_units, uint64_t* replaced) {
+    if (!r) { set_error("matchy_scan_result_utf16: no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_utf16) { set_error("matchy_scan_result_utf16: the result was not produced by a UTF-16 scan"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (text) *text = in->utf16_text;
+    if (text_len) *text_len = in->utf16_text_len;
+    if (code_units) *code_units = in->utf16_code_units;
+    if (replaced) *replaced = in->utf16_replaced;
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_utf16_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->utf16_timing(out);
+}
+void matchy_amd_utf16_geometry(uint32_t out[2]) {
+    if (out) { out[0] = utf16::TILE_BYTES; out[1] = UTF16_SCAN_CHUNK; }
+}
+
 int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, uint32_t fetch_mode,
                                bool want_text, matchy_scan_result_t* out) {
     if (!s || !out) return MATCHY_ERROR_INVALID_PARAM;

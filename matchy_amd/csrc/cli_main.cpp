@@ -38,6 +38,9 @@ int usage() {
             "                                    finished NDJSON; the others, and any the GPU refuses, are rendered on the host; same output; not with --follow)\n"
             "               [--whole-lines]   (every input line is ONE query, looked up whole like `matchy query` does a value: lists of addresses, names or\n"
             "                                  hashes; no extraction; not with --extractors, --pack-inputs, --gz-on-gpu, --gather-lines, --render-on-gpu)\n"
+            "               [--encoding=utf-16le|utf-16be|auto]   (UTF-16 inputs are transcoded to UTF-8 on the GPU in front of the scan; auto: per input, by a\n"
+            "                                  leading BOM, anything else is scanned as bytes; a leading BOM is skipped; offsets are those of the UTF-8 text;\n"
+            "                                  not with --follow, --pack-inputs, --gz-on-gpu, --whole-lines)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"

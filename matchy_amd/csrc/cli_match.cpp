@@ -16,6 +16,8 @@
 // --gz-stream-windows (with --gz-on-gpu --gz-pieces) does the same for a .gz file of ONE member that does not fit a batch: a chain of
 // windows of its DEFLATE stream (matchy_multi_scanner_submit_gz_stream; gz_stream.h walks it), each handing the bit it stopped at, the
 // CRC and length so far and the last 32 KiB of text to the next, with the partial line.
+// --encoding=utf-16le|utf-16be|auto sends the batches of UTF-16 inputs to the GPU as they are (matchy_multi_scanner_submit_utf16, utf16.hip):
+// cut behind 000A units (newline_cut16), transcoded to UTF-8 there and scanned; records, offsets and lines are those of the UTF-8 text.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -81,7 +83,10 @@ struct GzVerdict {
 // compressed, one segment each. GZ_WINDOW (--gz-windows): one window of whole members of one gzip file: ONE segment like a pack of one
 // file, but its lines count on from those of the windows in front. GZ_STREAM (--gz-stream-windows): one window of ONE DEFLATE stream, a
 // segment whose lines count on in the same way.
-enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW, GZ_STREAM };
+// UTF16 (--encoding): a piece of one UTF-16 input that ends behind a 000A unit; what comes back is its UTF-8 text.
+enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW, GZ_STREAM, UTF16 };
+// --encoding: how the bytes of an input are read. AUTO decides per input by its first two bytes (FF FE / FE FF, else BYTES).
+enum class Encoding { BYTES, UTF16LE, UTF16BE, AUTO };
 struct Batch {
     BatchKind kind = BatchKind::STREAM;
     size_t input = 0;                   // the input of a stream batch or a window; the first of a pack
@@ -98,18 +103,21 @@ struct Batch {
     std::shared_ptr<matchy_gz_stream_state_t> stream_state;   // GZ_STREAM: the state the window in front handed out (none for the first)
     uint32_t stream_text_cap = 0, stream_flags = 0;           // GZ_STREAM: MATCHY_STREAM_*
     bool window_last = false;           // GZ_WINDOW: the file ends with this window
+    uint32_t byte_order = 0;            // UTF16: MATCHY_UTF16_*
     bool armed = false;                 // --render-on-gpu: the batch was submitted with matchy_multi_scanner_set_render
 
     bool is_gz() const { return kind == BatchKind::GZ_PACK || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
-    bool segmented() const { return kind != BatchKind::STREAM; }   // the scan result carries a segment table
+    bool segmented() const { return kind != BatchKind::STREAM && kind != BatchKind::UTF16; }   // the scan result carries a segment table
+    // the batch's text is made on the device: it comes back only where wants_text says so
+    bool text_on_device() const { return is_gz() || kind == BatchKind::UTF16; }
     // the batch goes on where its input's earlier batches ended: only the first has line base 0 (every segment of a pack is a whole file)
-    bool continues_lines() const { return kind == BatchKind::STREAM || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
-    // a gz batch: its inflated text comes back only where something is rendered from it on the host
+    bool continues_lines() const { return kind == BatchKind::STREAM || kind == BatchKind::UTF16 || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
+    // a gz or UTF-16 batch: its text comes back only where something is rendered from it on the host
     bool wants_text(bool json, bool gather) const { return json && !gather && !armed; }
     // every input the batch carries, in segment order
     template <class F> void each_input(F&& f) const {
         switch (kind) {
-            case BatchKind::STREAM: f(input); break;
+            case BatchKind::STREAM: case BatchKind::UTF16: f(input); break;
             case BatchKind::PACK: for (const PackedInput& pi : pack) f(pi.input); break;
             case BatchKind::GZ_PACK: case BatchKind::GZ_WINDOW: case BatchKind::GZ_STREAM: for (const GzFile& g : gz) f(g.input); break;
         }
@@ -167,6 +175,19 @@ struct MatchPipeline {
         matchy_scanner_get_whole_lines_counters(sc, c);
         for (int k = 0; k < 4; ++k) wl_counters[k] += c[k];
     }
+    // --encoding: what the UTF-16 batches say about themselves, summed for -s (the times: count, prefix, write)
+    std::atomic<size_t> u16_inputs{0}, u16_batches{0};
+    std::atomic<unsigned long long> u16_units{0}, u16_replaced{0};
+    double u16_ms[3] = {0, 0, 0};   // guarded by mu
+    void add_utf16(const matchy_scanner_t* sc, const matchy_scan_result_t& r) {
+        uint64_t units = 0, replaced = 0;
+        float ms[3] = {0, 0, 0};
+        if (matchy_scan_result_utf16(&r, nullptr, nullptr, &units, &replaced) != MATCHY_SUCCESS) return;
+        matchy_scanner_get_utf16_timing(sc, ms);
+        ++u16_batches; u16_units += units; u16_replaced += replaced;
+        std::lock_guard<std::mutex> lk(mu);
+        for (int k = 0; k < 3; ++k) u16_ms[k] += ms[k];
+    }
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
     // arms the library for the batch about to be submitted, where its line bases are known
     void arm(Batch& b) {
@@ -212,6 +233,7 @@ struct MatchPipeline {
         const bool text = hb->wants_text(json, gather);
         switch (hb->kind) {
             case BatchKind::STREAM: rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg); break;
+            case BatchKind::UTF16: rc = matchy_multi_scanner_submit_utf16(ms, hb->ptr, hb->len, hb->byte_order, text, hb, hb->reg); break;
             case BatchKind::PACK: {
                 std::vector<uint32_t> starts;
                 for (const PackedInput& pi : hb->pack) starts.push_back(pi.start);
@@ -310,14 +332,15 @@ struct MatchPipeline {
         }
         // an armed gz pack comes back without its text: the library scans it with line context, and its "Lines with matches" are the
         // table's like those of any pack scanned with line context (plain batches of the same run are counted from their text as before)
-        const bool table_counts = line_ctx || gather || (b.armed && b.is_gz());
+        // (an armed UTF-16 batch likewise: its count is the scan's own)
+        const bool table_counts = line_ctx || gather || (b.armed && b.text_on_device());
         if (table_counts && b.segmented()) {   // per segment, from the table the GPU filled
             const matchy_scan_segment_t* segs = nullptr;
             size_t n_segs = 0;
             if (matchy_scan_result_segments(&r, nullptr, nullptr, &segs, &n_segs) == MATCHY_SUCCESS) for (size_t k = 0; k < n_segs; ++k) t.lines_with_matches += segs[k].lines_with_matches;
             else { fprintf(stderr, "[ERROR] no segments in the scan result of a pack: %s\n", matchy_amd_last_error()); d.ok = false; }
             if (line_ctx || !d.ok) return;
-        } else if (line_ctx || gather) {
+        } else if (table_counts) {
             uint64_t lwm = 0;
             if (matchy_scan_result_lines(&r, nullptr, nullptr, &lwm) == MATCHY_SUCCESS) t.lines_with_matches += lwm;
             else { fprintf(stderr, "[ERROR] no line context in a scan result: %s\n", matchy_amd_last_error()); d.ok = false; }
@@ -369,6 +392,7 @@ struct MatchPipeline {
         MatchPipeline* pl = (MatchPipeline*)user;
         Done* d = new Done();
         if (pl->whole_lines) pl->add_whole_lines(sc);
+        if (((const Batch*)tag)->kind == BatchKind::UTF16) pl->add_utf16(sc, *r);
         pl->render(sc, *r, data, len, *(const Batch*)tag, *d);
         return d;
     }
@@ -433,8 +457,20 @@ struct MatchPipeline {
 // released by the printer as their files complete. skip (inputs that are read): the first `skip` bytes of the stream — what the gz windows
 // in front have reported already (--gz-windows), which ends behind a '\n' — are read and cut into batches like the rest, so the cuts
 // are those of the whole stream, but not submitted; 0 is the whole input.
-bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t batch_bytes, uint64_t skip = 0) {
+// enc (--encoding): UTF16LE / UTF16BE read the input's byte stream — the mapped file, stdin, or what gzread returns — as UTF-16 in that
+// byte order, AUTO does so when the stream begins with FF FE or FE FF and reads anything else as bytes. A leading BOM of the byte order
+// in effect is skipped: it is not part of the text. The batches are cut behind 000A units (newline_cut16) and go out as they are.
+bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t batch_bytes, uint64_t skip = 0, Encoding enc = Encoding::BYTES) {
     const bool gz = ends_with_ci(path, ".gz");
+    // the byte order for a stream that begins with b[0 .. n): -1 = bytes; `bom` = bytes of the BOM to skip
+    auto utf16_order = [enc](const uint8_t* b, size_t n, size_t& bom) {
+        bom = 0;
+        const bool le = n >= 2 && b[0] == 0xFF && b[1] == 0xFE, be = n >= 2 && b[0] == 0xFE && b[1] == 0xFF;
+        if (enc == Encoding::BYTES || (enc == Encoding::AUTO && !le && !be)) return -1;
+        const int order = enc == Encoding::UTF16LE ? (int)MATCHY_UTF16_LE : enc == Encoding::UTF16BE ? (int)MATCHY_UTF16_BE : le ? (int)MATCHY_UTF16_LE : (int)MATCHY_UTF16_BE;
+        if (order == (int)MATCHY_UTF16_LE ? le : be) bom = 2;
+        return order;
+    };
     int fd = path == "-" ? 0 : open(path.c_str(), O_RDONLY);
     if (fd < 0) { fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), strerror(errno)); return false; }
     struct stat sb;
@@ -444,11 +480,16 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
         if (m != MAP_FAILED) {
             close(fd);
             (void)madvise(m, size, MADV_SEQUENTIAL);
-            const uint8_t* base = (const uint8_t*)m;
+            size_t bom = 0;
+            const int order = utf16_order((const uint8_t*)m, size, bom);
+            if (order >= 0) ++pl.u16_inputs;
+            const uint8_t* base = (const uint8_t*)m + bom;   // the first byte that is scanned (or transcoded: units lie at even offsets from it)
+            const size_t text_size = size - bom;
             size_t last_seq = 0;
-            for (size_t pos = 0; pos < size;) {
-                const size_t end = newline_cut(base, pos, size, batch_bytes);
+            for (size_t pos = 0; pos < text_size;) {
+                const size_t end = order >= 0 ? newline_cut16(base, pos, text_size, batch_bytes, (uint32_t)order) : newline_cut(base, pos, text_size, batch_bytes);
                 Batch b;
+                if (order >= 0) { b.kind = BatchKind::UTF16; b.byte_order = (uint32_t)order; }
                 b.input = input; b.ptr = base + pos; b.len = end - pos;
                 b.reg = prefault_and_pin(b.ptr, b.len);
                 last_seq = pl.submit(std::move(b));
@@ -466,22 +507,43 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
         gzbuffer(zf, 1u << 20);
     }
     size_t total_read = 0;
-    const StreamEnd e = read_batches(
-        [&](void* p, size_t n) {
-            const ssize_t r = gz ? (ssize_t)gzread(zf, p, (unsigned)n) : read(fd, p, n);
-            if (r < 0 && gz) errno = EIO;   // the decoder keeps its error: a retry would fail again
-            return r;
-        },
-        batch_bytes,
-        [&](Bytes&& data, size_t len, uint64_t off) {
-            total_read += len;
-            if (off + len <= skip) return true;   // reported already
-            const size_t drop = off < skip ? (size_t)(skip - off) : 0;   // skip lies behind a '\n': what is left starts a line
-            Batch b;
-            b.input = input; b.ptr = data.get() + drop; b.len = len - drop; b.own = std::move(data);
-            pl.submit(std::move(b));
-            return true;
-        });
+    auto rd_raw = [&](void* p, size_t n) {
+        const ssize_t r = gz ? (ssize_t)gzread(zf, p, (unsigned)n) : read(fd, p, n);
+        if (r < 0 && gz) errno = EIO;   // the decoder keeps its error: a retry would fail again
+        return r;
+    };
+    // --encoding: the stream's first two bytes are read ahead; what is no BOM to skip is handed to the batch reader first
+    uint8_t head[2];
+    size_t n_head = 0, head_pos = 0;
+    int order = -1;
+    bool head_failed = false;
+    if (enc != Encoding::BYTES) {
+        while (n_head < 2) {
+            const ssize_t r = rd_raw(head + n_head, 2 - n_head);
+            if (r < 0) { if (errno == EINTR) continue; head_failed = true; break; }
+            if (r == 0) break;
+            n_head += (size_t)r;
+        }
+        size_t bom = 0;
+        order = utf16_order(head, n_head, bom);
+        head_pos = bom;
+        if (order >= 0) ++pl.u16_inputs;
+    }
+    auto rd = [&](void* p, size_t n) -> ssize_t {
+        if (head_pos < n_head) { const size_t k = std::min(n, n_head - head_pos); memcpy(p, head + head_pos, k); head_pos += k; return (ssize_t)k; }
+        return rd_raw(p, n);
+    };
+    auto sink = [&](Bytes&& data, size_t len, uint64_t off) {
+        total_read += len;
+        if (off + len <= skip) return true;   // reported already
+        const size_t drop = off < skip ? (size_t)(skip - off) : 0;   // skip lies behind a '\n': what is left starts a line
+        Batch b;
+        if (order >= 0) { b.kind = BatchKind::UTF16; b.byte_order = (uint32_t)order; }
+        b.input = input; b.ptr = data.get() + drop; b.len = len - drop; b.own = std::move(data);
+        pl.submit(std::move(b));
+        return true;
+    };
+    const StreamEnd e = head_failed ? StreamEnd::FAILED : order >= 0 ? read_batches16(rd, batch_bytes, (uint32_t)order, sink) : read_batches(rd, batch_bytes, sink);
     const bool ok = e == StreamEnd::DONE;
     if (!ok) { int ze; fprintf(stderr, "[ERROR] Failed to process %s: %s\n", path.c_str(), gz && errno == EIO ? gzerror(zf, &ze) : strerror(errno)); }
     if (gz) gzclose(zf);   // closes fd as well
@@ -576,8 +638,9 @@ struct HostReader {
     const std::vector<std::string>& paths;
     size_t batch_bytes;
     std::vector<char> failed;
+    Encoding encoding = Encoding::BYTES;   // --encoding
     // bytes: the gz side's batches stay below 2^31
-    void read(size_t i, uint64_t skip = 0, size_t bytes = 0) { if (!read_input(pl, i, paths[i], bytes ? bytes : batch_bytes, skip)) failed[i] = 1; }
+    void read(size_t i, uint64_t skip = 0, size_t bytes = 0) { if (!read_input(pl, i, paths[i], bytes ? bytes : batch_bytes, skip, encoding)) failed[i] = 1; }
 };
 
 // --gz-on-gpu, the reader's side. Which .gz input goes into the pack in hand and when a pack goes out is decided by the packer
@@ -756,6 +819,9 @@ struct MatchOptions {
     std::string format = "json", extractors, devices;
     bool stats = false, follow = false, line_numbers = false, input_line = false, tally = false, pack = false, gz_gpu = false, gz_members = false, gz_windows = false, gz_stream_windows = false, gather_lines = false, render_gpu = false, whole_lines = false;
     size_t tally_limit = 20;   // --tally[=N]: rows of the report, 0 = all
+    // --encoding=utf-16le|utf-16be|auto: UTF-16 inputs are transcoded on the GPU in front of the scan; `encoding_given`: the flag was there
+    Encoding encoding = Encoding::BYTES;
+    bool encoding_given = false;
     // --gz-pieces[=BYTES] (with --gz-on-gpu): one large DEFLATE stream is inflated by many waves, in pieces of BYTES compressed bytes; 0 = off.
     // The default is the best of the sweep of tools/gz_pieces_timing.py: 4, 8 and 16 KiB lie within 3 % of each other on
     // level 6 log text, whose blocks have about 32 KiB; from 32 KiB on a piece holds more than one block and the time doubles.
@@ -789,6 +855,13 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
         for (const auto& s : switches) if (a == s.name) { o.*s.on = true; is_switch = true; }
         if (is_switch) continue;
         if (eqval("--format", v)) o.format = v;
+        else if (eqval("--encoding", v)) {
+            o.encoding_given = true;
+            if (v == "utf-16le") o.encoding = Encoding::UTF16LE;
+            else if (v == "utf-16be") o.encoding = Encoding::UTF16BE;
+            else if (v == "auto") o.encoding = Encoding::AUTO;
+            else { fprintf(stderr, "Error: Unknown encoding: %s. Use 'utf-16le', 'utf-16be' or 'auto'\n", v.c_str()); return 1; }
+        }
         else if (eqval("--batch-bytes", v)) { size_t b = strtoull(v.c_str(), nullptr, 10); if (b >= 4096) o.batch_bytes = b; }
         else if (eqval("--extractors", v)) o.extractors = v;
         else if (eqval("--devices", v)) o.devices = v;
@@ -814,6 +887,17 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
     if (o.pos.size() < 2) return usage();
     auto refuse = [](const char* why) { fprintf(stderr, "Error: %s\n", why); return 1; };
     if (o.format != "json" && o.format != "summary") { fprintf(stderr, "Error: Unknown format: %s. Use 'json' or 'summary'\n", o.format.c_str()); return 1; }
+    if (o.encoding_given) {
+        // the batches of a UTF-16 input are transcoded whole, on the GPU, in front of a plain scan: no segments, no compressed bytes, no queries
+        if (o.follow) return refuse("--encoding is not supported with --follow (a followed file is read as bytes as it grows)");
+        if (o.pack) return refuse("--encoding is not supported with --pack-inputs (a UTF-16 batch has no segments)");
+        if (o.gz_gpu) return refuse("--encoding is not supported with --gz-on-gpu (the GPU inflates .gz inputs into UTF-8 text; without the flag they are inflated on the host and transcoded)");
+        if (o.gz_members) return refuse("--encoding is not supported with --gz-members (it extends --gz-on-gpu)");
+        if (o.gz_windows) return refuse("--encoding is not supported with --gz-windows (it extends --gz-on-gpu)");
+        if (o.gz_stream_windows) return refuse("--encoding is not supported with --gz-stream-windows (it extends --gz-on-gpu)");
+        if (o.gz_pieces) return refuse("--encoding is not supported with --gz-pieces (it extends --gz-on-gpu)");
+        if (o.whole_lines) return refuse("--encoding is not supported with --whole-lines (whole-line queries read their input as bytes)");
+    }
     if (o.gz_windows && !(o.gz_gpu && o.gz_members)) return refuse("--gz-windows needs --gz-on-gpu --gz-members (it extends them to multi-member files larger than a batch)");
     if (o.gz_stream_windows && !(o.gz_gpu && o.gz_pieces)) return refuse("--gz-stream-windows needs --gz-on-gpu --gz-pieces (it extends them to one DEFLATE stream larger than a batch)");
     if (o.gz_members && !o.gz_gpu) return refuse("--gz-members needs --gz-on-gpu (it extends the gz packs to files of many members)");
@@ -968,6 +1052,9 @@ void report_stats(const MatchOptions& o, const MatchPipeline& pl, const GzReader
     if (o.gz_members) fprintf(stderr, "[INFO] gz members on the GPU: %zu in %zu multi-member files\n", gzr.multi_members, gzr.multi_files);
     if (o.gz_stream_windows) fprintf(stderr, "[INFO] gz stream windows on the GPU: %zu windows of %zu files, %zu finished on the host\n", gzr.sw_windows, gzr.sw_files, gzr.sw_host);
     if (o.gz_windows) fprintf(stderr, "[INFO] gz windows on the GPU: %zu windows of %zu files, %zu finished on the host\n", gzr.win_windows, gzr.win_files, gzr.win_host);
+    if (pl.u16_inputs.load())
+        fprintf(stderr, "[INFO] UTF-16: %zu inputs transcoded on the GPU in %zu batches (%llu code units, %llu U+FFFD written; count %.2f ms, prefix %.2f ms, write %.2f ms)\n",
+                pl.u16_inputs.load(), pl.u16_batches.load(), pl.u16_units.load(), pl.u16_replaced.load(), pl.u16_ms[0], pl.u16_ms[1], pl.u16_ms[2]);
 }
 
 }  // namespace
@@ -1009,7 +1096,8 @@ int cmd_match(int argc, char** argv) {
     pl.json = o.format == "json";
     // --gz-on-gpu without records to render: no text comes back from a gz pack, so "Lines with matches" is counted on the GPU for every
     // batch (line context; with --format summary it changes nothing that is printed)
-    pl.line_ctx = o.line_numbers || o.input_line || (o.gz_gpu && !pl.json);
+    // (--encoding likewise: the text of a UTF-16 batch is made on the device and stays there when nothing is rendered from it)
+    pl.line_ctx = o.line_numbers || o.input_line || ((o.gz_gpu || o.encoding_given) && !pl.json);
     pl.input_line = o.input_line; pl.gather = o.gather_lines; pl.gz_members = o.gz_members; pl.whole_lines = o.whole_lines;
     pl.render_gpu = o.render_gpu;   // takes effect with --format json only (MatchPipeline::arm)
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);
@@ -1032,7 +1120,7 @@ int cmd_match(int argc, char** argv) {
     std::vector<char> input_failed(paths.size(), 0);
     pl.line_base.assign(paths.size(), 0);
     pl.consumed.assign(paths.size(), -1);
-    HostReader host{pl, paths, o.batch_bytes, std::vector<char>(paths.size(), 0)};
+    HostReader host{pl, paths, o.batch_bytes, std::vector<char>(paths.size(), 0), o.encoding};
     GzReader gzr(pl, host, o.gz_members, o.gz_windows, o.gz_pieces, o.gz_stream_windows);
     PackStats packed;
     run_inputs(o, pl, host, gzr, packed, t, input_failed);

@@ -1574,6 +1574,53 @@ Scanner::GzBatch Scanner::gz_inflate_stream(const uint8_t* packed, size_t packed
 void Scanner::gz_queue_results(bool want_text) { gz_->queue_results(want_text, host_stream_); }
 GzInflate::Result Scanner::gz_finish() { return gz_->finish(); }
 
+// UTF-16 inputs (utf16.h). Like a gz scan, the pass and the scan behind it share this scanner's own stream.
+Scanner::GzBatch Scanner::utf16_transcode(const uint8_t* src, size_t len, uint32_t byte_order) {
+    if (segments_ && segments_->pending()) {
+        set_segments(nullptr, 0);
+        throw ParamError{"UTF-16 inputs and segments cannot be combined"};
+    }
+    if (whole_lines_) throw ParamError{"UTF-16 inputs and whole-line mode cannot be combined"};
+    Utf16Transcode::check(src, len, byte_order);
+    MXY_HIP(hipSetDevice(ddb_->device));
+    host_stream_.create(hipStreamNonBlocking);
+    if (!utf16_) utf16_ = std::make_unique<Utf16Transcode>();
+    utf16_pin_.release();
+    // the input: device memory is read where it lies when it is aligned for 16-byte loads; device memory that is not is copied, and host
+    // memory travels the way a piece of scan_host does — the whole pages inside it pinned for the copy (or found pinned by this
+    // library), the bytes in front of and behind them as they are
+    const uint8_t* in = src;
+    hipPointerAttribute_t attr{};
+    const bool on_device = len && hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    if (len && !on_device) (void)hipGetLastError();   // a plain host pointer is no error
+    if (on_device && ((uintptr_t)src & 15u)) {
+        uint8_t* dst = utf16_->input_buffer(len);
+        MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToDevice, host_stream_));
+        in = dst;
+    } else if (len && !on_device) {
+        uint8_t* dst = utf16_->input_buffer(len);
+        static const bool no_reg = getenv("MATCHY_AMD_NO_REGISTER") != nullptr;
+        uintptr_t a = 0, b = 0;
+        if (!no_reg && len >= ((size_t)4 << 20) && inner_pages(src, len, a, b) && pins::acquire(a, b)) {
+            utf16_pin_.a = a; utf16_pin_.b = b;
+            const size_t head = (size_t)(a - (uintptr_t)src), mid = (size_t)(b - a), tail = len - head - mid;
+            if (head) MXY_HIP(hipMemcpyAsync(dst, src, head, hipMemcpyHostToDevice, host_stream_));
+            MXY_HIP(hipMemcpyAsync(dst + head, (const void*)a, mid, hipMemcpyHostToDevice, host_stream_));
+            if (tail) MXY_HIP(hipMemcpyAsync(dst + head + mid, (const void*)b, tail, hipMemcpyHostToDevice, host_stream_));
+        } else MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, host_stream_));
+        in = dst;
+    }
+    utf16_->launch(in, len, byte_order, n_cu_, true, host_stream_);   // always timed: four event records per batch, for `matchy match -s`
+    return GzBatch{utf16_->device_text(), utf16_->text_len(), host_stream_};
+}
+void Scanner::HostPin::release() { if (b > a) pins::release(a, b); a = b = 0; }
+void Scanner::utf16_queue_text(bool want_text) { utf16_->queue_results(want_text, host_stream_); }
+Utf16Transcode::Result Scanner::utf16_finish() {
+    const Utf16Transcode::Result r = utf16_->finish();
+    utf16_pin_.release();   // behind the fetch: the copy is done
+    return r;
+}
+
 size_t host_piece_bytes() {
     static const size_t v = [] {
         const unsigned long long maxc = 1ull << 30;

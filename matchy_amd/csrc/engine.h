@@ -16,6 +16,7 @@
 #include "result_layout.h"
 #include "scan_types.h"
 #include "segments.h"
+#include "utf16.h"
 #include "whole_lines.h"
 
 namespace mxy {
@@ -280,6 +281,17 @@ public:
     // stream windows: find, count, chain, symbols, windows, resolve, verdict, tail of the last profiled window
     void gz_stream_timing(float out_ms[GZ_STREAM_PASSES]) const { for (int k = 0; k < GZ_STREAM_PASSES; ++k) out_ms[k] = 0; if (gz_) gz_->stream_timing(out_ms); }
     void gz_window_timing(float out_ms[4]) const { gz_timing(out_ms); out_ms[3] = gz_ ? gz_->tail_ms() : 0; }
+    // UTF-16 inputs (utf16.hip): utf16_transcode queues count, prefix and write on this scanner's own stream and returns, when the text's
+    // length has reached the host, the UTF-8 batch in device memory for the lookup scan the caller then launches on that stream over
+    // (text, len). `src` is host or device memory; byte_order: utf16::ORDER_LE / ORDER_BE. Segments and whole-line mode are not offered:
+    // a pending segment table (dropped then) or whole-line mode fails the call with ParamError, as does an input whose bound reaches 2^31
+    // bytes. utf16_queue_text goes behind the scan's kernels, utf16_finish behind the fetch. Never called, nothing of it is allocated,
+    // launched or copied.
+    GzBatch utf16_transcode(const uint8_t* src, size_t len, uint32_t byte_order);
+    void utf16_queue_text(bool want_text);
+    Utf16Transcode::Result utf16_finish();
+    // milliseconds of count, prefix and write of the last transcoded batch (recorded for every batch, with or without set_profile)
+    void utf16_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (utf16_) utf16_->timing(out_ms); }
     // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
     // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.
     // scan_host reads the setting itself; the other entries of a lookup scan call arm_whole_lines in front of arm_segments, which sets
@@ -428,6 +440,13 @@ private:
     std::unique_ptr<NdjsonRender> render_;     // created by the first arm_render that arms a scan
     std::unique_ptr<GzInflate> gz_;            // created by the first gz_inflate
     uint32_t gz_piece_bytes_ = 0;
+    std::unique_ptr<Utf16Transcode> utf16_;    // created by the first utf16_transcode
+    // the pages of a host input that utf16_transcode pinned for its copy (pins::acquire), until utf16_finish or the next batch
+    struct HostPin {
+        uintptr_t a = 0, b = 0;
+        void release();
+        ~HostPin() { release(); }
+    } utf16_pin_;
     // what gz_inflate and gz_inflate_files share: device, stream, the pass; launch(GzInflate&) plans and queues; then the segment table
     template <class Launch> GzBatch gz_pass(Launch&& launch);   // engine.cpp only
     // whole-line queries: the buffers of the front end (grown with the candidate list, reused between scans), created by the first scan in the mode

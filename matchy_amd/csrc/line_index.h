@@ -36,6 +36,9 @@ uint32_t line_chunks(uint32_t n_tiles);
 // after_count: recorded behind the streaming count kernel when not null (timing).
 hipError_t line_index_build(const uint8_t* data, uint32_t len, uint32_t* counts, uint32_t* chunk_sums, uint32_t* prefix, int n_cu, hipStream_t stream,
                             hipEvent_t after_count);
+// The prefix step of line_index_build alone (k_line_chunk_sum, k_line_scan), for other per-tile figures (utf16.hip): prefix[t] = sum of
+// counts[0 .. t), t = 0 .. n_tiles; n_tiles > 0, chunk_sums: line_chunks(n_tiles) entries.
+hipError_t tile_prefix_build(const uint32_t* counts, uint32_t n_tiles, uint32_t* chunk_sums, uint32_t* prefix, hipStream_t stream);
 // out[i] for record i of `recs` (n records of `stride` = 16 or 8 bytes that begin with the start offset). set != nullptr: the line numbers
 // also go into that set (set_slots: a power of two, at least twice the records of all calls that share it, filled with LINE_SET_EMPTY) and
 // *n_distinct grows by the number of lines that were not in it yet.

@@ -217,9 +217,14 @@ hipError_t line_index_build(const uint8_t* data, uint32_t len, uint32_t* counts,
     const uint32_t grid = std::min<uint32_t>((n_tiles + per_block - 1) / per_block, (uint32_t)std::max(n_cu, 1) * 8u);
     hipLaunchKernelGGL(k_line_count, dim3(grid), dim3(LINE_THREADS), 0, stream, data, len, n_tiles, counts);
     if (after_count) { const hipError_t e = hipEventRecord(after_count, stream); if (e != hipSuccess) return e; }
+    return tile_prefix_build(counts, n_tiles, chunk_sums, prefix, stream);
+}
+
+// the prefix step alone, over any per-tile figures whose total stays below 2^32 (n_tiles > 0)
+hipError_t tile_prefix_build(const uint32_t* counts, uint32_t n_tiles, uint32_t* chunk_sums, uint32_t* prefix, hipStream_t stream) {
     const uint32_t chunks = line_chunks(n_tiles);
-    hipLaunchKernelGGL(k_line_chunk_sum, dim3(chunks), dim3(LINE_THREADS), 0, stream, (const uint32_t*)counts, n_tiles, chunk_sums);
-    hipLaunchKernelGGL(k_line_scan, dim3(chunks), dim3(LINE_THREADS), 0, stream, (const uint32_t*)counts, n_tiles, (const uint32_t*)chunk_sums, prefix);
+    hipLaunchKernelGGL(k_line_chunk_sum, dim3(chunks), dim3(LINE_THREADS), 0, stream, counts, n_tiles, chunk_sums);
+    hipLaunchKernelGGL(k_line_scan, dim3(chunks), dim3(LINE_THREADS), 0, stream, counts, n_tiles, (const uint32_t*)chunk_sums, prefix);
     return hipGetLastError();
 }
 
