@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "domain_prefilter.h"
 #include "hashes.h"
 #include "scan_types.h"
 
@@ -332,36 +333,7 @@ __device__ inline bool d_valid_utf8(const uint8_t* s, uint32_t n) {
     return true;
 }
 
-// Byte-class masks of 8 log bytes at once (SWAR; bit 7 of each byte of the result is the class bit, all other bits 0).
-// Every addend keeps each byte below 0x100, so no carry crosses a byte.
-struct ByteMasks { uint64_t dc, dot, dash, high; };
-// The class arithmetic keeps every byte lane below 0x100, so no carry ever crosses a byte — nor the middle of a 64-bit word: the two
-// halves are computed on their own with 32-bit adds. (Written on uint64_t the compiler emits v_add_co / v_addc_co pairs, a carry chain
-// through VCC that costs twice as much on the vector pipe; it also fuses a 64-bit expression that merely spells the two halves back
-// into that form, hence the separate function.)
-struct ByteMasks32 { uint32_t dc, dot, dash, high; };
-__device__ __forceinline__ ByteMasks32 domain_masks32(uint32_t x) {
-    constexpr uint32_t H = 0x80808080u, L7 = 0x7F7F7F7Fu;
-    const uint32_t t = x & L7, l = t | 0x20202020u;
-    const uint32_t dig = (t + 0x50505050u) & ~(t + 0x46464646u);   // '0'..'9'
-    const uint32_t alp = (l + 0x1F1F1F1Fu) & ~(l + 0x05050505u);   // 'a'..'z' after case folding
-    const uint32_t ndot = (t ^ 0x2E2E2E2Eu) + L7, ndash = (t ^ 0x2D2D2D2Du) + L7;  // bit 7 set iff different
-    ByteMasks32 m;
-    m.high = x & H;
-    m.dot = ~ndot & ~x & H;
-    m.dash = ~ndash & ~x & H;
-    m.dc = (((dig | alp) & ~x) | m.dot | m.dash | m.high) & H;  // DOMAIN_CHAR_LOOKUP (ext:1597-1629)
-    return m;
-}
-__device__ __forceinline__ ByteMasks domain_masks(uint64_t x) {
-    const ByteMasks32 lo = domain_masks32((uint32_t)x), hi = domain_masks32((uint32_t)(x >> 32));
-    ByteMasks m;
-    m.dc = (uint64_t)lo.dc | ((uint64_t)hi.dc << 32);
-    m.dot = (uint64_t)lo.dot | ((uint64_t)hi.dot << 32);
-    m.dash = (uint64_t)lo.dash | ((uint64_t)hi.dash << 32);
-    m.high = (uint64_t)lo.high | ((uint64_t)hi.high << 32);
-    return m;
-}
+// Byte-class masks of 8 log bytes at once (ByteMasks, domain_masks): domain_prefilter.h, shared with the host.
 
 // ------------------------------------------------------------------------------------------------ IPv4
 // IPv4 dotted-quad rules (ext:813-869, 1120-1179) on a 20-byte window held in registers: q = bytes [dot-4, dot+12),

@@ -71,9 +71,13 @@ MXY_HD uint32_t dp_popc(uint32_t x) { return (uint32_t)__builtin_popcount(x); }
 // The domain anchor at j with its context record, decided from the masks where that is possible: last label of <= 7 bytes
 // that alone is a public suffix, name no longer than the look-back. `tldtab`: the exact table of last labels (DevDb::tld_tab;
 // Slot = uint2 or anything with x and y), 1 << TLD_TAB_BITS slots.
+// `pfxtab`: the exact table of the 8-byte windows that start a last label of 8 bytes or more (DevDb::tld_pfx, hashes.h), or
+// null. With it a window of 8 label bytes that starts no such label is no domain — what k_anchor's Bloom filter let through by mistake
+// ends here and not in the general walk; without it every such window is undecided.
 // Returns 0 (no domain), 1 (domain: start / end set, the whole name lies in the context) or 2 (undecided: general path).
-template <class Slot>
-MXY_HD int domain_rules(const Slot* tldtab, uint32_t min_labels, uint32_t j, const uint32_t (&c)[8], uint32_t& start, uint32_t& end) {
+template <class Slot, class PfxSlot>
+MXY_HD int domain_rules(const Slot* tldtab, const PfxSlot* pfxtab, uint32_t min_labels, uint32_t j, const uint32_t (&c)[8], uint32_t& start,
+                        uint32_t& end) {
     const ContextMasks m = context_planes(c);
     // last label = the domain-char bytes from bit 24 up; ll = its length (8: not terminated within the window)
     const uint32_t ndc = ~m.DC >> 24;
@@ -98,7 +102,8 @@ MXY_HD int domain_rules(const Slot* tldtab, uint32_t min_labels, uint32_t j, con
     const bool high = (m.HIGH & (r | label)) != 0;                   // needs the UTF-8 check of the general path
     const int by_run = (whole & (j != 24)) ? 2 : no_name ? 0 : high ? 2 : 1;
     const bool no_label = ((m.DOT & label) != 0) | ((((m.B >> 24) >> ll) & 1u) == 0);   // a later dot owns this run; the stop byte
-    if (ll > 7 || ll < 1) return 2;
+    if (ll < 1) return 2;
+    if (ll > 7) return (pfxtab == nullptr || tld_pfx_has(pfxtab, c[6], c[7])) ? 2 : 0;
     if (no_label) return 0;
     const uint32_t lo = ll >= 4 ? c[6] : c[6] & ((1u << (8 * ll)) - 1u);
     const uint32_t hi = ll > 4 ? c[7] & ((1u << (8 * ll - 32)) - 1u) : 0u;
@@ -113,6 +118,10 @@ MXY_HD int domain_rules(const Slot* tldtab, uint32_t min_labels, uint32_t j, con
     if (!alone) return 2;
     start = j - consumed; end = j + ll;
     return by_run;
+}
+template <class Slot>
+MXY_HD int domain_rules(const Slot* tldtab, uint32_t min_labels, uint32_t j, const uint32_t (&c)[8], uint32_t& start, uint32_t& end) {
+    return domain_rules(tldtab, (const Slot*)nullptr, min_labels, j, c, start, end);
 }
 
 }  // namespace mxy

@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <unordered_set>
 
+#include "domain_prefilter.h"
 #include "hashes.h"
 
 namespace mxy {
@@ -87,10 +88,14 @@ PslHost* load_psl() {
     h->mask = (uint32_t)(cap - 1);
     h->slots.assign(cap, PslSlot{0, 0, 0});
     // two filters in one array: [0, TLD_BLOOM_WORDS) over the last labels of all suffixes, byte-wise hash (the general walk of
-    // k_validate); behind it TLD_BLOOM_WORDS / 2 words for k_anchor's prefilter — labels that fit its 8-byte window, TWO bits per label
-    // from the two-multiply hash (bits 0..13 and 14..27). (Until round 3 the prefilter folded the first filter, which also held its
+    // k_validate); behind it TLD_BLOOM_WORDS / 2 words for k_anchor's prefilter — what its 8-byte window shows of a label: the label if it
+    // fits, its first 8 bytes if it does not (label_window_keep, domain_prefilter.h) —, TWO bits per key from the two-multiply hash (bits
+    // 0..13 and 14..27). (Until round 3 the prefilter folded the first filter, which also held its
     // bits, to half its size: a quarter of all short labels passed, "html" among them.)
+    static_assert(TLD_PREFILTER_BITS == TLD_BLOOM_BITS / 2, "the prefilter's filter is the second half of the array");
     h->bloom.assign(TLD_BLOOM_WORDS + TLD_BLOOM_WORDS / 2, 0);
+    h->tld_pfx.assign(1u << TLD_PFX_BITS, make_uint2(0u, 0u));
+    uint32_t n_pfx = 0;
     for (const std::string& s : h->suffixes) {
         if (s.empty()) continue;
         uint64_t rh = psl_hash_init();
@@ -105,16 +110,9 @@ PslHost* load_psl() {
         size_t ll = s.size() - (dot == std::string::npos ? 0 : dot + 1);
         uint32_t bit = tld_hash(last, ll);
         h->bloom[bit >> 5] |= 1u << (bit & 31);
-        if (ll >= 1 && ll <= 8) {  // second hash used by k_anchor's prefilter (labels that fit its 8-byte window)
-            uint8_t k8[8] = {0};
-            memcpy(k8, last, ll);
-            uint32_t lo8, hi8;
-            memcpy(&lo8, k8, 4); memcpy(&hi8, k8 + 4, 4);
-            const uint32_t h8 = tld_hash8(lo8, hi8);
-            const uint32_t ba = h8 & (TLD_BLOOM_BITS / 2 - 1), bb = (h8 >> 14) & (TLD_BLOOM_BITS / 2 - 1);
-            h->bloom[TLD_BLOOM_WORDS + (ba >> 5)] |= 1u << (ba & 31);
-            h->bloom[TLD_BLOOM_WORDS + (bb >> 5)] |= 1u << (bb & 31);
-        }
+        // k_anchor's prefilter: its filter and, for the labels that fill its 8-byte window, the exact table k_validate_dom asks
+        if (ll >= 1 && prefilter_add_label(&h->bloom[TLD_BLOOM_WORDS], h->tld_pfx.data(), last, ll) && ++n_pfx > TLD_PFX_MAX_KEYS)
+            throw std::runtime_error("matchy_amd: psl.bin has more long last labels than the prefix table holds (TLD_PFX_BITS)");
         h->max_tld_len = std::max<uint32_t>(h->max_tld_len, (uint32_t)ll);
         h->max_suffix_len = std::max<uint32_t>(h->max_suffix_len, (uint32_t)s.size());
         if (ll) h->tld_first[last[0] >> 5] |= 1u << (last[0] & 31);
@@ -475,6 +473,8 @@ void DeviceDb::upload(const DbImage& img, int dev) {
     view.max_suffix_len = psl.max_suffix_len;
     tld_tab.upload(psl.tld_tab);
     view.tld_tab = tld_tab.p;
+    tld_pfx.upload(psl.tld_pfx);
+    view.tld_pfx = tld_pfx.p;
     for (int k = 0; k < 8; ++k) view.tld_first[k] = psl.tld_first[k];
     bytes_uploaded += psl.slots.size() * sizeof(PslSlot) + psl.pool.size() + psl.bloom.size() * 4;
 }

@@ -49,6 +49,7 @@ struct PslHost {
     std::vector<uint8_t> pool;
     std::vector<uint32_t> bloom;
     std::vector<uint2> tld_tab;   // exact table of the last labels of <= 7 bytes (see DevDb::tld_tab)
+    std::vector<uint2> tld_pfx;   // exact table of the first 8 bytes of the last labels of >= 8 bytes (see DevDb::tld_pfx)
     uint32_t mask = 0, max_tld_len = 0, max_suffix_len = 0;
     uint32_t tld_first[8] = {0};
     static const PslHost& get();  // throws std::runtime_error if the container cannot be found
@@ -60,7 +61,7 @@ struct DeviceDb {
     DevDb view{};
     DevBuf<uint2> ip_nodes, ip_l1, ip_l24, ip_leaf;
     DevBuf<uint32_t> ip_bm24, lit_bm, sfx_bm;
-    DevBuf<uint2> tld_tab;
+    DevBuf<uint2> tld_tab, tld_pfx;
     DevBuf<uint32_t> dfa, dfa_node;
     DevBuf<uint8_t> dfa_cls;
     DevBuf<LitSlot> lit_slots;

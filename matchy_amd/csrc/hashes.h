@@ -183,6 +183,37 @@ MXY_HD uint64_t fx_u32(uint32_t v) { return rotl64((uint64_t)v * 0xf1357aea2e62a
 constexpr uint32_t TLD_TAB_BITS = 11;
 MXY_HD uint32_t tld_tab_slot(uint32_t lo, uint32_t hi24) { return ((lo ^ (hi24 * 0x9E3779B1u)) * 0x85EBCA6Bu) >> (32 - TLD_TAB_BITS); }
 
+// Exact table of the 8-byte windows that start a last label of 8 bytes or more (DevDb::tld_pfx; k_anchor's prefilter decides such labels
+// by these 8 bytes, domain_prefilter.h): open addressing, 1 << TLD_PFX_BITS slots of {bytes 0..3, bytes 4..7}; {0, 0} is an empty slot
+// (label bytes are never 0). A few hundred keys in the shipped list (a third full); load_psl refuses a list that would fill more than
+// three quarters of it.
+constexpr uint32_t TLD_PFX_BITS = 10;
+constexpr uint32_t TLD_PFX_MAX_KEYS = (3u << TLD_PFX_BITS) / 4;
+MXY_HD uint32_t tld_pfx_slot(uint32_t lo, uint32_t hi) { return ((lo ^ (hi * 0x9E3779B1u)) * 0x85EBCA6Bu) >> (32 - TLD_PFX_BITS); }
+
+template <class Slot>
+MXY_HD bool tld_pfx_has(const Slot* tab, uint32_t lo, uint32_t hi) {
+    uint32_t slot = tld_pfx_slot(lo, hi);
+    for (;;) {
+        const Slot t = tab[slot];
+        if (t.x == lo && t.y == hi) return true;
+        if ((t.x | t.y) == 0) return false;
+        slot = (slot + 1) & ((1u << TLD_PFX_BITS) - 1);
+    }
+}
+
+// host: enter a window; returns false if it was there already
+template <class Slot>
+inline bool tld_pfx_insert(Slot* tab, uint32_t lo, uint32_t hi) {
+    uint32_t slot = tld_pfx_slot(lo, hi);
+    for (;;) {
+        Slot& t = tab[slot];
+        if (t.x == lo && t.y == hi) return false;
+        if ((t.x | t.y) == 0) { t.x = lo; t.y = hi; return true; }
+        slot = (slot + 1) & ((1u << TLD_PFX_BITS) - 1);
+    }
+}
+
 // Bloom-filter bit (before masking) of a last label of <= 8 bytes packed little-endian in lo / hi (zero padded); the
 // streaming kernel's prefilter uses this two-multiply hash, longer labels use the byte-wise one (tld_hash_step).
 MXY_HD uint32_t tld_hash8(uint32_t lo, uint32_t hi) {

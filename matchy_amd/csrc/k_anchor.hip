@@ -83,7 +83,7 @@ __device__ __forceinline__ uint32_t anchor_pos(uint32_t e) {
 constexpr uint32_t CAND_STAGE = 16, RARE_STAGE = 8;
 typedef StagedChunkWriter<Candidate, CAND_STAGE> CandWriter;
 typedef BufferedWriter<uint2, RARE_STAGE> RareWriter;
-static_assert(TLD_BLOOM_BITS / 2 == 1u << 14, "the prefilter takes bits 0..13 and 14..27 of the label hash");
+static_assert(TLD_BLOOM_BITS / 2 == TLD_PREFILTER_BITS, "the prefilter takes bits 0..13 and 14..27 of the label hash");
 constexpr uint32_t BLOOM_FOLD_WORDS = TLD_BLOOM_WORDS / 2;   // words of the prefilter's own Bloom filter (behind the general one in DevDb::tld_bloom)
 
 struct WaveCtx {
@@ -425,8 +425,9 @@ __device__ __forceinline__ void drain_v4(uint32_t* ring, uint32_t& head, uint32_
 
 // Prefilter up to 64 domain anchors (first byte of the last label), one per lane; survivors go to the domain list.
 // Mirrors the first steps of val_domain (validate_kernels.hip): a '.' inside the label means a later dot owns the run, the
-// run must end at a boundary, and the label must be the last label of some public suffix. Undecidable cases (label
-// longer than 8 bytes, bytes not resident) are kept.
+// run must end at a boundary, and the label must be the last label of some public suffix — a label that fills the 8-byte window
+// must start like one (label_window_keep, domain_prefilter.h: the one definition of the rule). Anchors whose bytes are not
+// resident are kept.
 __device__ __forceinline__ void drain_dom(uint32_t* ring, uint32_t& head, uint32_t& tail, uint32_t n, bool final, const WaveCtx& cx,
                                           DomWriter& dw) {
     const uint32_t lane = lane_id();
@@ -456,38 +457,10 @@ __device__ __forceinline__ void drain_dom(uint32_t* ring, uint32_t& head, uint32
     const bool have_ctx = go && j >= cx.res_lo + 24 && j + 8 <= cx.res_hi;
     uint32_t ctx[8];
     raw_read<8>(cx.raw32, j - 24, ctx);   // log[j-24, j+8): the last label starts at byte 24
-    bool keep = go;   // anchors that cannot be decided here (bytes not resident, long last label) are kept
-    {
-        // the label's 8-byte window as SWAR masks (no per-byte loop)
-        constexpr uint64_t H = 0x8080808080808080ull;
-        const uint64_t w64 = (uint64_t)ctx[6] | ((uint64_t)ctx[7] << 32);
-        const ByteMasks mw = domain_masks(w64);
-        const uint64_t ndc = ~mw.dc & H;
-        if (ndc) {   // the label ends inside the window: ll = its length (>= 1: byte j can start a TLD)
-            const uint32_t ll = (uint32_t)(__ffsll((long long)ndc) - 1) >> 3;
-            const uint64_t below = (1ull << (8 * ll)) - 1ull;
-            const uint32_t stop = (uint32_t)(w64 >> (8 * ll)) & 0xFF;
-            const uint32_t h8 = tld_hash8((uint32_t)(w64 & below), (uint32_t)((w64 & below) >> 32));
-            const uint32_t bit = h8 & (TLD_BLOOM_BITS / 2 - 1), bit2 = (h8 >> 14) & (TLD_BLOOM_BITS / 2 - 1);
-            // a '.' inside the label: a later dot owns the run; the run must end at a boundary; the label must be
-            // some public suffix's last label (two bits of the prefilter's Bloom filter)
-            const bool k = (mw.dot & below) == 0 && d_is_boundary(stop) && ((cx.bloom[bit >> 5] >> (bit & 31)) & (cx.bloom[bit2 >> 5] >> (bit2 & 31)) & 1);
-            if (have_ctx) keep = k;
-        } else if (mw.dot) {
-            if (have_ctx) keep = false;         // 8 domain chars with a dot among them: a later dot owns the run
-        } else if (have_ctx && j + 24 <= cx.res_hi) {
-            // a label of 8+ bytes: usually not the last one ("www.examplesite.com" at 'e'). Look 16 bytes further: a
-            // dot before the first non-domain byte settles it; otherwise it stays undecided (long last label)
-            uint32_t more[4];
-            raw_read<4>(cx.raw32, j + 8, more);
-            const ByteMasks ma = domain_masks((uint64_t)more[0] | ((uint64_t)more[1] << 32));
-            const ByteMasks mb = domain_masks((uint64_t)more[2] | ((uint64_t)more[3] << 32));
-            const uint64_t na = ~ma.dc & H, nb = ~mb.dc & H;
-            const uint64_t below_a = na ? ((1ull << ((uint32_t)(__ffsll((long long)na) - 1) & ~7u)) - 1ull) : ~0ull;
-            const uint64_t below_b = na ? 0ull : (nb ? ((1ull << ((uint32_t)(__ffsll((long long)nb) - 1) & ~7u)) - 1ull) : ~0ull);
-            keep = ((ma.dot & below_a) | (mb.dot & below_b)) == 0;
-        }
-    }
+    // anchors whose bytes are not resident are kept; every other one is decided from its label window, a label that fills it included
+    // (evaluated by every lane: a filter address is a filter address)
+    const bool k = label_window_keep(ctx[6], ctx[7], cx.bloom, [](uint32_t b) { return d_is_boundary(b); });
+    const bool keep = have_ctx ? k : go;
     const uint32_t slot = dw.reserve(keep, p.dom_list, p.dom_cap, [] { return &cold_tok()->counters->n_dom; },
                                      [] { const uint32_t st = cold_tok()->dom_static; return st ? (blockIdx.x * 4u + (threadIdx.x >> 6)) * st : 0xFFFFFFFFu; },
                                      [] { return cold_tok()->dom_chunk; });

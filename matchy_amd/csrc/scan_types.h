@@ -126,6 +126,9 @@ struct DevDb {
     uint32_t lc_n_ign;
     const uint2* lc_cased;        // Cased ranges
     uint32_t lc_n_cased;
+    // exact open-addressing table (1 << TLD_PFX_BITS slots, hashes.h) of the first 8 bytes of the last labels of >= 8 bytes: what
+    // k_anchor's prefilter kept of a label that fills its window is checked against it in k_validate_dom (domain_rules).
+    const uint2* tld_pfx;
 };
 
 constexpr uint32_t DFA_LDS_ENTRIES = 8192;      // 32 KiB of transition rows per workgroup of k_lookup

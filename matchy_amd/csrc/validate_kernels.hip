@@ -863,7 +863,8 @@ __device__ bool val_eth(const uint8_t* a, uint8_t* lower) {  // ext:1328-1361, 1
 // k_validate_dom — stage A2a: one lane per domain anchor with its context record (planes written by k_anchor, read
 // coalesced). Lean on purpose (no general walk, no global log reads): it is latency-bound, so its speed is the number of
 // resident waves. Anchors it cannot decide (no context, last label > 7 bytes or not a suffix on its own, name longer than
-// the context, non-ASCII) go to the rare list as RARE_DOM for k_validate.
+// the context, non-ASCII) go to the rare list as RARE_DOM for k_validate; a window of 8 label bytes that starts no last label of
+// the list (DevDb::tld_pfx, read from global memory: LDS is what keeps this kernel's workgroups resident) is refused here.
 // AC (p.filter_ac): databases with globs — a name is listed if its hash is in the literal bitmap or its text reaches an output
 // state of the glob automaton (walked here from the context bytes, shallow rows in LDS), so k_lookup does not have to fetch
 // the text of every valid name from the log again.
@@ -956,7 +957,7 @@ __global__ __launch_bounds__(256) void k_validate_dom(TokParams p, DevDb db) {
         if (cur.j != 0xFFFFFFFFu) {
             uint32_t s = 0, e = 0;
             int r = 2;
-            if (!(cur.j & 0x80000000u)) r = domain_rules(tldtab, p.min_labels, cur.j, cur.c, s, e);
+            if (!(cur.j & 0x80000000u)) r = domain_rules(tldtab, db.tld_pfx, p.min_labels, cur.j, cur.c, s, e);
             slow = r == 2;
             if (r == 1) {
                 pend_start = s; pend_lt = (e - s) | ((uint32_t)IT_DOMAIN << 24); pend = true;
