@@ -649,6 +649,39 @@ void matchy_amd_extractor_set_unique(matchy_extractor_t *extractor, bool enabled
 bool matchy_amd_extractor_unique(const matchy_extractor_t *extractor);
 void matchy_amd_extractor_reset_unique(matchy_extractor_t *extractor);
 uint64_t matchy_amd_extractor_unique_count(const matchy_extractor_t *extractor);
+/* Candidates as text (`matchy extract --render-on-gpu`). The candidates of `data` are put into the order of `matchy extract` — by line,
+ * then domain, IPv4, e-mail, IPv6, hashes, Bitcoin, Ethereum, Monero, then by start — and written as that command's output on the
+ * GPU: one line per candidate with the raw bytes data[start, end), for addresses too (not the canonical value),
+ *   json  {"type":"<name>","value":"<bytes>"}   with \ -> \\ and " -> \" and no other escape
+ *   csv   <name>,"<bytes>"                      with " doubled (the header line is the caller's)
+ *   text  <bytes>
+ * <name> being matchy_item_type_name in lower case. No candidate record crosses the bus. With matchy_amd_extractor_set_unique the block
+ * holds the first occurrences only: exactly the candidates matchy_extractor_extract_chunk would have returned. The block is pinned
+ * host memory, BORROWED until the handle's next call; inputs above the piece size of a scan are cut at newlines, their blocks handed
+ * out end to end and their counts summed. A status other than _OK hands out nothing (text NULL, counts zero); the call still returns
+ * MATCHY_SUCCESS, and a batch that was _REFUSED has not touched the set of distinct texts: extract_chunk can take it. MATCHY_ERROR_INVALID_PARAM for a NULL handle or out, NULL data
+ * with len > 0, or an unknown format. Like extract_chunk this serialises on the handle. */
+#define MATCHY_AMD_EXTRACT_FORMAT_JSON 0
+#define MATCHY_AMD_EXTRACT_FORMAT_CSV 1
+#define MATCHY_AMD_EXTRACT_FORMAT_TEXT 2
+#define MATCHY_AMD_EXTRACT_TEXT_OK 0
+#define MATCHY_AMD_EXTRACT_TEXT_REFUSED 1    /* a launch of more than 2^30 bytes or 2^32 list entries: the order key does not hold it */
+#define MATCHY_AMD_EXTRACT_TEXT_MISCOUNT 2   /* the candidate lists did not hold what the scan counted: the block is not valid */
+typedef struct matchy_amd_extract_text_t {
+  const uint8_t *text;           /* NULL when there is none */
+  uint64_t text_len;
+  uint64_t n_records;
+  uint64_t by_type[12];          /* records per MATCHY_ITEM_TYPE_* */
+  uint32_t status;               /* MATCHY_AMD_EXTRACT_TEXT_* */
+  uint32_t reserved;
+} matchy_amd_extract_text_t;
+int32_t matchy_amd_extractor_extract_rendered(const matchy_extractor_t *extractor, const uint8_t *data, uintptr_t len,
+                                              uint32_t format /* 0 json, 1 csv, 2 text */, matchy_amd_extract_text_t *out);
+/* Of the last _extract_rendered (its last piece): device milliseconds of keys + sort, of the measure step, of the write step, and of the
+ * block's device-to-host copy. */
+void matchy_amd_extractor_get_render_timing(const matchy_extractor_t *extractor, float out_ms[4]);
+/* Allocations of the pass's buffers since the handle was made: a call like the one before adds none. */
+uint64_t matchy_amd_extractor_render_allocations(const matchy_extractor_t *extractor);
 const char *matchy_amd_last_error(void);
 /* Diagnostics: states of the flattened Aho-Corasick automaton on the handle's default device; 0 = the database has no glob
  * section or its automaton is walked node by node (flattened table above MATCHY_AMD_DFA_MAX_MB, default 8192), -1 = error. */

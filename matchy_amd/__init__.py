@@ -25,6 +25,7 @@ ITEM_TYPE_NAMES = ["Domain", "Email", "IPv4", "IPv6", "MD5", "SHA1", "SHA256", "
 EXTRACT_DOMAINS, EXTRACT_EMAILS, EXTRACT_IPV4, EXTRACT_IPV6 = 1, 2, 4, 8
 EXTRACT_HASHES, EXTRACT_BITCOIN, EXTRACT_ETHEREUM, EXTRACT_MONERO = 16, 32, 64, 128
 EXTRACT_ALL = 255
+EXTRACT_FORMATS = {"json": 0, "csv": 1, "text": 2}   # MATCHY_AMD_EXTRACT_FORMAT_*
 
 # every symbol include/matchy_amd.h declares
 EXPORTED_SYMBOLS = [
@@ -52,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_set_line_context", "matchy_scanner_line_context", "matchy_scan_result_lines", "matchy_multi_scanner_set_line_context",
     "matchy_scan_result_to_ndjson_lines", "matchy_scanner_get_line_timing",
     "matchy_amd_extractor_set_unique", "matchy_amd_extractor_unique", "matchy_amd_extractor_reset_unique", "matchy_amd_extractor_unique_count",
+    "matchy_amd_extractor_extract_rendered", "matchy_amd_extractor_get_render_timing", "matchy_amd_extractor_render_allocations",
     "matchy_scanner_set_tally", "matchy_scanner_tally", "matchy_scanner_reset_tally", "matchy_scanner_tally_top",
     "matchy_multi_scanner_set_tally", "matchy_multi_scanner_tally_top", "matchy_multi_scanner_reset_tally", "matchy_tally_free",
     "matchy_scanner_set_segments", "matchy_scan_result_segments", "matchy_scan_result_to_ndjson_segments",
@@ -133,6 +135,12 @@ class _Match(C.Structure):
 
 class _Matches(C.Structure):
     _fields_ = [("items", C.POINTER(_Match)), ("count", C.c_size_t), ("_internal", C.c_void_p)]
+
+
+class _ExtractText(C.Structure):
+    # matchy_amd_extract_text_t
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_uint64), ("n_records", C.c_uint64), ("by_type", C.c_uint64 * 12),
+                ("status", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class _ScanHit(C.Structure):
@@ -337,6 +345,9 @@ def lib():
         "matchy_amd_extractor_unique": (C.c_bool, [vp]),
         "matchy_amd_extractor_reset_unique": (None, [vp]),
         "matchy_amd_extractor_unique_count": (C.c_uint64, [vp]),
+        "matchy_amd_extractor_extract_rendered": (C.c_int32, [vp, cp, C.c_size_t, C.c_uint32, C.POINTER(_ExtractText)]),
+        "matchy_amd_extractor_get_render_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_amd_extractor_render_allocations": (C.c_uint64, [vp]),
         "matchy_item_type_name": (cp, [C.c_uint8]),
         "matchy_scanner_create": (vp, [vp, C.c_uint32, C.c_int32]),
         "matchy_scanner_free": (None, [vp]),
@@ -683,6 +694,31 @@ class Extractor:
                     for i in range(m.count)]
         finally:
             L.matchy_matches_free(C.byref(m))
+
+    def extract_rendered(self, data: bytes, fmt="json"):
+        """The output of `matchy extract` for the candidates of `data`, ordered and written on the GPU (matchy_amd_extractor_extract_rendered):
+        (text, counts) with counts a dict item type name -> records. fmt: "json", "csv" (without the header line) or "text"."""
+        L = lib()
+        out = _ExtractText()
+        rc = L.matchy_amd_extractor_extract_rendered(self._h, bytes(data), len(data), EXTRACT_FORMATS[fmt] if isinstance(fmt, str) else fmt, C.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"matchy_amd_extractor_extract_rendered failed: rc={rc} {last_error()}")
+        if out.status != 0:
+            raise RuntimeError(f"matchy_amd_extractor_extract_rendered: status {out.status}")
+        text = C.string_at(out.text, out.text_len) if out.text_len else b""
+        counts = {ITEM_TYPE_NAMES[t]: int(out.by_type[t]) for t in range(12) if out.by_type[t]}
+        assert sum(counts.values()) == out.n_records
+        return text, counts
+
+    def render_timing(self):
+        """device milliseconds of keys + sort, measure, write and the block's copy of the last extract_rendered"""
+        ms = (C.c_float * 4)()
+        lib().matchy_amd_extractor_get_render_timing(self._h, ms)
+        return tuple(ms)
+
+    @property
+    def render_allocations(self):
+        return int(lib().matchy_amd_extractor_render_allocations(self._h))
 
     def close(self):
         if self._h:

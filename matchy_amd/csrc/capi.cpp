@@ -966,6 +966,41 @@ int32_t matchy_extractor_extract_chunk(const matchy_extractor_t* ec, const uint8
     } catch (const HipError& ex) { set_error(ex.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& ex) { set_error(ex.what()); return MATCHY_ERROR_IO; }
 }
+// candidates as text (Scanner::set_extract_text, extract_render.hip): the block is the scanner's, under the handle's lock
+int32_t matchy_amd_extractor_extract_rendered(const matchy_extractor_t* ec, const uint8_t* data, uintptr_t len, uint32_t format, matchy_amd_extract_text_t* out) {
+    if (!ec || !out || (!data && len) || format > MATCHY_AMD_EXTRACT_FORMAT_TEXT) return MATCHY_ERROR_INVALID_PARAM;
+    memset(out, 0, sizeof(*out));
+    ExtractorH* e = const_cast<ExtractorH*>(reinterpret_cast<const ExtractorH*>(ec));
+    try {
+        std::lock_guard<std::mutex> lk(e->mu);
+        struct OffAtExit { Scanner& s; ~OffAtExit() { s.set_extract_text(-1); } } off{*e->scanner};   // extract_chunk stays what it is
+        e->scanner->set_extract_text((int)format);
+        if (getenv("MATCHY_AMD_TRACE")) e->scanner->set_profile(true);   // the trace line names the extraction kernels' time beside the pass's
+        ScanOutput so;
+        e->scanner->scan_host(data, len, false, true, so, nullptr, nullptr, nullptr, nullptr);
+        const ExtractTextView& v = so.extract_text;
+        out->status = v.status;
+        if (v.status != XR_OK) return MATCHY_SUCCESS;
+        out->text = v.text; out->text_len = v.len; out->n_records = v.n_records;
+        for (int t = 0; t < IT_COUNT; ++t) out->by_type[t] = v.by_type[t];
+        return MATCHY_SUCCESS;
+    } catch (const HipError& ex) { set_error(ex.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& ex) { set_error(ex.what()); return MATCHY_ERROR_IO; }
+}
+void matchy_amd_extractor_get_render_timing(const matchy_extractor_t* ec, float out[4]) {
+    if (!out) return;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    if (!ec) return;
+    ExtractorH* e = const_cast<ExtractorH*>(reinterpret_cast<const ExtractorH*>(ec));
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->scanner->extract_text_timing(out);
+}
+uint64_t matchy_amd_extractor_render_allocations(const matchy_extractor_t* ec) {
+    if (!ec) return 0;
+    ExtractorH* e = const_cast<ExtractorH*>(reinterpret_cast<const ExtractorH*>(ec));
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->scanner->extract_text_allocations();
+}
 void matchy_matches_free(matchy_matches_t* m) {
     if (!m) return;
     delete reinterpret_cast<MatchesInternal*>(m->_internal);

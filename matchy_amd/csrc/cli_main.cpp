@@ -43,6 +43,8 @@ int usage() {
             "                                  not with --follow, --pack-inputs, --gz-on-gpu, --whole-lines)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
+            "               [--render-on-gpu]   (the items of a batch are put into line order and written as json / csv / text on the GPU: one block per\n"
+            "                                    batch crosses the bus in place of the item records; same output; not with --show-candidates)\n"
             "  matchy inspect <DATABASE> [-j] [-v]\n"
             "  matchy validate <DATABASE> [-l standard|strict] [-j]\n");
     return 2;
@@ -163,17 +165,36 @@ inline int line_rank(uint8_t t) {
         default: return 4;   // the hash types
     }
 }
-bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, bool show_cand, ExtractStats& st) {
+bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, bool show_cand, bool on_gpu, ExtractStats& st) {
     if (!len) return true;
-    // line table: [start, end) of every trimmed, non-empty line
+    // line table: [start, end) of every trimmed, non-empty line (--render-on-gpu: the GPU counts the newlines itself, no table)
     std::vector<std::pair<size_t, size_t>> lines;
     for (size_t p = 0; p < len;) {
         const uint8_t* nlp = (const uint8_t*)memchr(data + p, '\n', len - p);
         size_t e = nlp ? (size_t)(nlp - data) : len, a = p, b = e;
         while (a < b && is_ws(data[a])) { if (data[a] == 0x0C) data[a] = ' '; ++a; }
         while (b > a && is_ws(data[b - 1])) { if (data[b - 1] == 0x0C) data[b - 1] = ' '; --b; }
-        if (b > a) { lines.push_back({a, b}); st.lines++; st.bytes += b - a; }
+        if (b > a) { if (!on_gpu) lines.push_back({a, b}); st.lines++; st.bytes += b - a; }
         p = e + 1;
+    }
+    if (on_gpu) {
+        matchy_amd_extract_text_t t;
+        if (matchy_amd_extractor_extract_rendered(ex, data, len, (uint32_t)fmt, &t) != MATCHY_SUCCESS) {
+            fprintf(stderr, "[ERROR] extraction failed: %s\n", matchy_amd_last_error());
+            return false;
+        }
+        if (t.status == MATCHY_AMD_EXTRACT_TEXT_OK) {
+            if (t.text_len) fwrite(t.text, 1, t.text_len, stdout);
+            st.found += t.n_records;
+            st.v4 += t.by_type[MATCHY_ITEM_TYPE_IPV4]; st.v6 += t.by_type[MATCHY_ITEM_TYPE_IPV6];
+            st.dom += t.by_type[MATCHY_ITEM_TYPE_DOMAIN]; st.mail += t.by_type[MATCHY_ITEM_TYPE_EMAIL];
+            return true;
+        }
+        // the GPU refused the batch: the host path prints it; its lines are counted already
+        ExtractStats host;
+        if (!extract_batch(ex, data, len, fmt, false, false, host)) return false;
+        st.found += host.found; st.v4 += host.v4; st.v6 += host.v6; st.dom += host.dom; st.mail += host.mail;
+        return true;
     }
     matchy_matches_t m;
     memset(&m, 0, sizeof(m));
@@ -231,7 +252,7 @@ bool extract_batch(matchy_extractor_t* ex, uint8_t* data, size_t len, int fmt, b
 int cmd_extract(int argc, char** argv) {
     std::vector<std::string> inputs;
     std::string format = "json", types;
-    bool have_types = false, unique = false, stats = false, show_cand = false;
+    bool have_types = false, unique = false, stats = false, show_cand = false, on_gpu = false;
     uint32_t min_labels = 2;
     size_t batch_bytes = (size_t)256 << 20;
     for (int i = 0; i < argc; ++i) {
@@ -253,10 +274,12 @@ int cmd_extract(int argc, char** argv) {
         else if (a == "-u" || a == "--unique") unique = true;
         else if (a == "-s" || a == "--stats") stats = true;
         else if (a == "--show-candidates") show_cand = true;
+        else if (a == "--render-on-gpu") on_gpu = true;
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); return 2; }
         else inputs.push_back(a);
     }
     if (inputs.empty()) return usage();
+    if (on_gpu && show_cand) { fprintf(stderr, "Error: --show-candidates prints every item on the host and cannot be combined with --render-on-gpu\n"); return 1; }
     for (char& ch : format) ch = (char)tolower((unsigned char)ch);
     const int fmt = format == "json" ? 0 : format == "csv" ? 1 : format == "text" ? 2 : -1;
     if (fmt < 0) { fprintf(stderr, "Error: Invalid format '%s', expected: json, csv, or text\n", format.c_str()); return 1; }
@@ -305,7 +328,7 @@ int cmd_extract(int argc, char** argv) {
         int fd = path == "-" ? 0 : open(path.c_str(), O_RDONLY);
         if (fd < 0) { fprintf(stderr, "Error: Failed to open file: %s\n", path.c_str()); ok = false; break; }
         const StreamEnd e = read_batches([&](void* p, size_t n) { return read(fd, p, n); }, batch_bytes, [&](Bytes&& data, size_t len, uint64_t) {
-            return extract_batch(ex, data.get(), len, fmt, show_cand, st);
+            return extract_batch(ex, data.get(), len, fmt, show_cand, on_gpu, st);
         });
         if (e == StreamEnd::FAILED) fprintf(stderr, "Error: read failed on %s: %s\n", path.c_str(), strerror(errno));
         ok = e == StreamEnd::DONE;

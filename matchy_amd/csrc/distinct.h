@@ -53,6 +53,11 @@ public:
     // copies exactly them to `out`. Synchronises `stream`.
     void filter(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
                 std::vector<Candidate>& out, hipStream_t stream);
+    // The same, with the survivors left in device memory: returns their number; survivors() holds them (no padding entries among them)
+    // until the next filter call.
+    uint32_t filter_device(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
+                           hipStream_t stream);
+    const Candidate* survivors() const { return out_dev_.p; }
     void reset();                                  // empties the set, keeps the allocations
     uint64_t count() const { return table_.count(); }   // distinct texts since creation or the last reset
     // HIP-event milliseconds of the dedup kernels of the last filter() (growth included), when set_profile(true)
@@ -60,6 +65,8 @@ public:
     float last_ms() const { return last_ms_; }
 
 private:
+    uint32_t run(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
+                 hipStream_t stream, bool& open);
     TextTable table_;
     DevBuf<Candidate> out_dev_;
     bool profile_ = false;

@@ -110,13 +110,15 @@ DistinctSet::DistinctSet() : table_(DISTINCT_OWNER) {}
 
 void DistinctSet::reset() { table_.reset(); }
 
-void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
-                         std::vector<Candidate>& out, hipStream_t stream) {
-    out.clear();
+// claim + publish of one batch: the survivors in out_dev_, their number returned. `false` in `open`: the batch had nothing to filter and
+// the table was not opened; otherwise the caller closes the table once it has what it wants from out_dev_.
+uint32_t DistinctSet::run(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
+                          hipStream_t stream, bool& open) {
+    open = false;
     last_ms_ = 0;
     table_.check();
     const size_t n = (size_t)n_a + n_b;
-    if (n == 0 || cand_true == 0) return;
+    if (n == 0 || cand_true == 0) return 0;
     if (len > DISTINCT_MAX_LEN) throw HipError{"distinct set: batch longer than 1 GiB"};
     if (n >= DISTINCT_MAX_INDEX) throw HipError{"distinct set: more than 2^29 candidate list entries in one batch"};
     table_.start_batch(stream);
@@ -141,11 +143,31 @@ void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list
     }, p.t, stream);
     const uint32_t n_out = table_.host_counters().n_new;
     if (n_out > p.out_cap) throw HipError{"distinct set: more survivors than candidates"};
+    open = true;
+    return n_out;
+}
+
+void DistinctSet::filter(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
+                         std::vector<Candidate>& out, hipStream_t stream) {
+    out.clear();
+    bool open;
+    const uint32_t n_out = run(log, len, list_a, n_a, list_b, n_b, cand_true, stream, open);
+    if (!open) return;
     out.resize(n_out);
     if (n_out) MXY_HIP(hipMemcpyAsync(out.data(), out_dev_.p, (size_t)n_out * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
     MXY_HIP(hipStreamSynchronize(stream));
     if (profile_) MXY_HIP(hipEventElapsedTime(&last_ms_, ev_[0], ev_[1]));
     table_.close();
+}
+
+uint32_t DistinctSet::filter_device(const uint8_t* log, uint32_t len, const Candidate* list_a, uint32_t n_a, const Candidate* list_b, uint32_t n_b, uint32_t cand_true,
+                                    hipStream_t stream) {
+    bool open;
+    const uint32_t n_out = run(log, len, list_a, n_a, list_b, n_b, cand_true, stream, open);
+    if (!open) return 0;
+    if (profile_) MXY_HIP(hipEventElapsedTime(&last_ms_, ev_[0], ev_[1]));   // the publish step has waited for the stream
+    table_.close();
+    return n_out;
 }
 
 }  // namespace mxy

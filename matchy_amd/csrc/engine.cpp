@@ -1,6 +1,7 @@
 #include "engine.h"
 #include "batch_reader.h"
 #include "distinct.h"
+#include "extract_render_core.h"
 #include "render_core.h"
 #include "tally.h"
 #include "unicode_lower.h"
@@ -1378,7 +1379,8 @@ const FinalHit* Scanner::queue_record_copies(ScanOutput& out, bool want_cands, H
         }
         out.n_c4 = c.n_c4;
     }
-    if (want_cands && !unique_ && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
+    const bool as_text = want_cands && extract_text_format_ >= 0 && !last_.lookup;   // the lists are rendered where they lie (queue_post_passes)
+    if (want_cands && !unique_ && !as_text && c.n_cand + c.n_cand_a) {   // k_anchor's IPv4 list, then the validation kernels' list
         out.cands.resize((size_t)c.n_cand_a + c.n_cand);
         if (c.n_cand_a) MXY_HIP(hipMemcpyAsync(out.cands.data(), w0.cands_a.p, (size_t)c.n_cand_a * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
         if (c.n_cand) MXY_HIP(hipMemcpyAsync(out.cands.data() + c.n_cand_a, w0.cands.p, (size_t)c.n_cand * sizeof(Candidate), hipMemcpyDeviceToHost, stream));
@@ -1440,8 +1442,23 @@ void Scanner::queue_post_passes(ScanOutput& out, const FinalHit* dev_recs, bool 
         render_->resolve(in, to_host, n_cu_, profile_, stream);
         out.render.armed = true;
     }
-    // distinct texts: both lists go through the handle's set where they lie, and only the first occurrences come back
-    if (want_cands && unique_) {
+    // candidates as text: both lists, or the first occurrences the handle's set leaves on the device, are ordered and written where they lie
+    out.extract_text = ExtractTextView{};
+    if (want_cands && extract_text_format_ >= 0 && !last_.lookup) {
+        if (!extract_render_) extract_render_ = std::make_unique<ExtractRender>();
+        XrInput in;
+        in.data = last_.ptr; in.len = last_.len; in.format = (uint32_t)extract_text_format_;
+        in.list_a = w0.cands_a.p; in.n_a = c.n_cand_a; in.list_b = w0.cands.p; in.n_b = c.n_cand; in.n_real = c.cand_true;
+        if (last_.len > xrender::MAX_LEN || (uint64_t)c.n_cand_a + c.n_cand > 0xFFFFFFFFull) extract_render_->refuse();   // in front of the set: it stays as it is
+        else {
+            if (unique_) {
+                in.n_real = distinct_->filter_device(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, stream);
+                in.list_a = distinct_->survivors(); in.n_a = in.n_real; in.list_b = nullptr; in.n_b = 0;
+            }
+            extract_render_->resolve(in, n_cu_, stream);
+        }
+        out.extract_text.armed = true;
+    } else if (want_cands && unique_) {
         distinct_->filter(last_.ptr, last_.len, w0.cands_a.p, c.n_cand_a, w0.cands.p, c.n_cand, c.cand_true, out.cands, stream);
         if (trace) fprintf(stderr, "[matchy_amd] distinct: %zu of %u candidates are new, dedup %.3f ms behind %.3f ms of extraction kernels\n", out.cands.size(), c.cand_true,
                            distinct_->last_ms(), timing_.total_ms);
@@ -1489,6 +1506,17 @@ void Scanner::finish_fetch(ScanOutput& out, bool want_cands, HitMode hit_mode, h
     }
     for (auto& t : out.by_type) t = 0;
     if (want_cands) for (const Candidate& cd : out.cands) { uint32_t ty = cd.len_type >> 24; if (ty < IT_COUNT) out.by_type[ty]++; }
+    if (out.extract_text.armed) {
+        out.extract_text = extract_render_->finish();   // a second wait: the demand of the block is known only now
+        for (int t = 0; t < IT_COUNT; ++t) out.by_type[t] = out.extract_text.by_type[t];
+        if (getenv("MATCHY_AMD_TRACE")) {
+            float ms[4];
+            extract_render_->timing(ms);
+            fprintf(stderr, "[matchy_amd] extract text: %llu records, block of %llu bytes, status %u; keys + sort %.3f ms, measure %.3f ms, write %.3f ms, copy %.3f ms, behind %.3f ms of extraction kernels\n",
+                    (unsigned long long)out.extract_text.n_records, (unsigned long long)out.extract_text.len, out.extract_text.status, ms[0], ms[1], ms[2], ms[3],
+                    timing_.total_ms);
+        }
+    }
 }
 
 void Scanner::fetch(ScanOutput& out, bool want_cands, hipStream_t stream, HitMode hit_mode, bool sorted) {
@@ -1725,6 +1753,13 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         out.render.armed = true;
         out.render_own.clear();
     }
+    // candidates as text: the blocks of the pieces go end to end into one pinned block, the counts add up
+    const bool as_text = want_cands && extract_text_format_ >= 0 && !lookup;
+    if (as_text) {
+        if (!extract_render_) extract_render_ = std::make_unique<ExtractRender>();
+        extract_render_->begin();
+        out.extract_text.armed = true;
+    }
     do {
         const size_t n = newline_cut(data, pos, len, MAXC) - pos;
         if (n > ((size_t)1 << 30)) throw HipError{"scan_host: a single line exceeds 1 GiB"};
@@ -1802,6 +1837,12 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
             if (part.render.status != RENDER_OK) out.render.status = part.render.status;
             else if (part.render.len) out.render_own.insert(out.render_own.end(), part.render.text, part.render.text + part.render.len);
         }
+        if (part.extract_text.armed) {
+            ExtractTextView& v = out.extract_text;
+            if (part.extract_text.status != XR_OK) v.status = part.extract_text.status;
+            v.n_records += part.extract_text.n_records;
+            for (int t = 0; t < IT_COUNT; ++t) v.by_type[t] += part.extract_text.by_type[t];
+        }
         // a piece ends at a line end: its block goes behind the blocks of the pieces in front of it
         if (part.has_hit_lines) {
             out.has_hit_lines = true;
@@ -1839,6 +1880,7 @@ void Scanner::scan_host(const uint8_t* data, size_t len, bool lookup, bool want_
         v.line_off = out.hl_off_own.data(); v.line_no = out.hl_no_own.empty() ? nullptr : out.hl_no_own.data();
         v.line_of_fin = out.hl_of_own.empty() ? nullptr : out.hl_of_own.data(); v.line_of_c4 = nullptr;
     }
+    if (as_text && out.extract_text.status == XR_OK) { out.extract_text.text = extract_render_->joined(); out.extract_text.len = extract_render_->joined_len(); }
     if (out.render.armed && out.render.status == RENDER_OK) { out.render.text = out.render_own.empty() ? nullptr : out.render_own.data(); out.render.len = out.render_own.size(); }
     if (out.has_segments) {
         out.segments = out.seg_own.data(); out.n_segments = out.seg_own.size();

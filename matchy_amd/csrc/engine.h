@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "db_image.h"
+#include "extract_render.h"
 #include "hip_owners.h"
 #include "hit_lines.h"
 #include "inflate.h"
@@ -126,6 +127,9 @@ struct ScanOutput {
     // HITS_FINAL); scan_host owns it in render_own, the blocks of its pieces end to end
     RenderView render;
     std::vector<uint8_t> render_own;
+    // candidates as text (Scanner::set_extract_text): the output of `matchy extract` for the candidates of this fetch, in pinned host memory,
+    // BORROWED like fin; scan_host hands out the blocks of its pieces end to end, with the counts summed. `cands` stays empty then.
+    ExtractTextView extract_text;
 };
 
 // Process-wide registry of the host ranges this library pinned (hipHostRegister): the caller's (matchy_amd_host_register, kept until
@@ -313,6 +317,16 @@ public:
     bool unique() const { return unique_; }
     void reset_unique();
     uint64_t unique_count() const;
+    // Candidates as text (extract_render.hip), for extractor handles: while a format is set (xrender::FORMAT_*; negative: off), a fetch of
+    // an extraction scan with want_cands orders its candidates and writes the output of `matchy extract` on the device; ScanOutput::extract_text
+    // is what comes back, and the candidate records stay where they are. With set_unique the block holds the first occurrences only. A
+    // launch the order key does not hold is refused (XR_REFUSED) before the distinct set sees it. Off (the default), nothing of it is
+    // allocated, launched or copied.
+    void set_extract_text(int format) { extract_text_format_ = format; }
+    int extract_text_format() const { return extract_text_format_; }
+    // device milliseconds of keys + sort, measure, write and the block's copy of the last fetch that rendered candidates
+    void extract_text_timing(float out_ms[4]) const { for (int k = 0; k < 4; ++k) out_ms[k] = 0; if (extract_render_) extract_render_->timing(out_ms); }
+    uint64_t extract_text_allocations() const { return extract_render_ ? extract_render_->allocations() : 0; }
     // Hit tally (tally.hip): while on, every fetch of a lookup scan counts the final records of its batch per distinct (item type, matched
     // text) in a table that lives in device memory across scans and pieces; tally_top reads the first `limit` entries out (0 = all). Off
     // (the default), nothing of it is allocated, launched or copied; switching it off keeps what was counted.
@@ -463,6 +477,8 @@ private:
     std::unique_ptr<WholeLines> wl_;
     bool unique_ = false;
     std::unique_ptr<DistinctSet> distinct_;    // created by the first set_unique(true), kept (with its texts) while the feature is switched off
+    int extract_text_format_ = -1;
+    std::unique_ptr<ExtractRender> extract_render_;   // created by the first fetch that renders candidates
     bool tally_on_ = false;
     std::unique_ptr<HitTally> tally_;          // created by the first set_tally(true), kept (with its counts) while the feature is switched off
     DevBuf<uint32_t> spill_scratch_;           // per-thread scratch of k_lookup_spill (allocated when a scan first spills)

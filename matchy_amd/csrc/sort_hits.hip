@@ -12,6 +12,9 @@
 // Digits that are the same in every key (the high bytes of short lengths and of offsets below the batch size: usually three or
 // four of the eight) are found by k_sort_plan from the global histogram and their passes return at once; the ping-pong halves each
 // pass reads and writes are planned there too, so nothing comes back to the host between the launches.
+//
+// sort_pairs is the same sort for (key, value) pairs another pass has built (extract_render.hip: the candidates of `matchy extract` by
+// line, type rank and start): k_sort_hist counts the digits of the ready keys, then the plan and the digit passes run as above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +56,20 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_keys(const FinalHit* fin,
         const unsigned long long k = ((unsigned long long)f.start << 32) | ((unsigned long long)d_type_rank(f.len_type >> 24) << 24) | (f.len_type & 0xFFFFFFull);
         keys[i] = k;
         vals[i] = i;
+#pragma unroll
+        for (uint32_t p = 0; p < SORT_PASSES; ++p) atomicAdd(&h[p * SORT_BINS + ((uint32_t)(k >> (8 * p)) & 0xFFu)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < SORT_PASSES * SORT_BINS; i += SORT_THREADS) if (h[i]) atomicAdd(&ghist[i], h[i]);
+}
+
+// the histogram alone, over keys the caller has built (sort_pairs)
+__global__ __launch_bounds__(SORT_THREADS) void k_sort_hist(const unsigned long long* keys, uint32_t n, uint32_t* ghist) {
+    __shared__ uint32_t h[SORT_PASSES * SORT_BINS];
+    for (uint32_t i = threadIdx.x; i < SORT_PASSES * SORT_BINS; i += SORT_THREADS) h[i] = 0;
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * SORT_THREADS + threadIdx.x; i < n; i += gridDim.x * SORT_THREADS) {
+        const unsigned long long k = keys[i];
 #pragma unroll
         for (uint32_t p = 0; p < SORT_PASSES; ++p) atomicAdd(&h[p * SORT_BINS + ((uint32_t)(k >> (8 * p)) & 0xFFu)], 1u);
     }
@@ -187,30 +204,58 @@ size_t sort_hits_temp_bytes(uint32_t n) {
     return (PLAN_WORDS + GHIST_WORDS + 2 * nblocks * SORT_BINS) * 4;   // plan, digit totals, tile histograms, tile offsets
 }
 
+// the layout of `temp`
+struct SortTemp { SortPlan* plan; uint32_t* ghist; uint32_t* bhist; uint32_t* boff; uint32_t nblocks; };
+static SortTemp sort_temp(void* temp, uint32_t n) {
+    uint32_t* words = reinterpret_cast<uint32_t*>(temp);
+    SortTemp t;
+    t.plan = reinterpret_cast<SortPlan*>(words);
+    t.ghist = words + PLAN_WORDS;
+    t.bhist = t.ghist + GHIST_WORDS;
+    t.nblocks = (n + SORT_TILE - 1) / SORT_TILE;
+    t.boff = t.bhist + (size_t)t.nblocks * SORT_BINS;
+    return t;
+}
+static int keys_grid(uint32_t n) { return (int)std::min<uint32_t>((n + SORT_THREADS - 1) / SORT_THREADS, 1024u); }
+
+// the plan and the digit passes, over the keys and values in half 0 and their histogram in t.ghist
+static void sort_digit_passes(unsigned long long* keys, uint32_t* vals, uint32_t n, const SortTemp& t, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sort_plan, dim3(1), dim3(256), 0, stream, (const uint32_t*)t.ghist, n, t.plan);
+    for (uint32_t p = 0; p < SORT_PASSES; ++p) {
+        hipLaunchKernelGGL(k_sort_block_hist, dim3(t.nblocks), dim3(SORT_THREADS), 0, stream, (const unsigned long long*)keys, n, p, (const SortPlan*)t.plan, t.bhist);
+        hipLaunchKernelGGL(k_sort_scan, dim3((t.nblocks + SCAN_CHUNK - 1) / SCAN_CHUNK), dim3(SORT_BINS), 0, stream, (const uint32_t*)t.ghist, p,
+                           (const SortPlan*)t.plan, (const uint32_t*)t.bhist, t.boff, t.nblocks);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(t.nblocks), dim3(SORT_THREADS), 0, stream, keys, vals, n, p, (const SortPlan*)t.plan, (const uint32_t*)t.boff);
+    }
+}
+
 // keys/vals: 2 * n entries each (two halves); temp: sort_hits_temp_bytes(n); out: n records
 hipError_t sort_hits(const FinalHit* fin, uint32_t n, unsigned long long* keys, uint32_t* vals, void* temp, size_t temp_bytes,
                      FinalHit* out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (temp_bytes < sort_hits_temp_bytes(n)) return hipErrorInvalidValue;
-    uint32_t* words = reinterpret_cast<uint32_t*>(temp);
-    SortPlan* plan = reinterpret_cast<SortPlan*>(words);
-    uint32_t* ghist = words + PLAN_WORDS;
-    uint32_t* bhist = ghist + GHIST_WORDS;
-    const uint32_t nblocks = (n + SORT_TILE - 1) / SORT_TILE;
-    uint32_t* boff = bhist + (size_t)nblocks * SORT_BINS;
-    hipError_t e = hipMemsetAsync(ghist, 0, GHIST_WORDS * 4, stream);
+    const SortTemp t = sort_temp(temp, n);
+    hipError_t e = hipMemsetAsync(t.ghist, 0, GHIST_WORDS * 4, stream);
     if (e != hipSuccess) return e;
-    const int kb = (int)std::min<uint32_t>((n + SORT_THREADS - 1) / SORT_THREADS, 1024u);
-    hipLaunchKernelGGL(k_sort_keys, dim3(kb), dim3(SORT_THREADS), 0, stream, fin, n, keys, vals, ghist);
-    hipLaunchKernelGGL(k_sort_plan, dim3(1), dim3(256), 0, stream, (const uint32_t*)ghist, n, plan);
-    for (uint32_t p = 0; p < SORT_PASSES; ++p) {
-        hipLaunchKernelGGL(k_sort_block_hist, dim3(nblocks), dim3(SORT_THREADS), 0, stream, (const unsigned long long*)keys, n, p, (const SortPlan*)plan, bhist);
-        hipLaunchKernelGGL(k_sort_scan, dim3((nblocks + SCAN_CHUNK - 1) / SCAN_CHUNK), dim3(SORT_BINS), 0, stream, (const uint32_t*)ghist, p,
-                           (const SortPlan*)plan, (const uint32_t*)bhist, boff, nblocks);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks), dim3(SORT_THREADS), 0, stream, keys, vals, n, p, (const SortPlan*)plan, (const uint32_t*)boff);
-    }
-    hipLaunchKernelGGL(k_sort_gather, dim3((n + 255) / 256), dim3(256), 0, stream, fin, (const uint32_t*)vals, n, (const SortPlan*)plan, out);
+    hipLaunchKernelGGL(k_sort_keys, dim3(keys_grid(n)), dim3(SORT_THREADS), 0, stream, fin, n, keys, vals, t.ghist);
+    sort_digit_passes(keys, vals, n, t, stream);
+    hipLaunchKernelGGL(k_sort_gather, dim3((n + 255) / 256), dim3(256), 0, stream, fin, (const uint32_t*)vals, n, (const SortPlan*)t.plan, out);
     return hipGetLastError();
 }
+
+// The same sort for (key, value) pairs the caller has built (extract_render.hip): keys[0, n) and vals[0, n) are half 0 of arrays of
+// 2 * n entries; temp: sort_hits_temp_bytes(n). The sorted pairs lie in the half that *sort_pairs_half(temp) names once the stream
+// gets there (0 or 1: the word is written on the device); n == 0 launches nothing and leaves that word alone.
+hipError_t sort_pairs(unsigned long long* keys, uint32_t* vals, uint32_t n, void* temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (temp_bytes < sort_hits_temp_bytes(n)) return hipErrorInvalidValue;
+    const SortTemp t = sort_temp(temp, n);
+    hipError_t e = hipMemsetAsync(t.ghist, 0, GHIST_WORDS * 4, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sort_hist, dim3(keys_grid(n)), dim3(SORT_THREADS), 0, stream, (const unsigned long long*)keys, n, t.ghist);
+    sort_digit_passes(keys, vals, n, t, stream);
+    return hipGetLastError();
+}
+const uint32_t* sort_pairs_half(const void* temp) { return &reinterpret_cast<const SortPlan*>(temp)->final_half; }
 
 }  // namespace mxy
