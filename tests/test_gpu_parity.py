@@ -99,11 +99,13 @@ def test_extractor_differential_fuzz(gpu_extractor, oracle):
 
 
 def test_extractor_segment_and_block_edges(gpu_extractor, oracle):
-    # tokens / runs that straddle the 64-byte row, 1 KiB block and 16 KiB segment edges of the tokenizer
+    # tokens / runs that straddle the edges of k_anchor's geometry: 256-byte rows (lane 63 -> lane 0), 2 KiB blocks (2048, 6144: a
+    # block edge that is no window or segment edge), the 8 KiB LDS window and the shortest segment (SEG_MIN = 8192), 16 KiB and
+    # 32 KiB segments; 64 and 1024 were the row and the block of the first tokenizer and stay
     payloads = [b"10.20.30.40", b"evil.example.com", b"user@mail.example.org", b"2001:db8::8a2e:370:7334",
                 b"5d41402abc4b2a76b9719d911017c592", b"2c26b46b68ffc68ff99b453c1d30413413422d706483bfa0f98a5e886266e7ae",
                 b"0x5aAeb6053F3E94C9b9A09f33669435E7Ef1BeAed", b"1A1zP1eP5QGefi2DMPTfTL5SLmv7DivfNa"]
-    for edge in (64, 1024, 16384, 32768):
+    for edge in (64, 256, 1024, 2048, 6144, 8192, 16384, 32768):
         for pl in payloads:
             for shift in range(0, len(pl) + 2):
                 pre = edge - shift
