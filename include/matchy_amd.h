@@ -895,6 +895,53 @@ void matchy_amd_utf16_geometry(uint32_t out[2]);
  * submitted without want_text is scanned with line context whatever the setting is, like an armed gz pack. */
 int32_t matchy_multi_scanner_submit_utf16(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, uint32_t byte_order, bool want_text,
                                           void *tag, const void *pinned_range);
+/* ---- Percent- and JSON-escaped inputs (opt-in: with these calls never made a scanner allocates, launches and copies nothing more and
+ * every output stays as it is). `data` — host or device memory — is `len` bytes of text that carries escapes; it is decoded on the GPU
+ * (count, prefix, write over the batch and one 16-byte read of the text's length; JSON: a scan over the tiles for the escape state in
+ * front of them) and the ordinary lookup scan runs over the decoded text on the same stream. modes: MATCHY_UNESCAPE_PERCENT,
+ * MATCHY_UNESCAPE_JSON, or both: then the text is percent(json(data)), two runs of the pass.
+ * Every input position emits 0 to 4 bytes. The bytes of a valid escape are consumed: its first byte owns the output.
+ *   PERCENT  '%' followed by two hex digits (either case), all inside the input: the byte with that value. Anything else is literal,
+ *            '%' with fewer than two hex digits behind it or at the end of the input included. '+' stays '+'; "%25" becomes '%' once:
+ *            one pass, no re-scan of its output.
+ *   JSON     A backslash is an introducer if it is not itself escaped: esc[i] = data[i-1] == '\\' && !esc[i-1], esc[0] = 0.
+ *            An introducer and one of " \ / b f n r t: a two-byte escape for the byte it names. An introducer, 'u' and four hex
+ *            digits: a six-byte escape for a UTF-16 code unit, written as UTF-8. A high-surrogate escape followed immediately by a
+ *            low-surrogate escape is written as the four bytes of the pair (the low one emits nothing); any other surrogate escape as
+ *            EF BF BD, one per escape. An introducer followed by anything else is NOT an escape and both bytes emit themselves (\u
+ *            with fewer than four hex digits, a backslash in front of a real LF or as the last byte); the byte behind it still counts
+ *            as escaped.
+ *   Line ends, both modes: a real 0x0A always emits itself. An escape whose value is LF (%0A, %0a, \n, \u000a, \u000A) is written as
+ *            ONE SPACE: a boundary byte for every extractor that LF is one for, but it ends no line. The decoded text has exactly the
+ *            LF bytes of the input, in order, and since no escape spans a real LF, decode(A + B) == decode(A) + decode(B) for any
+ *            cut behind an LF: batches cut at line ends need no state from the batch before.
+ * The text is never longer than the input. Every fetch mode of matchy_scanner_scan_device, line context, hit lines, rendered records
+ * and the tally work as they do there: `bytes` is the length of the decoded text, `lines` counts its '\n' bytes and the offsets of hits
+ * and line records are offsets into it (no mapping back to the raw input).
+ * want_text: the decoded batch is copied to pinned host memory once, behind the scan, for matchy_scan_hit_to_json and the NDJSON calls.
+ * NOT combined with segments or whole-line queries. MATCHY_ERROR_INVALID_PARAM with a message, and a scanner that stays usable: NULL
+ * handles, modes 0 or above 3, no input, len >= 0x7FFF0000, a pending segment table (dropped) and whole-line mode. */
+#define MATCHY_UNESCAPE_PERCENT 1u
+#define MATCHY_UNESCAPE_JSON 2u
+int32_t matchy_scanner_scan_escaped(matchy_scanner_t *scanner, const uint8_t *data, size_t len, uint32_t modes, uint32_t fetch_mode,
+                                    bool want_text, matchy_scan_result_t *out);
+/* text / text_len: the decoded batch — NULL / its length without want_text; borrowed from the scanner until its next scan, or owned by
+ * the result for MATCHY_SCAN_FETCH_SORTED (like the hit arrays of that mode). counters: valid escapes decoded, U+FFFD written, escapes
+ * for LF written as a space; with both modes, summed over the two runs. MATCHY_ERROR_INVALID_PARAM for a result of another kind of
+ * scan. Any out pointer may be NULL. */
+int32_t matchy_scan_result_unescaped(const matchy_scan_result_t *result, const uint8_t **text, size_t *text_len, uint64_t counters[3]);
+/* Milliseconds of the count (JSON: with the state steps), prefix and write steps of the last escaped scan, summed over its runs
+ * (recorded for every such scan, with or without matchy_scanner_set_profile); zeros before the first. */
+void matchy_scanner_get_unescape_timing(const matchy_scanner_t *scanner, float out_ms[3]);
+/* Input bytes per tile of the passes, tiles per workgroup of the prefix step, tiles per workgroup of the state scan (tests place
+ * their cases on these boundaries). */
+void matchy_amd_unescape_geometry(uint32_t out[3]);
+/* matchy_multi_scanner_submit of an escaped batch: the worker that takes it decodes and scans it on its GPU. The batch from _next
+ * answers matchy_scan_result_unescaped; its data / len are the decoded text, owned by the result, and its length — NULL and the length
+ * without want_text. pinned_range as for matchy_multi_scanner_submit. A batch armed with matchy_multi_scanner_set_render that is
+ * submitted without want_text is scanned with line context whatever the setting is, like an armed gz pack. */
+int32_t matchy_multi_scanner_submit_escaped(matchy_multi_scanner_t *ms, const uint8_t *data, size_t len, uint32_t modes, bool want_text,
+                                            void *tag, const void *pinned_range);
 /* Deterministic builds for tests: fixes the build_epoch metadata value. */
 int32_t matchy_builder_set_build_epoch(matchy_builder_t *b, uint64_t epoch);
 

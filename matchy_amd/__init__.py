@@ -72,9 +72,12 @@ EXPORTED_SYMBOLS = [
     "matchy_scanner_get_whole_lines_timing", "matchy_multi_scanner_set_whole_lines",
     "matchy_scanner_scan_utf16", "matchy_scan_result_utf16", "matchy_scanner_get_utf16_timing", "matchy_amd_utf16_geometry",
     "matchy_multi_scanner_submit_utf16",
+    "matchy_scanner_scan_escaped", "matchy_scan_result_unescaped", "matchy_scanner_get_unescape_timing", "matchy_amd_unescape_geometry",
+    "matchy_multi_scanner_submit_escaped",
 ]
 
 UTF16_LE, UTF16_BE = 0, 1   # MATCHY_UTF16_*: the byte order of a UTF-16 scan (Scanner.scan_utf16)
+UNESCAPE_PERCENT, UNESCAPE_JSON = 1, 2   # MATCHY_UNESCAPE_*: the grammars of an escaped scan (Scanner.scan_escaped); both: percent(json(x))
 
 # MATCHY_GZ_*: the status of one member of a gz scan (ScanResult.gz_status)
 GZ_OK, GZ_BAD_HEADER, GZ_TRUNCATED, GZ_BAD_BLOCK, GZ_BAD_CODES, GZ_BAD_SYMBOL, GZ_BAD_DISTANCE = 0, 1, 2, 3, 4, 5, 6
@@ -426,6 +429,11 @@ def lib():
         "matchy_scanner_get_utf16_timing": (None, [vp, C.POINTER(C.c_float)]),
         "matchy_amd_utf16_geometry": (None, [C.POINTER(C.c_uint32)]),
         "matchy_multi_scanner_submit_utf16": (C.c_int32, [vp, vp, C.c_size_t, C.c_uint32, C.c_bool, vp, vp]),
+        "matchy_scanner_scan_escaped": (C.c_int32, [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
+        "matchy_scan_result_unescaped": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+        "matchy_scanner_get_unescape_timing": (None, [vp, C.POINTER(C.c_float)]),
+        "matchy_amd_unescape_geometry": (None, [C.POINTER(C.c_uint32)]),
+        "matchy_multi_scanner_submit_escaped": (C.c_int32, [vp, vp, C.c_size_t, C.c_uint32, C.c_bool, vp, vp]),
         "matchy_multi_scanner_submit_gz": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzMember), C.c_size_t, C.c_bool, vp]),
         "matchy_scanner_scan_gz_files": (C.c_int32, [vp, vp, C.c_size_t, C.POINTER(_GzFile), C.c_size_t, C.c_uint32, C.c_bool, C.POINTER(_ScanResult)]),
         "matchy_scan_result_gz_files": (C.c_int32, [C.POINTER(_ScanResult), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
@@ -875,6 +883,18 @@ class ScanResult:
             return None
         return dict(text=C.string_at(t.value, n.value) if t.value else None, text_len=int(n.value), code_units=int(units.value), replaced=int(repl.value))
 
+    def unescaped(self):
+        """what an escaped scan (Scanner.scan_escaped; matchy_scan_result_unescaped) says about its batch, as a dict: text (the decoded
+        batch as bytes, a copy; None without want_text), text_len, escapes (valid escapes decoded), replaced (U+FFFD written) and
+        lf_escapes (escapes for LF written as a space); None for any other scan"""
+        if self._raw is None:
+            raise RuntimeError("the result is closed")
+        t, n, ctr = C.c_void_p(), C.c_size_t(), (C.c_uint64 * 3)()
+        if lib().matchy_scan_result_unescaped(C.byref(self._raw), C.byref(t), C.byref(n), ctr) != 0:
+            return None
+        return dict(text=C.string_at(t.value, n.value) if t.value else None, text_len=int(n.value), escapes=int(ctr[0]), replaced=int(ctr[1]),
+                    lf_escapes=int(ctr[2]))
+
     def gz_window(self):
         """(WINDOW_* status, carry bytes) of a gz scan of a window (Scanner.scan_gz_window): the carry is the partial line behind the
         window's last newline, to be handed to the next window; None for any other scan"""
@@ -1281,6 +1301,28 @@ class Scanner:
         lib().matchy_scanner_get_utf16_timing(self._h, out)
         return tuple(out)
 
+    def scan_escaped(self, data, modes=UNESCAPE_PERCENT, want_text=False, fetch_mode=1, nbytes=None) -> ScanResult:
+        """decode the percent- and/or JSON-escaped batch `data` on the GPU and scan the text (matchy_scanner_scan_escaped). data: bytes,
+        or an address (host or device memory) together with nbytes. modes: UNESCAPE_PERCENT, UNESCAPE_JSON or both (percent(json(x))).
+        The result's offsets are offsets into the decoded text; unescaped() has the text (with want_text), its length and the
+        counters. An escape for LF becomes a space: the text has the line ends of the input."""
+        if isinstance(data, int):
+            ptr, n = data, int(nbytes)
+        else:
+            data = bytes(data)
+            ptr, n = C.cast(C.c_char_p(data), C.c_void_p), len(data)
+        raw = _ScanResult()
+        rc = lib().matchy_scanner_scan_escaped(self._h, ptr, n, modes, fetch_mode, bool(want_text), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"matchy_scanner_scan_escaped failed: rc={rc} {last_error()}")
+        return ScanResult(self, raw)
+
+    def unescape_timing_ms(self):
+        """(count, prefix, write) milliseconds of the last escaped scan, summed over its runs; zeros before the first"""
+        out = (C.c_float * 3)()
+        lib().matchy_scanner_get_unescape_timing(self._h, out)
+        return tuple(out)
+
     def scan_gz_files(self, blobs, want_text=False, fetch_mode=1) -> ScanResult:
         """inflate the gzip files `blobs` (bytes each, of one member or many) on the GPU, one wave per member, and scan them as one batch
         of len(blobs) segments (matchy_scanner_scan_gz_files). The result has .segments / .segment_of like a segmented scan,
@@ -1509,6 +1551,13 @@ class MultiScanner:
         if rc != 0:
             raise RuntimeError(f"matchy_multi_scanner_submit_utf16 failed ({rc}): " + last_error())
 
+    def submit_escaped(self, host_ptr: int, nbytes: int, modes=UNESCAPE_PERCENT, want_text=False, tag: int = 0):
+        """queue one escaped batch that lives at a host address (matchy_multi_scanner_submit_escaped). next() then carries "unescaped"
+        (text_len and the counters) and "text": the decoded batch with want_text, else None"""
+        rc = lib().matchy_multi_scanner_submit_escaped(self._h, host_ptr, nbytes, modes, bool(want_text), tag, None)
+        if rc != 0:
+            raise RuntimeError(f"matchy_multi_scanner_submit_escaped failed ({rc}): " + last_error())
+
     def submit_gz_ptr(self, host_ptr: int, nbytes: int, members, want_text=False, tag: int = 0):
         """queue a pack of gzip files that lives at a host address: members = [(offset, len, out_len)] (matchy_multi_scanner_submit_gz).
         next() then carries gz_status, the segment table and, with want_text, the inflated text"""
@@ -1595,6 +1644,10 @@ class MultiScanner:
         if u is not None:   # a UTF-16 batch: data / len are the UTF-8 text (NULL without want_text) and its length
             out["text"] = C.string_at(b.data, b.len) if b.data else None
             out["utf16"] = dict(text_len=u["text_len"], code_units=u["code_units"], replaced=u["replaced"])
+        u = r.unescaped()
+        if u is not None:   # an escaped batch: data / len are the decoded text (NULL without want_text) and its length
+            out["text"] = C.string_at(b.data, b.len) if b.data else None
+            out["unescaped"] = {k: u[k] for k in ("text_len", "escapes", "replaced", "lf_escapes")}
         r.close()
         return out
 
@@ -1637,6 +1690,14 @@ def utf16_geometry():
     out = (C.c_uint32 * 2)()
     lib().matchy_amd_utf16_geometry(out)
     return int(out[0]), int(out[1])
+
+
+def unescape_geometry():
+    """(input bytes per tile, tiles per workgroup of the prefix step, tiles per workgroup of the state scan) of the unescape passes
+    (matchy_amd_unescape_geometry)"""
+    out = (C.c_uint32 * 3)()
+    lib().matchy_amd_unescape_geometry(out)
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def numa_cpus(sysfs_root: str, pci_bus_id: str):

@@ -10,7 +10,7 @@ LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libmatchy_amd.so"
 BINDIR = PKG / "bin"
 CLI = BINDIR / "matchy"
-SOURCES = ["k_anchor.hip", "validate_kernels.hip", "lookup_kernels.hip", "sort_hits.hip", "line_index.hip", "hit_lines.hip", "render.hip", "extract_render.hip", "text_table.hip", "distinct.hip", "tally.hip", "segments.hip", "inflate.hip", "inflate_pieces.hip", "whole_lines.hip", "utf16.hip", "ip_tables.hip", "engine.cpp", "db_image.cpp", "db_builder.cpp", "data_codec.cpp", "unicode_lower.cpp", "host_topology.cpp", "host_lookup.cpp", "capi.cpp", "ndjson_host.cpp", "multi_scanner.cpp"]
+SOURCES = ["k_anchor.hip", "validate_kernels.hip", "lookup_kernels.hip", "sort_hits.hip", "line_index.hip", "hit_lines.hip", "render.hip", "extract_render.hip", "text_table.hip", "distinct.hip", "tally.hip", "segments.hip", "inflate.hip", "inflate_pieces.hip", "whole_lines.hip", "utf16.hip", "unescape.hip", "ip_tables.hip", "engine.cpp", "db_image.cpp", "db_builder.cpp", "data_codec.cpp", "unicode_lower.cpp", "host_topology.cpp", "host_lookup.cpp", "capi.cpp", "ndjson_host.cpp", "multi_scanner.cpp"]
 # the `matchy` command line, built with g++ on top of the library: main and the small commands, `matchy match`
 CLI_SOURCES = ["cli_main.cpp", "cli_match.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -405,6 +405,37 @@ const char* mxy::capi::utf16_refusal(const uint8_t* data, size_t len, uint32_t b
     if (len >= ((size_t)1 << 31) || utf16::out_bound(len) >= (1ull << 31)) return "the input may transcode to 2^31 bytes or more (3 bytes per code unit); cut it into smaller batches";
     return nullptr;
 }
+const char* mxy::capi::unescape_refusal(const uint8_t* data, size_t len, uint32_t modes) {
+    if (modes == 0 || modes > (MATCHY_UNESCAPE_PERCENT | MATCHY_UNESCAPE_JSON)) return "modes is MATCHY_UNESCAPE_PERCENT, MATCHY_UNESCAPE_JSON or both";
+    if (!data && len) return "no input";
+    if (len >= 0x7FFF0000u) return "the input reaches 2^31 bytes; cut it into smaller batches";
+    return nullptr;
+}
+
+// Scans behind a front pass (Scanner::utf16_transcode, Scanner::unescape): the pass and the scan are queued on the scanner's own
+// stream; the fetch is that of matchy_scanner_scan_device. scan_front_text is what the entries share: the scan of the text `b` the pass
+// left on the device, queue_text() behind the scan's kernels, finish() behind the fetch (the pass's Result, which it returns), and the
+// text in the result — borrowed, or owned where the hit arrays are.
+namespace {
+template <class QueueText, class Finish>
+auto scan_front_text(ScannerH* h, const Scanner::GzBatch& b, uint32_t fetch_mode, const char* entry, QueueText&& queue_text, Finish&& finish,
+                     matchy_scan_result_t* out) {
+    if (b.len >= 0x7FFF0000u) throw ParamError{std::string(entry) + ": the text reaches 2^31 bytes; cut the input into smaller batches"};
+    const FetchPlan plan(fetch_mode);
+    ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
+    const bool hit_lines = build_request(*h->sc, plan, b.text, b.len, b.stream, false, true, rq);
+    h->sc->scan_device(rq, b.stream);
+    queue_text();
+    ScanOutput so;
+    h->sc->fetch(so, false, b.stream, plan.hit_mode(), plan.sorted);
+    const auto u = finish();
+    finish_result(*h->sc, plan, so, u.text_len, hit_lines, out);
+    ScanResultInternal* in = internal_of(out);
+    in->front_text = u.text; in->front_text_len = u.text_len;
+    if (plan.sorted && u.text) { in->front_text_own.assign(u.text, u.text + u.text_len); in->front_text = in->front_text_own.data(); }
+    return u;
+}
+}  // namespace
 
 // hit tally (Scanner::set_tally, tally.hip): the table is the scanner's
 namespace {
@@ -1279,8 +1310,7 @@ static int32_t scan_gz_pack(ScannerH* h, const uint8_t* packed, size_t packed_le
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
     catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
 }
-// UTF-16 inputs (Scanner::utf16_transcode, utf16.hip): the transcoding and the scan are queued on the scanner's own stream; the fetch is
-// that of matchy_scanner_scan_device
+// UTF-16 inputs (Scanner::utf16_transcode, utf16.hip): scan_front_text does the scan behind the pass
 static_assert(MATCHY_UTF16_LE == utf16::ORDER_LE && MATCHY_UTF16_BE == utf16::ORDER_BE, "the kernels take MATCHY_UTF16_* values directly");
 int32_t matchy_scanner_scan_utf16(matchy_scanner_t* s, const uint8_t* data, size_t len, uint32_t byte_order, uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out) {
     if (!s || !out) { set_error("matchy_scanner_scan_utf16: no scanner or no result"); return MATCHY_ERROR_INVALID_PARAM; }
@@ -1289,21 +1319,11 @@ int32_t matchy_scanner_scan_utf16(matchy_scanner_t* s, const uint8_t* data, size
     ScannerH* h = reinterpret_cast<ScannerH*>(s);
     try {
         const Scanner::GzBatch b = h->sc->utf16_transcode(data, len, byte_order);   // refuses segments and whole-line mode
-        if (b.len >= 0x7FFF0000u) throw ParamError{"matchy_scanner_scan_utf16: the text reaches 2^31 bytes; cut the input into smaller batches"};
-        const FetchPlan plan(fetch_mode);
-        ScanRequest rq;   // not forked: the scan shares the stream of the pass in front of it
-        const bool hit_lines = build_request(*h->sc, plan, b.text, b.len, b.stream, false, true, rq);
-        h->sc->scan_device(rq, b.stream);
-        h->sc->utf16_queue_text(want_text);
-        ScanOutput so;
-        h->sc->fetch(so, false, b.stream, plan.hit_mode(), plan.sorted);
-        const Utf16Transcode::Result u = h->sc->utf16_finish();
-        finish_result(*h->sc, plan, so, u.text_len, hit_lines, out);
+        const Utf16Transcode::Result u = scan_front_text(h, b, fetch_mode, "matchy_scanner_scan_utf16", [&] { h->sc->utf16_queue_text(want_text); },
+                                                         [&] { return h->sc->utf16_finish(); }, out);
         ScanResultInternal* in = internal_of(out);
         in->has_utf16 = true;
-        in->utf16_text = u.text; in->utf16_text_len = u.text_len;
         in->utf16_code_units = u.code_units; in->utf16_replaced = u.replaced;
-        if (plan.sorted && u.text) { in->utf16_text_own.assign(u.text, u.text + u.text_len); in->utf16_text = in->utf16_text_own.data(); }
         return MATCHY_SUCCESS;
     } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
     catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
@@ -1313,8 +1333,8 @@ int32_t matchy_scan_result_utf16(const matchy_scan_result_t* r, const uint8_t** 
     if (!r) { set_error("matchy_scan_result_utf16: no result"); return MATCHY_ERROR_INVALID_PARAM; }
     const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
     if (!in || !in->has_utf16) { set_error("matchy_scan_result_utf16: the result was not produced by a UTF-16 scan"); return MATCHY_ERROR_INVALID_PARAM; }
-    if (text) *text = in->utf16_text;
-    if (text_len) *text_len = in->utf16_text_len;
+    if (text) *text = in->front_text;
+    if (text_len) *text_len = in->front_text_len;
     if (code_units) *code_units = in->utf16_code_units;
     if (replaced) *replaced = in->utf16_replaced;
     return MATCHY_SUCCESS;
@@ -1324,6 +1344,41 @@ void matchy_scanner_get_utf16_timing(const matchy_scanner_t* s, float out[3]) {
 }
 void matchy_amd_utf16_geometry(uint32_t out[2]) {
     if (out) { out[0] = utf16::TILE_BYTES; out[1] = UTF16_SCAN_CHUNK; }
+}
+
+// Percent- and JSON-escaped inputs (Scanner::unescape, unescape.hip)
+static_assert(MATCHY_UNESCAPE_PERCENT == unescape::MODE_PERCENT && MATCHY_UNESCAPE_JSON == unescape::MODE_JSON, "the pass takes MATCHY_UNESCAPE_* values directly");
+int32_t matchy_scanner_scan_escaped(matchy_scanner_t* s, const uint8_t* data, size_t len, uint32_t modes, uint32_t fetch_mode, bool want_text, matchy_scan_result_t* out) {
+    if (!s || !out) { set_error("matchy_scanner_scan_escaped: no scanner or no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    memset(out, 0, sizeof(*out));
+    if (const char* why = unescape_refusal(data, len, modes)) { set_error(std::string("matchy_scanner_scan_escaped: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    ScannerH* h = reinterpret_cast<ScannerH*>(s);
+    try {
+        const Scanner::GzBatch b = h->sc->unescape(data, len, modes);   // refuses segments and whole-line mode
+        const Unescape::Result u = scan_front_text(h, b, fetch_mode, "matchy_scanner_scan_escaped", [&] { h->sc->unescape_queue_text(want_text); },
+                                                   [&] { return h->sc->unescape_finish(); }, out);
+        ScanResultInternal* in = internal_of(out);
+        in->has_unescaped = true;
+        in->unescape_counters[0] = u.escapes; in->unescape_counters[1] = u.replaced; in->unescape_counters[2] = u.lf_escapes;
+        return MATCHY_SUCCESS;
+    } catch (const ParamError& e) { set_error(e.what); matchy_scan_result_free(out); return MATCHY_ERROR_INVALID_PARAM; }
+    catch (const HipError& e) { set_error(e.what); return MATCHY_ERROR_IO; }
+    catch (const std::exception& e) { set_error(e.what()); return MATCHY_ERROR_IO; }
+}
+int32_t matchy_scan_result_unescaped(const matchy_scan_result_t* r, const uint8_t** text, size_t* text_len, uint64_t counters[3]) {
+    if (!r) { set_error("matchy_scan_result_unescaped: no result"); return MATCHY_ERROR_INVALID_PARAM; }
+    const ScanResultInternal* in = reinterpret_cast<const ScanResultInternal*>(r->_internal);
+    if (!in || !in->has_unescaped) { set_error("matchy_scan_result_unescaped: the result was not produced by an escaped scan"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (text) *text = in->front_text;
+    if (text_len) *text_len = in->front_text_len;
+    if (counters) for (int k = 0; k < 3; ++k) counters[k] = in->unescape_counters[k];
+    return MATCHY_SUCCESS;
+}
+void matchy_scanner_get_unescape_timing(const matchy_scanner_t* s, float out[3]) {
+    if (s && out) reinterpret_cast<const ScannerH*>(s)->sc->unescape_timing(out);
+}
+void matchy_amd_unescape_geometry(uint32_t out[3]) {
+    if (out) { out[0] = unescape::TILE_BYTES; out[1] = UNESCAPE_SCAN_CHUNK; out[2] = UNESCAPE_STATE_CHUNK; }
 }
 
 int32_t matchy_scanner_scan_gz(matchy_scanner_t* s, const uint8_t* packed, size_t packed_len, const matchy_gz_member_t* members, size_t n, uint32_t fetch_mode,

@@ -20,6 +20,8 @@ const char* gz_stream_refusal(const uint8_t* packed, size_t packed_len, const ma
 
 // the 2^31 bound of matchy_scanner_scan_utf16 / matchy_multi_scanner_submit_utf16 and their byte_order test
 const char* utf16_refusal(const uint8_t* data, size_t len, uint32_t byte_order);
+// the same for matchy_scanner_scan_escaped / matchy_multi_scanner_submit_escaped: modes, no input, the length bound
+const char* unescape_refusal(const uint8_t* data, size_t len, uint32_t modes);
 
 struct ScanResultInternal {
     std::vector<matchy_scan_hit_t> hits;
@@ -60,12 +62,14 @@ struct ScanResultInternal {
     std::vector<uint8_t> gz_text_own;
     const uint8_t* gz_text = nullptr;
     size_t gz_text_len = 0;
-    // UTF-16 scan (matchy_scan_result_utf16): the UTF-8 text is the scanner's pinned block, or owned (utf16_text_own) where the hit arrays are
-    bool has_utf16 = false;
-    std::vector<uint8_t> utf16_text_own;
-    const uint8_t* utf16_text = nullptr;
-    size_t utf16_text_len = 0;
+    // scan behind a front pass (matchy_scan_result_utf16, matchy_scan_result_unescaped): the text the pass wrote is the scanner's pinned
+    // block, or owned (front_text_own) where the hit arrays are
+    bool has_utf16 = false, has_unescaped = false;
+    std::vector<uint8_t> front_text_own;
+    const uint8_t* front_text = nullptr;
+    size_t front_text_len = 0;
     uint64_t utf16_code_units = 0, utf16_replaced = 0;
+    uint64_t unescape_counters[3] = {0, 0, 0};   // escapes, replaced, lf_escapes
     // gz scan of files (matchy_scan_result_gz_files): one verdict per file and the members of file f, [first_member[f], first_member[f + 1]); owned
     bool has_gz_files = false;
     std::vector<int32_t> gz_file_status;

@@ -41,6 +41,9 @@ int usage() {
             "               [--encoding=utf-16le|utf-16be|auto]   (UTF-16 inputs are transcoded to UTF-8 on the GPU in front of the scan; auto: per input, by a\n"
             "                                  leading BOM, anything else is scanned as bytes; a leading BOM is skipped; offsets are those of the UTF-8 text;\n"
             "                                  not with --follow, --pack-inputs, --gz-on-gpu, --whole-lines)\n"
+            "               [--unescape=percent|json|json+percent]   (%%XX and/or JSON string escapes are decoded on the GPU in front of the scan; an escape\n"
+            "                                  for a line end becomes a space, so line numbers are the input's; offsets are those of the decoded text;\n"
+            "                                  not with --follow, --pack-inputs, --gz-on-gpu, --whole-lines, --encoding)\n"
             "  matchy query <DATABASE> <QUERY> [-q]\n"
             "  matchy extract <INPUT>... [--format json|csv|text] [--types LIST] [--min-labels N] [-u] [-s] [--show-candidates]\n"
             "               [--render-on-gpu]   (the items of a batch are put into line order and written as json / csv / text on the GPU: one block per\n"

@@ -18,6 +18,9 @@
 // CRC and length so far and the last 32 KiB of text to the next, with the partial line.
 // --encoding=utf-16le|utf-16be|auto sends the batches of UTF-16 inputs to the GPU as they are (matchy_multi_scanner_submit_utf16, utf16.hip):
 // cut behind 000A units (newline_cut16), transcoded to UTF-8 there and scanned; records, offsets and lines are those of the UTF-8 text.
+// --unescape=percent|json|json+percent sends the batches of every input — read as bytes and cut behind LF as ever — to the GPU to be decoded
+// in front of the scan (matchy_multi_scanner_submit_escaped, unescape.hip): records and offsets are those of the decoded text, and since an
+// escape for LF becomes a space, line numbers are those of the input.
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/mman.h>
@@ -84,7 +87,8 @@ struct GzVerdict {
 // file, but its lines count on from those of the windows in front. GZ_STREAM (--gz-stream-windows): one window of ONE DEFLATE stream, a
 // segment whose lines count on in the same way.
 // UTF16 (--encoding): a piece of one UTF-16 input that ends behind a 000A unit; what comes back is its UTF-8 text.
-enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW, GZ_STREAM, UTF16 };
+// ESCAPED (--unescape): a newline-aligned piece of one input, like STREAM; what comes back is its decoded text.
+enum class BatchKind { STREAM, PACK, GZ_PACK, GZ_WINDOW, GZ_STREAM, UTF16, ESCAPED };
 // --encoding: how the bytes of an input are read. AUTO decides per input by its first two bytes (FF FE / FE FF, else BYTES).
 enum class Encoding { BYTES, UTF16LE, UTF16BE, AUTO };
 struct Batch {
@@ -104,20 +108,22 @@ struct Batch {
     uint32_t stream_text_cap = 0, stream_flags = 0;           // GZ_STREAM: MATCHY_STREAM_*
     bool window_last = false;           // GZ_WINDOW: the file ends with this window
     uint32_t byte_order = 0;            // UTF16: MATCHY_UTF16_*
+    uint32_t unescape_modes = 0;        // ESCAPED: MATCHY_UNESCAPE_*
     bool armed = false;                 // --render-on-gpu: the batch was submitted with matchy_multi_scanner_set_render
 
     bool is_gz() const { return kind == BatchKind::GZ_PACK || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
-    bool segmented() const { return kind != BatchKind::STREAM && kind != BatchKind::UTF16; }   // the scan result carries a segment table
+    bool front_pass() const { return kind == BatchKind::UTF16 || kind == BatchKind::ESCAPED; }   // the scan runs over a text made from the batch on the device
+    bool segmented() const { return kind != BatchKind::STREAM && !front_pass(); }   // the scan result carries a segment table
     // the batch's text is made on the device: it comes back only where wants_text says so
-    bool text_on_device() const { return is_gz() || kind == BatchKind::UTF16; }
+    bool text_on_device() const { return is_gz() || front_pass(); }
     // the batch goes on where its input's earlier batches ended: only the first has line base 0 (every segment of a pack is a whole file)
-    bool continues_lines() const { return kind == BatchKind::STREAM || kind == BatchKind::UTF16 || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
-    // a gz or UTF-16 batch: its text comes back only where something is rendered from it on the host
+    bool continues_lines() const { return kind == BatchKind::STREAM || front_pass() || kind == BatchKind::GZ_WINDOW || kind == BatchKind::GZ_STREAM; }
+    // a gz, UTF-16 or escaped batch: its text comes back only where something is rendered from it on the host
     bool wants_text(bool json, bool gather) const { return json && !gather && !armed; }
     // every input the batch carries, in segment order
     template <class F> void each_input(F&& f) const {
         switch (kind) {
-            case BatchKind::STREAM: case BatchKind::UTF16: f(input); break;
+            case BatchKind::STREAM: case BatchKind::UTF16: case BatchKind::ESCAPED: f(input); break;
             case BatchKind::PACK: for (const PackedInput& pi : pack) f(pi.input); break;
             case BatchKind::GZ_PACK: case BatchKind::GZ_WINDOW: case BatchKind::GZ_STREAM: for (const GzFile& g : gz) f(g.input); break;
         }
@@ -188,6 +194,22 @@ struct MatchPipeline {
         std::lock_guard<std::mutex> lk(mu);
         for (int k = 0; k < 3; ++k) u16_ms[k] += ms[k];
     }
+    // --unescape: the modes of every batch that is read as bytes (0: off), and what the decoded batches say about themselves, summed for -s
+    uint32_t unescape_modes = 0;
+    std::atomic<size_t> ue_batches{0};
+    std::atomic<unsigned long long> ue_in_bytes{0}, ue_text_bytes{0}, ue_counters[3] = {{0}, {0}, {0}};
+    double ue_ms[3] = {0, 0, 0};   // guarded by mu
+    void add_unescaped(const matchy_scanner_t* sc, const matchy_scan_result_t& r, size_t in_len) {
+        uint64_t c[3] = {0, 0, 0};
+        size_t text_len = 0;
+        float ms[3] = {0, 0, 0};
+        if (matchy_scan_result_unescaped(&r, nullptr, &text_len, c) != MATCHY_SUCCESS) return;
+        matchy_scanner_get_unescape_timing(sc, ms);
+        ++ue_batches; ue_in_bytes += in_len; ue_text_bytes += text_len;
+        for (int k = 0; k < 3; ++k) ue_counters[k] += c[k];
+        std::lock_guard<std::mutex> lk(mu);
+        for (int k = 0; k < 3; ++k) ue_ms[k] += ms[k];
+    }
     std::vector<unsigned long long> line_base;   // per input; the printer's (then --follow's)
     // arms the library for the batch about to be submitted, where its line bases are known
     void arm(Batch& b) {
@@ -234,6 +256,7 @@ struct MatchPipeline {
         switch (hb->kind) {
             case BatchKind::STREAM: rc = matchy_multi_scanner_submit(ms, hb->ptr, hb->len, hb, hb->reg); break;
             case BatchKind::UTF16: rc = matchy_multi_scanner_submit_utf16(ms, hb->ptr, hb->len, hb->byte_order, text, hb, hb->reg); break;
+            case BatchKind::ESCAPED: rc = matchy_multi_scanner_submit_escaped(ms, hb->ptr, hb->len, hb->unescape_modes, text, hb, hb->reg); break;
             case BatchKind::PACK: {
                 std::vector<uint32_t> starts;
                 for (const PackedInput& pi : hb->pack) starts.push_back(pi.start);
@@ -332,7 +355,7 @@ struct MatchPipeline {
         }
         // an armed gz pack comes back without its text: the library scans it with line context, and its "Lines with matches" are the
         // table's like those of any pack scanned with line context (plain batches of the same run are counted from their text as before)
-        // (an armed UTF-16 batch likewise: its count is the scan's own)
+        // (an armed UTF-16 or escaped batch likewise: its count is the scan's own)
         const bool table_counts = line_ctx || gather || (b.armed && b.text_on_device());
         if (table_counts && b.segmented()) {   // per segment, from the table the GPU filled
             const matchy_scan_segment_t* segs = nullptr;
@@ -393,6 +416,7 @@ struct MatchPipeline {
         Done* d = new Done();
         if (pl->whole_lines) pl->add_whole_lines(sc);
         if (((const Batch*)tag)->kind == BatchKind::UTF16) pl->add_utf16(sc, *r);
+        if (((const Batch*)tag)->kind == BatchKind::ESCAPED) pl->add_unescaped(sc, *r, ((const Batch*)tag)->len);
         pl->render(sc, *r, data, len, *(const Batch*)tag, *d);
         return d;
     }
@@ -460,6 +484,7 @@ struct MatchPipeline {
 // enc (--encoding): UTF16LE / UTF16BE read the input's byte stream — the mapped file, stdin, or what gzread returns — as UTF-16 in that
 // byte order, AUTO does so when the stream begins with FF FE or FE FF and reads anything else as bytes. A leading BOM of the byte order
 // in effect is skipped: it is not part of the text. The batches are cut behind 000A units (newline_cut16) and go out as they are.
+// pl.unescape_modes (--unescape): the batches are cut as ever and go out as escaped ones.
 bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t batch_bytes, uint64_t skip = 0, Encoding enc = Encoding::BYTES) {
     const bool gz = ends_with_ci(path, ".gz");
     // the byte order for a stream that begins with b[0 .. n): -1 = bytes; `bom` = bytes of the BOM to skip
@@ -490,6 +515,7 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
                 const size_t end = order >= 0 ? newline_cut16(base, pos, text_size, batch_bytes, (uint32_t)order) : newline_cut(base, pos, text_size, batch_bytes);
                 Batch b;
                 if (order >= 0) { b.kind = BatchKind::UTF16; b.byte_order = (uint32_t)order; }
+                else if (pl.unescape_modes) { b.kind = BatchKind::ESCAPED; b.unescape_modes = pl.unescape_modes; }
                 b.input = input; b.ptr = base + pos; b.len = end - pos;
                 b.reg = prefault_and_pin(b.ptr, b.len);
                 last_seq = pl.submit(std::move(b));
@@ -539,6 +565,7 @@ bool read_input(MatchPipeline& pl, size_t input, const std::string& path, size_t
         const size_t drop = off < skip ? (size_t)(skip - off) : 0;   // skip lies behind a '\n': what is left starts a line
         Batch b;
         if (order >= 0) { b.kind = BatchKind::UTF16; b.byte_order = (uint32_t)order; }
+        else if (pl.unescape_modes) { b.kind = BatchKind::ESCAPED; b.unescape_modes = pl.unescape_modes; }
         b.input = input; b.ptr = data.get() + drop; b.len = len - drop; b.own = std::move(data);
         pl.submit(std::move(b));
         return true;
@@ -822,6 +849,8 @@ struct MatchOptions {
     // --encoding=utf-16le|utf-16be|auto: UTF-16 inputs are transcoded on the GPU in front of the scan; `encoding_given`: the flag was there
     Encoding encoding = Encoding::BYTES;
     bool encoding_given = false;
+    // --unescape=percent|json|json+percent: the batches are decoded on the GPU in front of the scan (MATCHY_UNESCAPE_*; 0: off)
+    uint32_t unescape_modes = 0;
     // --gz-pieces[=BYTES] (with --gz-on-gpu): one large DEFLATE stream is inflated by many waves, in pieces of BYTES compressed bytes; 0 = off.
     // The default is the best of the sweep of tools/gz_pieces_timing.py: 4, 8 and 16 KiB lie within 3 % of each other on
     // level 6 log text, whose blocks have about 32 KiB; from 32 KiB on a piece holds more than one block and the time doubles.
@@ -881,6 +910,12 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
             if (b > 0xFFFFFFFFull || !gz_piece_bytes_valid((uint32_t)b)) { fprintf(stderr, "error: --gz-pieces=BYTES needs a power of two from 512 to 1048576, got '%s'\n", n.c_str()); return 2; }
             o.gz_pieces = (uint32_t)b;
         }
+        else if (eqval("--unescape", v)) {
+            if (v == "percent") o.unescape_modes = MATCHY_UNESCAPE_PERCENT;
+            else if (v == "json") o.unescape_modes = MATCHY_UNESCAPE_JSON;
+            else if (v == "json+percent") o.unescape_modes = MATCHY_UNESCAPE_JSON | MATCHY_UNESCAPE_PERCENT;
+            else { fprintf(stderr, "Error: Unknown escape grammar: %s. Use 'percent', 'json' or 'json+percent'\n", v.c_str()); return 1; }
+        }
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); return 2; }
         else o.pos.push_back(a);
     }
@@ -897,6 +932,18 @@ int parse_match_options(int argc, char** argv, MatchOptions& o) {
         if (o.gz_stream_windows) return refuse("--encoding is not supported with --gz-stream-windows (it extends --gz-on-gpu)");
         if (o.gz_pieces) return refuse("--encoding is not supported with --gz-pieces (it extends --gz-on-gpu)");
         if (o.whole_lines) return refuse("--encoding is not supported with --whole-lines (whole-line queries read their input as bytes)");
+    }
+    if (o.unescape_modes) {
+        // the batches of an input are decoded whole, on the GPU, in front of a plain scan: no segments, no compressed bytes, no queries
+        if (o.follow) return refuse("--unescape is not supported with --follow (a followed file is scanned as it grows, as it is)");
+        if (o.pack) return refuse("--unescape is not supported with --pack-inputs (a decoded batch has no segments)");
+        if (o.gz_gpu) return refuse("--unescape is not supported with --gz-on-gpu (the GPU inflates .gz inputs into the text that is scanned; without the flag they are inflated on the host and decoded)");
+        if (o.gz_members) return refuse("--unescape is not supported with --gz-members (it extends --gz-on-gpu)");
+        if (o.gz_windows) return refuse("--unescape is not supported with --gz-windows (it extends --gz-on-gpu)");
+        if (o.gz_stream_windows) return refuse("--unescape is not supported with --gz-stream-windows (it extends --gz-on-gpu)");
+        if (o.gz_pieces) return refuse("--unescape is not supported with --gz-pieces (it extends --gz-on-gpu)");
+        if (o.whole_lines) return refuse("--unescape is not supported with --whole-lines (whole-line queries read their input as it is)");
+        if (o.encoding_given) return refuse("--unescape is not supported with --encoding (one front pass per batch: transcode the input first)");
     }
     if (o.gz_windows && !(o.gz_gpu && o.gz_members)) return refuse("--gz-windows needs --gz-on-gpu --gz-members (it extends them to multi-member files larger than a batch)");
     if (o.gz_stream_windows && !(o.gz_gpu && o.gz_pieces)) return refuse("--gz-stream-windows needs --gz-on-gpu --gz-pieces (it extends them to one DEFLATE stream larger than a batch)");
@@ -1055,6 +1102,10 @@ void report_stats(const MatchOptions& o, const MatchPipeline& pl, const GzReader
     if (pl.u16_inputs.load())
         fprintf(stderr, "[INFO] UTF-16: %zu inputs transcoded on the GPU in %zu batches (%llu code units, %llu U+FFFD written; count %.2f ms, prefix %.2f ms, write %.2f ms)\n",
                 pl.u16_inputs.load(), pl.u16_batches.load(), pl.u16_units.load(), pl.u16_replaced.load(), pl.u16_ms[0], pl.u16_ms[1], pl.u16_ms[2]);
+    if (o.unescape_modes)
+        fprintf(stderr, "[INFO] Unescape: %zu batches decoded on the GPU (%llu -> %llu bytes; %llu escapes, %llu U+FFFD written, %llu LF escapes as spaces; count %.2f ms, prefix %.2f ms, write %.2f ms)\n",
+                pl.ue_batches.load(), pl.ue_in_bytes.load(), pl.ue_text_bytes.load(), pl.ue_counters[0].load(), pl.ue_counters[1].load(), pl.ue_counters[2].load(), pl.ue_ms[0],
+                pl.ue_ms[1], pl.ue_ms[2]);
 }
 
 }  // namespace
@@ -1096,8 +1147,9 @@ int cmd_match(int argc, char** argv) {
     pl.json = o.format == "json";
     // --gz-on-gpu without records to render: no text comes back from a gz pack, so "Lines with matches" is counted on the GPU for every
     // batch (line context; with --format summary it changes nothing that is printed)
-    // (--encoding likewise: the text of a UTF-16 batch is made on the device and stays there when nothing is rendered from it)
-    pl.line_ctx = o.line_numbers || o.input_line || ((o.gz_gpu || o.encoding_given) && !pl.json);
+    // (--encoding and --unescape likewise: the text of such a batch is made on the device and stays there when nothing is rendered from it)
+    pl.line_ctx = o.line_numbers || o.input_line || ((o.gz_gpu || o.encoding_given || o.unescape_modes) && !pl.json);
+    pl.unescape_modes = o.unescape_modes;
     pl.input_line = o.input_line; pl.gather = o.gather_lines; pl.gz_members = o.gz_members; pl.whole_lines = o.whole_lines;
     pl.render_gpu = o.render_gpu;   // takes effect with --format json only (MatchPipeline::arm)
     if (pl.line_ctx) matchy_multi_scanner_set_line_context(ms, true);

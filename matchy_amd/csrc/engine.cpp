@@ -1602,6 +1602,36 @@ Scanner::GzBatch Scanner::gz_inflate_stream(const uint8_t* packed, size_t packed
 void Scanner::gz_queue_results(bool want_text) { gz_->queue_results(want_text, host_stream_); }
 GzInflate::Result Scanner::gz_finish() { return gz_->finish(); }
 
+// The input of a front pass (utf16.h, unescape.h): device memory is read where it lies when it is aligned for 16-byte loads; device
+// memory that is not is copied, and host memory travels the way a piece of scan_host does — the whole pages inside it pinned for the
+// copy (or found pinned by this library), the bytes in front of and behind them as they are
+template <class Pass>
+const uint8_t* Scanner::front_pass_input(Pass& pass, HostPin& pin, const uint8_t* src, size_t len) {
+    pin.release();
+    hipPointerAttribute_t attr{};
+    const bool on_device = len && hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    if (len && !on_device) (void)hipGetLastError();   // a plain host pointer is no error
+    if (on_device && ((uintptr_t)src & 15u)) {
+        uint8_t* dst = pass.input_buffer(len);
+        MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToDevice, host_stream_));
+        return dst;
+    }
+    if (len && !on_device) {
+        uint8_t* dst = pass.input_buffer(len);
+        static const bool no_reg = getenv("MATCHY_AMD_NO_REGISTER") != nullptr;
+        uintptr_t a = 0, b = 0;
+        if (!no_reg && len >= ((size_t)4 << 20) && inner_pages(src, len, a, b) && pins::acquire(a, b)) {
+            pin.a = a; pin.b = b;
+            const size_t head = (size_t)(a - (uintptr_t)src), mid = (size_t)(b - a), tail = len - head - mid;
+            if (head) MXY_HIP(hipMemcpyAsync(dst, src, head, hipMemcpyHostToDevice, host_stream_));
+            MXY_HIP(hipMemcpyAsync(dst + head, (const void*)a, mid, hipMemcpyHostToDevice, host_stream_));
+            if (tail) MXY_HIP(hipMemcpyAsync(dst + head + mid, (const void*)b, tail, hipMemcpyHostToDevice, host_stream_));
+        } else MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, host_stream_));
+        return dst;
+    }
+    return src;
+}
+
 // UTF-16 inputs (utf16.h). Like a gz scan, the pass and the scan behind it share this scanner's own stream.
 Scanner::GzBatch Scanner::utf16_transcode(const uint8_t* src, size_t len, uint32_t byte_order) {
     if (segments_ && segments_->pending()) {
@@ -1613,31 +1643,7 @@ Scanner::GzBatch Scanner::utf16_transcode(const uint8_t* src, size_t len, uint32
     MXY_HIP(hipSetDevice(ddb_->device));
     host_stream_.create(hipStreamNonBlocking);
     if (!utf16_) utf16_ = std::make_unique<Utf16Transcode>();
-    utf16_pin_.release();
-    // the input: device memory is read where it lies when it is aligned for 16-byte loads; device memory that is not is copied, and host
-    // memory travels the way a piece of scan_host does — the whole pages inside it pinned for the copy (or found pinned by this
-    // library), the bytes in front of and behind them as they are
-    const uint8_t* in = src;
-    hipPointerAttribute_t attr{};
-    const bool on_device = len && hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeDevice;
-    if (len && !on_device) (void)hipGetLastError();   // a plain host pointer is no error
-    if (on_device && ((uintptr_t)src & 15u)) {
-        uint8_t* dst = utf16_->input_buffer(len);
-        MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToDevice, host_stream_));
-        in = dst;
-    } else if (len && !on_device) {
-        uint8_t* dst = utf16_->input_buffer(len);
-        static const bool no_reg = getenv("MATCHY_AMD_NO_REGISTER") != nullptr;
-        uintptr_t a = 0, b = 0;
-        if (!no_reg && len >= ((size_t)4 << 20) && inner_pages(src, len, a, b) && pins::acquire(a, b)) {
-            utf16_pin_.a = a; utf16_pin_.b = b;
-            const size_t head = (size_t)(a - (uintptr_t)src), mid = (size_t)(b - a), tail = len - head - mid;
-            if (head) MXY_HIP(hipMemcpyAsync(dst, src, head, hipMemcpyHostToDevice, host_stream_));
-            MXY_HIP(hipMemcpyAsync(dst + head, (const void*)a, mid, hipMemcpyHostToDevice, host_stream_));
-            if (tail) MXY_HIP(hipMemcpyAsync(dst + head + mid, (const void*)b, tail, hipMemcpyHostToDevice, host_stream_));
-        } else MXY_HIP(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, host_stream_));
-        in = dst;
-    }
+    const uint8_t* in = front_pass_input(*utf16_, utf16_pin_, src, len);
     utf16_->launch(in, len, byte_order, n_cu_, true, host_stream_);   // always timed: four event records per batch, for `matchy match -s`
     return GzBatch{utf16_->device_text(), utf16_->text_len(), host_stream_};
 }
@@ -1646,6 +1652,28 @@ void Scanner::utf16_queue_text(bool want_text) { utf16_->queue_results(want_text
 Utf16Transcode::Result Scanner::utf16_finish() {
     const Utf16Transcode::Result r = utf16_->finish();
     utf16_pin_.release();   // behind the fetch: the copy is done
+    return r;
+}
+
+// Percent- and JSON-escaped inputs (unescape.h): the same shape
+Scanner::GzBatch Scanner::unescape(const uint8_t* src, size_t len, uint32_t modes) {
+    if (segments_ && segments_->pending()) {
+        set_segments(nullptr, 0);
+        throw ParamError{"escaped inputs and segments cannot be combined"};
+    }
+    if (whole_lines_) throw ParamError{"escaped inputs and whole-line mode cannot be combined"};
+    Unescape::check(src, len, modes);
+    MXY_HIP(hipSetDevice(ddb_->device));
+    host_stream_.create(hipStreamNonBlocking);
+    if (!unescape_) unescape_ = std::make_unique<Unescape>();
+    const uint8_t* in = front_pass_input(*unescape_, unescape_pin_, src, len);
+    unescape_->launch(in, len, modes, n_cu_, true, host_stream_);   // always timed, like the UTF-16 pass
+    return GzBatch{unescape_->device_text(), unescape_->text_len(), host_stream_};
+}
+void Scanner::unescape_queue_text(bool want_text) { unescape_->queue_results(want_text, host_stream_); }
+Unescape::Result Scanner::unescape_finish() {
+    const Unescape::Result r = unescape_->finish();
+    unescape_pin_.release();   // behind the fetch: the copy is done
     return r;
 }
 

@@ -17,6 +17,7 @@
 #include "result_layout.h"
 #include "scan_types.h"
 #include "segments.h"
+#include "unescape.h"
 #include "utf16.h"
 #include "whole_lines.h"
 
@@ -297,6 +298,17 @@ public:
     Utf16Transcode::Result utf16_finish();
     // milliseconds of count, prefix and write of the last transcoded batch (recorded for every batch, with or without set_profile)
     void utf16_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (utf16_) utf16_->timing(out_ms); }
+    // Percent- and JSON-escaped inputs (unescape.hip): the contract of the three utf16_* members above. unescape queues the steps of the
+    // pass on this scanner's own stream and returns, when the text's length has reached the host, the decoded batch in device memory;
+    // modes: unescape::MODE_PERCENT, MODE_JSON or both (percent(json(x))). `src` is host or device memory. A pending segment table
+    // (dropped then), whole-line mode, modes outside 1..3 and an input of 0x7FFF0000 bytes or more fail the call with ParamError.
+    // unescape_queue_text goes behind the scan's kernels, unescape_finish behind the fetch. Never called, nothing of it is allocated,
+    // launched or copied.
+    GzBatch unescape(const uint8_t* src, size_t len, uint32_t modes);
+    void unescape_queue_text(bool want_text);
+    Unescape::Result unescape_finish();
+    // milliseconds of count, prefix and write of the last decoded batch (recorded for every batch, with or without set_profile)
+    void unescape_timing(float out_ms[3]) const { for (int k = 0; k < 3; ++k) out_ms[k] = 0; if (unescape_) unescape_->timing(out_ms); }
     // Whole-line queries (whole_lines.hip): while on, a lookup scan treats its buffer as a list of queries, one per line, and looks every
     // line up like Database::lookup does a single query; extraction (k_anchor, the validators, the extract flags) plays no part.
     // scan_host reads the setting itself; the other entries of a lookup scan call arm_whole_lines in front of arm_segments, which sets
@@ -462,6 +474,10 @@ private:
         void release();
         ~HostPin() { release(); }
     } utf16_pin_;
+    std::unique_ptr<Unescape> unescape_;       // created by the first unescape
+    HostPin unescape_pin_;                     // the same for unescape, until unescape_finish or the next batch
+    // what utf16_transcode and unescape share: the input where the pass can read it (device memory, 16-byte aligned), queued on host_stream_
+    template <class Pass> const uint8_t* front_pass_input(Pass& pass, HostPin& pin, const uint8_t* src, size_t len);   // engine.cpp only
     // what gz_inflate and gz_inflate_files share: device, stream, the pass; launch(GzInflate&) plans and queues; then the segment table
     template <class Launch> GzBatch gz_pass(Launch&& launch);   // engine.cpp only
     // whole-line queries: the buffers of the front end (grown with the candidate list, reused between scans), created by the first scan in the mode

@@ -46,8 +46,8 @@ struct RenderSpec {
     }
 };
 // what a batch is: set by the submit call that queued it (matchy_multi_scanner_submit / _submit_near, _submit_segments, _submit_gz,
-// _submit_gz_files, _submit_gz_window, _submit_gz_stream, _submit_utf16, in this order), read by the worker that scans it
-enum class JobKind { PLAIN, SEGMENTS, GZ_MEMBERS, GZ_FILES, GZ_WINDOW, GZ_STREAM, UTF16 };
+// _submit_gz_files, _submit_gz_window, _submit_gz_stream, _submit_utf16, _submit_escaped, in this order), read by the worker that scans it
+enum class JobKind { PLAIN, SEGMENTS, GZ_MEMBERS, GZ_FILES, GZ_WINDOW, GZ_STREAM, UTF16, ESCAPED };
 struct MultiJob {
     JobKind kind;
     const uint8_t* data;                      // the caller's bytes: text, or (gz kinds) the compressed pack
@@ -63,8 +63,10 @@ struct MultiJob {
     uint32_t carry_cap = 0, window_flags = 0; // GZ_WINDOW
     std::unique_ptr<matchy_gz_stream_state_t> stream_state;   // GZ_STREAM: the state of the window (none for the first), copied at the submit like the carry
     uint32_t stream_text_cap = 0;             // GZ_STREAM (carry, carry_cap and window_flags as for GZ_WINDOW)
-    bool gz_text = false;                     // gz kinds: the inflated text comes back with the result; UTF16: the UTF-8 text
+    bool gz_text = false;                     // gz kinds: the inflated text comes back with the result; UTF16: the UTF-8 text; ESCAPED: the decoded text
     uint32_t byte_order = 0;                  // UTF16
+    uint32_t unescape_modes = 0;              // ESCAPED
+    bool has_front_pass() const { return kind == JobKind::UTF16 || kind == JobKind::ESCAPED; }
     std::shared_ptr<const RenderSpec> render; // matchy_multi_scanner_set_render, taken by the submit that followed it
     bool is_gz() const { return kind == JobKind::GZ_MEMBERS || kind == JobKind::GZ_FILES || kind == JobKind::GZ_WINDOW || kind == JobKind::GZ_STREAM; }
 };
@@ -136,8 +138,8 @@ struct MultiScanner {
             else if (j.len || j.kind != JobKind::PLAIN) {   // an empty batch with a table is scanned too: its result carries the table
                 matchy_scanner_t* sc = scanners[w];
                 // an armed gz pack without its text: nothing of it can be counted on the host afterwards, so this scan runs with line context
-                // (lines with matches per segment) whatever the setting is; an armed UTF-16 batch without its text likewise
-                matchy_scanner_set_line_context(sc, want_lines || ((j.is_gz() || j.kind == JobKind::UTF16) && j.render && !j.gz_text));
+                // (lines with matches per segment) whatever the setting is; an armed UTF-16 or escaped batch without its text likewise
+                matchy_scanner_set_line_context(sc, want_lines || ((j.is_gz() || j.has_front_pass()) && j.render && !j.gz_text));
                 matchy_scanner_set_hit_lines(sc, want_hit_lines);
                 if (touch_tally) matchy_scanner_set_tally(sc, want_tally);
                 if (j.is_gz()) (void)matchy_scanner_set_gz_pieces(sc, want_gz_pieces);   // tested by matchy_multi_scanner_set_gz_pieces
@@ -152,10 +154,12 @@ struct MultiScanner {
                     case JobKind::GZ_WINDOW: d.status = matchy_scanner_scan_gz_window(sc, j.data, j.len, &window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                     case JobKind::GZ_STREAM: d.status = matchy_scanner_scan_gz_stream(sc, j.data, j.len, &stream_window, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                     case JobKind::UTF16: d.status = matchy_scanner_scan_utf16(sc, j.data, j.len, j.byte_order, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
+                    case JobKind::ESCAPED: d.status = matchy_scanner_scan_escaped(sc, j.data, j.len, j.unescape_modes, MATCHY_SCAN_FETCH_SORTED, j.gz_text, &d.res); break;
                 }
-                if (j.kind == JobKind::UTF16) {   // the batch's data / len become the UTF-8 text, which the result owns
+                if (j.has_front_pass()) {   // the batch's data / len become the text the pass wrote, which the result owns
                     d.data = nullptr; d.len = 0;
-                    if (d.status == MATCHY_SUCCESS) (void)matchy_scan_result_utf16(&d.res, &d.data, &d.len, nullptr, nullptr);
+                    if (d.status == MATCHY_SUCCESS && j.kind == JobKind::UTF16) (void)matchy_scan_result_utf16(&d.res, &d.data, &d.len, nullptr, nullptr);
+                    if (d.status == MATCHY_SUCCESS && j.kind == JobKind::ESCAPED) (void)matchy_scan_result_unescaped(&d.res, &d.data, &d.len, nullptr);
                 }
                 if (j.is_gz()) {   // the batch's data / len become the inflated text, which the result owns
                     d.data = nullptr; d.len = 0;
@@ -403,6 +407,14 @@ int32_t matchy_multi_scanner_submit_utf16(matchy_multi_scanner_t* h, const uint8
     if (const char* why = utf16_refusal(data, len, byte_order)) { set_error(std::string("matchy_multi_scanner_submit_utf16: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
     MultiJob j{JobKind::UTF16, data, len, tag};
     j.pinned = pinned_range; j.gz_text = want_text; j.byte_order = byte_order;
+    return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
+}
+int32_t matchy_multi_scanner_submit_escaped(matchy_multi_scanner_t* h, const uint8_t* data, size_t len, uint32_t modes, bool want_text, void* tag,
+                                            const void* pinned_range) {
+    if (!h) { set_error("matchy_multi_scanner_submit_escaped: no scanner"); return MATCHY_ERROR_INVALID_PARAM; }
+    if (const char* why = unescape_refusal(data, len, modes)) { set_error(std::string("matchy_multi_scanner_submit_escaped: ") + why); return MATCHY_ERROR_INVALID_PARAM; }
+    MultiJob j{JobKind::ESCAPED, data, len, tag};
+    j.pinned = pinned_range; j.gz_text = want_text; j.unescape_modes = modes;
     return enqueue(reinterpret_cast<MultiScanner*>(h), std::move(j));
 }
 size_t matchy_multi_scanner_pending(const matchy_multi_scanner_t* h) {
